@@ -10,9 +10,15 @@ forward solve (fused kernel) + loss + continuous-adjoint backward (fused kernel)
 all-reduce of the flat gradient] + Adam update, on BASELINE.json configs[1]/[2] (B=4096 per GPU, 200 raw
 observations -> 399 rectilinear knots, 20 channels incl. time, H=HH=32, nl=3, RK4-3/8, step 1).
 `value` = sample-steps/s = (samples processed by all ranks) * (T-1) / time, fp32 throughout.
-The headline line is WEAK scaling (B=4096 per GPU, the sharding rule of the task statement); for N>1 the same run also
+The headline line is WEAK scaling (B=4096 per GPU, the sharding rule of the task statement); for N>1 a --full run also
 times the north-star's STRONG-scaling workload (global B=4096 sharded over the N ranks) and reports it under "strong".
 Inputs: raw synthetic series (ncde_amd.data) turned into coefficients by the GPU builders (csrc/ncde_prepare.hip).
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the benchmark
+measures or checks, outside the timed region: the kernel rooflines, z_T against the golden fixture, the forward-only /
+adjoint=False / all-fp32-MFMA legs, the other scaling mode and the all-reduce time (N>1), the CPU baseline and the other
+BASELINE configs.  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32): the logits,
+the loss, every parameter's gradient and every parameter after the optimizer update (rank 0's shard for N>1).
 """
 import argparse
 import ctypes
@@ -267,10 +273,12 @@ class Workload:
     def step(self):
         return D.train_step(self.model, self.bucket, self.opt, self.coeffs, self.labels, self.loss_fn)
 
-    def timed(self, steps, warmup, world, dev):
-        """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks (seconds)."""
+    def timed(self, steps, warmup, world, dev, capture=False):
+        """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks (seconds).
+        `capture`: keep the model output of the last timed step in `self.last_out` (a forward hook that only stores a reference)."""
         for _ in range(warmup):
             self.step()
+        hook = self.model.register_forward_hook(lambda m, i, o: setattr(self, "last_out", o)) if capture else None
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
@@ -281,11 +289,49 @@ class Workload:
         if world > 1:
             torch.distributed.barrier()
         dt = time.perf_counter() - t0
+        if hook is not None:
+            hook.remove()
+        self.last_loss = loss
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         if world > 1:
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         assert torch.isfinite(loss).item(), "training diverged"
         return float(tmax.item()), float(loss)
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_LOGITS = 1 << 20      # more logits than this (a --batch override): a fixed, seeded sample of the rows
+
+
+def dump_outputs(out_dir, w):
+    """What the last timed step handed its caller, as float32 .npy files: the logits (model output), the loss, each parameter's
+    gradient (after the all-reduce for N>1) and each parameter after the optimizer update.  Call right after `w.timed(...,
+    capture=True)`, before anything else touches the model."""
+    arrays = {"logits": w.last_out.detach(), "loss": w.last_loss.reshape(1)}
+    for name, p in w.model.named_parameters():
+        key = name.replace(".", "_")
+        arrays["grad_" + key] = p.grad if p.grad is not None else torch.zeros_like(p)
+        arrays["param_" + key] = p.detach()
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    if arrays["logits"].shape[0] > DUMP_MAX_LOGITS:
+        rows = np.sort(np.random.default_rng(0).choice(arrays["logits"].shape[0], DUMP_MAX_LOGITS, replace=False))
+        arrays["logits"] = arrays["logits"][rows]
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs to dump: %d bytes" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def kernel_names(model, c, coeffs):
+    """(forward, adjoint) kernel names the C-ABI dispatches this workload to (host-side query, nothing is launched but the read-in)."""
+    spec = model.func.fused_spec()
+    with torch.no_grad():
+        z0 = model.initial_linear(coeffs[:, 0, :c["C"]]).contiguous()
+    p = solver.build_problem(coeffs, "cubic" if c["interpolation"] == "cubic" else "linear", z0, spec, c["solver"], _lib.OUT_INTERVAL,
+                             model.kernel_flags)
+    lib = _lib.lib()
+    return tuple((lib.ncde_kernel_name(ctypes.byref(p), k) or b"?").decode() for k in (0, 1))
 
 
 def _pmc_summary(config, B_local):
@@ -568,10 +614,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"),
-                    help="which workload the headline `value` is quoted on; with N>1 the other one is timed too")
+                    help="which workload the headline `value` is quoted on; with --full and N>1 the other one is timed too")
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU (weak) / global (strong) batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward-only / adjoint=False / other-scaling legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines, golden z_T error, the extra legs, all-reduce time, CPU baseline, other configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the forward-only / adjoint=False / other-scaling legs")
     ap.add_argument("--cpu-sample", type=int, default=1024)
     args = ap.parse_args()
 
@@ -611,10 +661,12 @@ def main():
     B_local, B_total, lo = shard(args.scaling)
     w = Workload(c, B_local, B_total, lo, dev)
     model, coeffs, T = w.model, w.coeffs, w.T
-    z_err = golden_z_err(model, c, coeffs) if (rank == 0 and args.config == "cfg2" and lo == 0) else None
-    dt, loss = w.timed(args.steps, args.warmup, world, dev)
+    z_err = golden_z_err(model, c, coeffs) if (args.full and rank == 0 and args.config == "cfg2" and lo == 0) else None
+    dt, loss = w.timed(args.steps, args.warmup, world, dev, capture=args.dump_outputs is not None)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, w)
 
-    if world > 1:      # the step's one exchange in isolation: all-reduce of the flat fp32 gradient bucket, per rank, HIP events
+    if world > 1 and args.full:      # the step's one exchange in isolation: all-reduce of the flat fp32 gradient bucket, per rank, HIP events
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for _ in range(3):
             torch.distributed.all_reduce(w.bucket.flat)
@@ -631,7 +683,7 @@ def main():
 
     tf = td = t32 = None
     other = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # forward-only throughput (inference), same inputs
         with torch.no_grad():
             model(coeffs)
@@ -672,7 +724,7 @@ def main():
             del ow
 
     if rank == 0:
-        roofs, names = rooflines(model, c, coeffs, args.config, B_local, T)
+        roofs, names = rooflines(model, c, coeffs, args.config, B_local, T) if args.full else (None, kernel_names(model, c, coeffs))
         rec = {
             "metric": "solved integration steps/sec (fwd+adjoint)",
             "value": B_total * (T - 1) * args.steps / dt,
@@ -687,16 +739,16 @@ def main():
                                    % (args.config, c["interpolation"], c["solver"], B_local, B_total, c["L"], T, c["C"], c["H"],
                                       c["nl"], "RCCL grad all-reduce + " if world > 1 else ""),
                        "global_batch": B_total, "seq_len": c["L"], "parallelism": "dp%d" % world},
-            "roofline": roofs[1],
-            "roofline_forward": roofs[0],
             "loss": loss,
             "rccl_ranks": rccl_ranks, "collective_backend": backend if world > 1 else None,
-            "ms_allreduce": ms_allreduce,
+            "ms_allreduce": ms_allreduce if (args.full or world == 1) else None,
             "allreduce_floats": int(w.bucket.flat.numel()),
         }
+        if args.full:
+            rec["roofline"], rec["roofline_forward"] = roofs[1], roofs[0]
         # where the step's time goes outside the two solver kernels (cdeint's per-call host work, the
         # range-fault re-execution launches, the gradient reduction, read-in / read-out layers, loss, Adam -- and launch gaps)
-        kf, kb = roofs[0].get("ms_per_launch"), roofs[1].get("ms_per_launch")
+        kf, kb = (roofs[0].get("ms_per_launch"), roofs[1].get("ms_per_launch")) if args.full else (None, None)
         if kf is not None and kb is not None:
             rec["step_breakdown"] = {"forward_kernel_ms": kf, "backward_kernel_ms": kb, "other_ms": round(dt / args.steps * 1e3 - kf - kb, 4),
                                      "note": "other = ms_per_step - the two solver kernels' own time (HIP events): everything cdeint, autograd, "
@@ -717,14 +769,14 @@ def main():
             rec["strong" if args.scaling == "weak" else "weak"] = {"value": rec["value"], "ms_per_step": rec["ms_per_step"], "global_batch": B_total, "batch_per_gpu": B_local, "note": "identical to the headline at n_gpus=1"}
         elif other is not None:
             rec[other["scaling"]] = other
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # a BOUNDED sample: the same CPU work as 1024 samples of cfg2 (10 - 30 s with the repetitions) whatever the config -- cfg5 is
             # 113 x the flops per sample (798 steps of a 128-wide field over 80 channels): 16 samples there
             per_sample = lambda cc: flops_forward_per_sample_step(cc) * ((cc["L"] * 2 - 1 if cc["interpolation"] == "rectilinear" else cc["L"]) - 1)
             cpu_B = int(min(args.cpu_sample, max(16, 16 * round(args.cpu_sample * per_sample(CONFIGS["cfg2"]) / per_sample(c) / 16))))
             rec["cpu_baseline"] = cpu_baseline(c, w.fw, w.rw, cpu_B)
             rec["gpu_over_cpu"] = rec["value"] / rec["cpu_baseline"]["value"]
-        if world == 1 and args.config == "cfg2" and not args.no_extras and not args.batch:
+        if args.full and world == 1 and args.config == "cfg2" and not args.no_extras and not args.batch:
             # the other BASELINE shapes, OUTSIDE the headline's timed region: a few steps each so that the driver's record carries
             # all three (kernel names, step time, roofline with PMC traffic where a summary of these sources is committed)
             del w, model, coeffs

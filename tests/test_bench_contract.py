@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys(gpu_lib):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--cpu-sample", "32"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--cpu-sample", "32"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -59,3 +59,38 @@ def test_bench_prints_one_json_line_with_the_contract_keys(gpu_lib):
     assert rec["value"] > 10 * c["value"]                      # north star: >= 10x the CPU path
     # value = samples * (T-1) * steps / time
     assert abs(rec["value"] - 4096 * 398 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-6
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(gpu_lib, tmp_path):
+    """Without --full the line carries the headline only (no rooflines, CPU baseline, golden check or other configs); --dump-outputs
+    writes what the last timed step computed as float32 .npy files, and two runs with the same arguments write the same values."""
+    import numpy as np
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["dtype"] == "f32" and rec["higher_is_better"] is True
+    assert abs(rec["value"] - 4096 * 398 / (rec["ms_per_step"] * 1e-3)) / rec["value"] < 1e-6
+    for k in ("roofline", "roofline_forward", "cpu_baseline", "other_configs", "z_err_vs_golden", "forward_only_value", "fp32_mfma_value"):
+        assert k not in rec, k
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert "logits.npy" in files and "loss.npy" in files
+    assert {"grad_func_tanh_output_layer_0_weight.npy", "param_func_tanh_output_layer_0_weight.npy"} <= set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), f
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-7, err_msg=f)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "logits.npy").shape == (4096, 1)
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - rec["loss"]) <= 1e-6 * abs(rec["loss"])

@@ -1,6 +1,6 @@
 """Summarise rocprofv3 --pmc passes (counter_collection.csv files under a directory) per kernel:
     python tools/pmc_summary.py <dir> <out.json> [--config cfg2 --batch 4096 --passes 8 --note "..."]
---passes = forward (= backward) passes the profiled command executed (bench.py --steps K --warmup W --no-extras: K + W training steps
+--passes = forward (= backward) passes the profiled command executed (bench.py --steps K --warmup W --full --no-extras: K + W training steps
 + the 1 + 3 launches of its HIP-event timing leg): a pass of the windowed batch-tiled backward is MANY launches of two kernels, and
 `*_per_pass` = (sum over all launches seen) / passes is what bench.py reports as `roofline.traffic`.
 FETCH_SIZE / WRITE_SIZE are in KiB-like units of 1024 B per the counter definition; FETCH_SIZE of wide coalesced reads
