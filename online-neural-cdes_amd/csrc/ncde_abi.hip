@@ -284,7 +284,7 @@ int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
             if (!tiled_ok) return fail(NCDE_ERR_UNSUPPORTED, "the batch-tiled family does not cover this problem (pass %d)", pass);
             return 2;
         }
-        if (tiled_ok && ncde_tiled_preferred(p, pass)) return 2;
+        if (tiled_ok) return 2;
         if (y.variant) {
             if (!ncde_variant_supported(p, pass)) return fail(NCDE_ERR_UNSUPPORTED, "vector-field variant outside what ncde_variant.hip covers (pass %d)", pass);
             return 3;
@@ -294,7 +294,7 @@ int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
     }
     if (y.variant) {   // gated fields / evaluate / derivative inputs: the batch-tiled family knows the minimal-gated field;
                        // everything else runs on their own kernels on the generic structure
-        if (!(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) && ncde_tiled_supported(p, pass) && ncde_tiled_preferred(p, pass)) return 2;
+        if (!(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) && ncde_tiled_supported(p, pass)) return 2;
         if ((p->flags & NCDE_FLAG_FORCE_FAST) || !ncde_variant_supported(p, pass))
             return fail(NCDE_ERR_UNSUPPORTED, "vector-field variant outside what ncde_variant.hip covers (pass %d)", pass);
         return 3;
@@ -306,7 +306,7 @@ int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
         return 1;
     }
     if (fast_ok && !(p->flags & NCDE_FLAG_FORCE_GENERIC)) return 1;
-    if (!(p->flags & NCDE_FLAG_FORCE_GENERIC) && ncde_tiled_supported(p, pass) && ncde_tiled_preferred(p, pass)) return 2;
+    if (!(p->flags & NCDE_FLAG_FORCE_GENERIC) && ncde_tiled_supported(p, pass)) return 2;
     const int rc = generic_supported(p, y, pass);
     return rc == NCDE_OK ? 0 : rc;
 }

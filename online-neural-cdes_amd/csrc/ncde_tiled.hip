@@ -2925,15 +2925,14 @@ int tiled_dmax(const NcdeProblem* p) {
 }
 
 int tiled_fwd_ns(const NcdeProblem* p);
-// Split-bf16 output tiles in the forward: one sample tile per workgroup, last hidden width 32 / 64 / 128, unless the caller
-// asks for plain fp32-input MFMA (NCDE_FLAG_FP32_MFMA).
-bool tiled_fwd_bf(const NcdeProblem* p) {
+// which split the forward's output tiles multiply in: 0 none (fp32-input MFMA: NCDE_FLAG_FP32_MFMA, a last hidden width other than
+// 32 / 64 / 128, more than one sample tile per workgroup), 2 = 2-way split-fp16 (default), 1 = 3-way split-bf16 (NCDE_FLAG_SPLIT_BF16;
+// also what re-executes range-faulted sample tiles of mode 2)
+int tiled_fwd_split(const NcdeProblem* p) {
     const int dl = p->layer_out[p->n_layers - 1];
-    return !(p->flags & NCDE_FLAG_FP32_MFMA) && (dl == 32 || dl == 64 || dl == 128) && tiled_fwd_ns(p) == 1;
+    if ((p->flags & NCDE_FLAG_FP32_MFMA) || !(dl == 32 || dl == 64 || dl == 128) || tiled_fwd_ns(p) != 1) return 0;
+    return (p->flags & NCDE_FLAG_SPLIT_BF16) ? 1 : 2;
 }
-// which split the forward's output tiles multiply in: 0 none (fp32-input MFMA), 2 = 2-way split-fp16 (default), 1 = 3-way
-// split-bf16 (NCDE_FLAG_SPLIT_BF16; also what re-executes range-faulted sample tiles of mode 2)
-int tiled_fwd_split(const NcdeProblem* p) { return !tiled_fwd_bf(p) ? 0 : ((p->flags & NCDE_FLAG_SPLIT_BF16) ? 1 : 2); }
 int64_t tiled_fault_floats(const NcdeProblem* p) { return (((int64_t)(p->batch + 15) / 16 + 1) + 63) & ~(int64_t)63; }   // one word per tile + the weights' word
 // Floats of the fragment-ordered copy of the output layer (and of the gate head): 0 when the last hidden width is not one
 // of the whole-panel cases the kernels read packed.  The split-bf16 copy (forward, pass 0) takes 1.5 x.
@@ -3024,13 +3023,15 @@ int tiled_adj_pk(const NcdeProblem* p) {
     return (dlast == 256) ? 16 : ((dlast == 128) ? 8 : (dlast == 64 ? 4 : (dlast == 32 ? 2 : (dlast == 16 ? 1 : 0))));
 }
 
-// small square models: every weight fragment register-resident (see ncde_adj_tiled, RES)
-bool tiled_adj_res(const NcdeProblem* p) {
+// RES of the sweep (ncde_adj_tiled) for small square hidden stacks (H = every width = 16 PK, PK <= 4): 1 = every weight fragment
+// register-resident (small models, default time axis only), 2 = hidden matrices resident, output tiles streamed; 0 = streamed
+int tiled_adj_res(const NcdeProblem* p) {
     const int pk = tiled_adj_pk(p);
-    bool res = p->field_kind != NCDE_FIELD_MINIMAL && pk >= 1 && pk <= 4 && p->hidden == 16 * pk && p->hidden * p->channels / 16 <= 2 * TL_ADJ_NW &&
-               p->output != NCDE_OUT_TIMES;      // default time axis only (see ncde_adj_tiled)
-    for (int l = 0; l < p->n_layers; ++l) res = res && p->layer_out[l] == 16 * pk && p->layer_in[l] == 16 * pk;
-    return res;
+    bool sq = pk >= 1 && pk <= 4 && p->hidden == 16 * pk;
+    for (int l = 0; l < p->n_layers; ++l) sq = sq && p->layer_out[l] == 16 * pk && p->layer_in[l] == 16 * pk;
+    if (!sq) return 0;
+    if (p->field_kind != NCDE_FIELD_MINIMAL && p->hidden * p->channels / 16 <= 2 * TL_ADJ_NW && p->output != NCDE_OUT_TIMES) return 1;
+    return ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr ? 2 : 0;
 }
 // round 5: 128 < H <= 256 over hidden widths <= 128 runs the BIGH instantiation of the sweep: 4 waves (one per SIMD, 512 registers)
 // ... and so does a last hidden width of 256 (PK = 16: hidden widths 129 .. 256 are zero-padded to it, ncde_abi.hip) at any H <= 256
@@ -3050,18 +3051,11 @@ size_t tiled_adj_lds_base(const NcdeProblem* p) {
         return sizeof(float) * (size_t)(4 * p->hidden * 16 + (p->n_layers + 2) * D * 16 + p->channels * 16);
     return sizeof(float) * (size_t)(4 * p->hidden * 16 + (p->n_layers + 2) * D * 16 + p->channels * 16 + tiled_adj_nwv(p) * scw);
 }
-// hidden matrices resident, output tiles streamed (RES = 2): small square hidden stacks that do not qualify for RES = 1
-bool tiled_adj_res2(const NcdeProblem* p) {
-    const int pk = tiled_adj_pk(p);
-    bool ok = !tiled_adj_res(p) && pk >= 1 && pk <= 4 && p->hidden == 16 * pk && ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr;
-    for (int l = 0; l < p->n_layers; ++l) ok = ok && p->layer_out[l] == 16 * pk && p->layer_in[l] == 16 * pk;
-    return ok;
-}
 // split-bf16 record A / recompute in pass B: streamed weights, last hidden width 32 / 64 / 128, room for the split image of
 // x_L in the sweep's LDS, and the caller did not ask for plain fp32-input MFMA
 bool tiled_adj_bf(const NcdeProblem* p) {
     const int pk = tiled_adj_pk(p);
-    return !(p->flags & NCDE_FLAG_FP32_MFMA) && pk >= 2 && pk <= 8 && !tiled_adj_res(p) && p->field_input == NCDE_INPUT_MATMUL &&
+    return !(p->flags & NCDE_FLAG_FP32_MFMA) && pk >= 2 && pk <= 8 && tiled_adj_res(p) != 1 && p->field_input == NCDE_INPUT_MATMUL &&
            tiled_adj_lds_base(p) + (size_t)pk * 16 * 16 * 6 <= (size_t)kLdsLimit;
 }
 // ---- XCD-cooperative output phase (ncde_coop.h) --------------------------------------------------------------------------------------
@@ -3069,6 +3063,9 @@ struct CoopPlan {
     bool ok;
     int M, G;      // members per group, groups of ONE launch
     int chunk;     // sample tiles per launch: all of them, or -- round 6, more tiles than CUs -- the largest multiple of M that is resident at once
+    // workspace regions (float offsets, placed by the pass's plan): packed weight images, exchange area, {sw, 1/sw, max |Wo| bits at [8],
+    // the call's status word at [16]}, sync words
+    long long img, x, scale, sync;
 };
 constexpr int kCoopLdsFloats = 2 * 10 * 2 * 64 * 4 + 2 * 8 * 64 * 4 + 2 * 80 * 16 + 2 * 256 + 2 * 64 + 2 * 4 * 64 + 2 * 16 + 8;      // = COOP_LDS of ncde_adj_tiled
 size_t tiled_coop_lds(const NcdeProblem* p) {
@@ -3130,7 +3127,7 @@ void coop_mark_in_flight(hipStream_t st) {      // after the last cooperative la
 // state-unit blocks: C/4 in {5, 10, 20}) in registers.  Original field, matmul input, last hidden width 128, H <= 128, and every
 // workgroup resident at once (one per CU).
 CoopPlan tiled_coop_plan(const NcdeProblem* p) {
-    CoopPlan c{false, 0, 0, 0};
+    CoopPlan c{};
     if (p->flags & (NCDE_FLAG_NO_COOP | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_DEBUG_PROFILE)) return c;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL || p->n_layers < 1) return c;      // (any time axis: round 6)
     if (p->layer_out[p->n_layers - 1] != 128 || p->hidden > 128 || p->hidden % 16 || p->channels % 4) return c;
@@ -3156,33 +3153,50 @@ size_t tiled_adj_lds(const NcdeProblem* p) {
     return tiled_adj_lds_base(p) + (tiled_adj_bf(p) ? (size_t)tiled_adj_pk(p) * 16 * 16 * 6 : 0);
 }
 
-// The forward's cooperative output phase (ncde_fwd_tiled<.., COOP>): same groups, same packed weight images, an exchange area without
-// the partials.  Workspace regions (float offsets) behind the split-fp16 forward's own [h2 copy | bf16 copy | fault words].
-struct FwdCoopPlan {
-    bool ok;
-    int M, G, chunk;
-    long long img, x, scale, sync, end;
-};
-constexpr int kFwdCoopLdsFloats = 2 * 2 * 2048 + 2 * 2 * 1280 + 2 * 2 * 64 + 2 * 8 * 64 + 8 * 16 + 64 + 320 + 4 * 4 * 256 + 8;      // = CBX .. CFL of ncde_fwd_tiled
-FwdCoopPlan tiled_fwd_coop_plan(const NcdeProblem* p) {
-    FwdCoopPlan f{};
-    if (p->field_input != NCDE_INPUT_MATMUL || tiled_fwd_split(p) != 2 || tiled_fwd_ns(p) != 1) return f;
-    const CoopPlan c = tiled_coop_plan(p);
-    if (!c.ok) return f;
-    const size_t lds = sizeof(float) * ((size_t)16 * (size_t)(2 * p->hidden + 2 * tiled_dmax(p) + p->channels) + (size_t)kFwdCoopLdsFloats);
-    if (lds > (size_t)kLdsLimit) return f;
-    const int n_tiles = (p->batch + 15) / 16;
-    const CoopDims d{p->hidden, p->channels, 128, c.M, c.G};
-    long long off = 64 + tiled_pack_floats(p, false) + tiled_pack_floats(p, true) + tiled_fault_floats(p);
-    off = (off + 63) & ~63LL;
-    f.img = off; off += (long long)c.M * (coop_p_words() + coop_t_words());
-    f.x = off; off += d.per_tile_fwd() * c.chunk;
-    f.scale = off; off += 64;      // [0] sw, [1] 1 / sw, [8] max |Wo| bits, [16] the call's status word (KArgs.coop_status)
-    f.sync = off; off += 64 + coop_sync_words(c.G, c.chunk);
-    f.end = off + 64;
-    f.ok = true; f.M = c.M; f.G = c.G; f.chunk = c.chunk;
-    (void)n_tiles;
-    return f;
+// Whenever the static plan is cooperative -- before the run-time gate, whatever it decides -- the max |Wo| word and the call's status
+// word start at 0: ncde_coop_status_offset advertises the status word for every such call.
+hipError_t coop_zero_words(float* w, const CoopPlan& c, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(w + c.scale + 8, 0, sizeof(unsigned), st);
+    return e != hipSuccess ? e : hipMemsetAsync(w + c.scale + 16, 0, sizeof(unsigned), st);
+}
+// The cooperative launches' weight images (max |Wo|, then every group member's packed register image) and the KArgs fields that
+// every cooperative kernel reads.
+void coop_prepare(const NcdeProblem* p, KArgs* a, float* w, const CoopPlan& c, hipStream_t st) {
+    unsigned* amax = reinterpret_cast<unsigned*>(w + c.scale + 8);
+    hipLaunchKernelGGL(ncde_coop_absmax, dim3(512), dim3(256), 0, st, a->Wo, (long long)p->hidden * p->channels * 128, amax);
+    hipLaunchKernelGGL(ncde_coop_pack, dim3(1024), dim3(256), 0, st, a->Wo, (const unsigned*)amax, reinterpret_cast<unsigned*>(w + c.img),
+                       w + c.scale, p->channels, 128, c.M);
+    a->coop_img = reinterpret_cast<const unsigned*>(w + c.img);
+    a->coop_x = w + c.x;
+    a->coop_scale = w + c.scale;
+    a->coop_sync = reinterpret_cast<unsigned*>(w + c.sync);
+    a->coop_M = c.M;
+    a->coop_G = c.G;
+    a->coop_status = reinterpret_cast<unsigned*>(w + c.scale + 16);      // zeroed ONCE per call: a time-out in one window stops the later ones
+    a->coop_inject = (p->flags & NCDE_FLAG_COOP_FAULT_INJECT) ? 1 : 0;
+    a->coop_spin = a->coop_inject ? (1u << 12) : (unsigned)COOP_SPIN_LIMIT;
+}
+// KArgs of the cooperative launch over the sample tiles t0 .. t0 + tiles - 1: every per-sample pointer of the pass moves to the chunk
+// (the stage record keeps the batch stride of the whole batch; the adjoint's hidden-layer partials are per workgroup: rows t0 ..)
+KArgs coop_chunk_args(const KArgs& a, int batch, int t0, int tiles) {
+    KArgs c = a;
+    const long long z = 16LL * t0 * a.Hr;      // rows of z0 / grad_z0 / the stage record; out / z_out / grad_out: n_out rows per sample
+    c.B = std::min(batch - 16 * t0, 16 * tiles);
+    c.coeffs = a.coeffs + 16LL * t0 * a.cs_b;
+    c.coop_G = tiles / a.coop_M;
+    if (a.stages) { c.stages = a.stages + z; c.Brec = batch; }
+    if (a.grad_out) {      // adjoint
+        c.grad_out = a.grad_out + z * a.n_out;
+        c.grad_z0 = a.grad_z0 + z;
+        if (a.z_out) c.z_out = a.z_out + z * a.n_out;
+        c.gpart = a.gpart + (long long)t0 * a.gstride;
+        c.win_max = a.coop_sync + coop_sync_words(c.coop_G, tiles);
+    } else {      // forward
+        c.z0 = a.z0 + z;
+        c.out = a.out + z * a.n_out;
+        if (a.fault) c.fault = a.fault + t0;
+    }
+    return c;
 }
 
 bool tiled_adj_ok(const NcdeProblem* p) {
@@ -3216,10 +3230,8 @@ struct TiledAdjPlan {
     long long recS;      // cooperative sweep: per (stage, tile) scales for ncde_dwo_h2
     long long recA, recB, recC, recD, gpartA, gpartB, carry, pack, pack_bf, total;   // float offsets into the workspace
     long long theta_o;
-    // cooperative output phase: packed weight images, exchange area, {absmax bits, sw, 1/sw}, sync words
-    bool coop;
-    int coop_M, coop_G, coop_chunk;
-    long long coop_img, coop_x, coop_scale, coop_sync, coop_state;
+    CoopPlan coop;           // the cooperative sequence (coop.ok) and its regions
+    long long coop_state;    // ... + the sweep's hidden-dW accumulators while its registers hold Wo
 };
 
 // Record budget of one time window.  The continuous adjoint exists to be O(1) in memory (torchcde README: "slower but more
@@ -3281,7 +3293,7 @@ TiledAdjPlan tiled_adj_plan(const NcdeProblem* p, const Layout& y) {
     t.parts = 1;
     while (t.parts < 64 && (row_tiles / t.nrt) * 4 * t.parts < 4096 && 4 * t.parts * 2 <= t.n_st) t.parts *= 2;
     t.parts_pw = t.parts;
-    const CoopPlan cp = bf ? tiled_coop_plan(p) : CoopPlan{false, 0, 0, 0};
+    const CoopPlan cp = bf ? tiled_coop_plan(p) : CoopPlan{};
     if (cp.ok) {      // ncde_dwo_h2: 16 row tiles per workgroup, the sample-tile pairs of a stage split over `parts` workgroups
         int pp = 1;
         while (pp * 2 <= 32 && pp * 2 <= cp.chunk / 2) pp *= 2;
@@ -3291,21 +3303,284 @@ TiledAdjPlan tiled_adj_plan(const NcdeProblem* p, const Layout& y) {
     t.carry = off; off += 2LL * t.n_st * p->hidden * 16;
     t.pack = off; off += tiled_pack_floats(p, false, true);
     t.pack_bf = off; off += (bf && p->field_kind != NCDE_FIELD_MINIMAL) ? tiled_pack_floats(p, true) : 0;
-    t.coop = cp.ok;
+    t.coop = cp;
     if (cp.ok) {
-        t.coop_M = cp.M; t.coop_G = cp.G; t.coop_chunk = cp.chunk;
         off = (off + 63) & ~63LL;
         t.recS = off; off += tiles * 32 + 512;      // (+ the over-read of the last 1 KB chunk ncde_dwo_h2 fetches)
         const CoopDims d{p->hidden, p->channels, 128, cp.M, cp.G};
         off = (off + 63) & ~63LL;
-        t.coop_img = off; off += (long long)cp.M * (coop_p_words() + coop_t_words());
-        t.coop_x = off; off += d.per_tile() * cp.chunk;
-        t.coop_scale = off; off += 64;      // [0] sw, [1] 1 / sw, [8] max |Wo| bits, [16] the call's status word (KArgs.coop_status)
+        t.coop.img = off; off += (long long)cp.M * (coop_p_words() + coop_t_words());
+        t.coop.x = off; off += d.per_tile() * cp.chunk;
+        t.coop.scale = off; off += 64;
         t.coop_state = off; off += (long long)t.n_st * 2 * 8 * 512 * 4;      // the sweep's hidden-dW accumulators while its registers hold Wo: 2 x TL_DWT x NT float4 per workgroup
-        t.coop_sync = off; off += 64 + coop_sync_words(cp.G, cp.chunk);
+        t.coop.sync = off; off += 64 + coop_sync_words(cp.G, cp.chunk);
     }
     t.total = off + 64;
     return t;
+}
+
+// ---- kernel choice: lookups ----------------------------------------------------------------------------------------------------------
+using SweepFn = void (*)(KArgs);
+using PassBFn = void (*)(KArgs, int, int, float*);
+
+// per-workgroup forward, matmul input, fp32-input MFMA: NS sample tiles per workgroup, `small` = a state slice of <= 4 elements per thread
+template <int NS>
+SweepFn tiled_fwd_fn(bool g, bool small) {
+    if (g) return ncde_fwd_tiled<NS, TL_NW, 16, 1>;
+    return small ? ncde_fwd_tiled<NS, TL_NW, 4> : ncde_fwd_tiled<NS, TL_NW, 16>;
+}
+// forward instantiation with split output tiles: BF = 1 split-bf16, 2 split-fp16; resh = resident hidden fragments (0 / 2 / 4)
+template <int BF>
+SweepFn tiled_fwd_split_fn(bool g, bool small, int resh) {
+    if (resh == 2) return g ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF, 2> : ncde_fwd_tiled<1, TL_NW, 4, 0, BF, 2>;
+    if (resh == 4) return g ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF, 4> : ncde_fwd_tiled<1, TL_NW, 4, 0, BF, 4>;
+    if (g) return small ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF> : ncde_fwd_tiled<1, TL_NW, 16, 1, BF>;
+    return small ? ncde_fwd_tiled<1, TL_NW, 4, 0, BF> : ncde_fwd_tiled<1, TL_NW, 16, 0, BF>;
+}
+SweepFn tiled_fwd_direct_fn(bool g, bool small) {
+    if (g) return small ? ncde_fwd_tiled<1, TL_NW, 4, 1, 0, 0, 1> : ncde_fwd_tiled<1, TL_NW, 16, 1, 0, 0, 1>;
+    return small ? ncde_fwd_tiled<1, TL_NW, 4, 0, 0, 0, 1> : ncde_fwd_tiled<1, TL_NW, 16, 0, 0, 0, 1>;
+}
+
+// Adjoint, matmul input.  Columns: PK = 1, 2, 4, 8, 16 (last hidden width / 16); nullptr = no such instantiation.
+int tiled_pk_col(int pk) { return pk == 16 ? 4 : (pk == 8 ? 3 : (pk == 4 ? 2 : (pk == 2 ? 1 : 0))); }
+// the sweep, H <= 128: [gated][split-bf16 records][RES: 0 streamed weights, 1 every fragment resident, 2 hidden matrices resident]
+const SweepFn kAdjSweep[2][2][3][5] = {
+    {{{ncde_adj_tiled<1, TL_ADJ_NW>, ncde_adj_tiled<2, TL_ADJ_NW>, ncde_adj_tiled<4, TL_ADJ_NW>, ncde_adj_tiled<8, TL_ADJ_NW>},
+      {ncde_adj_tiled<1, TL_ADJ_NW, 1>, ncde_adj_tiled<2, TL_ADJ_NW, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 1>},
+      {ncde_adj_tiled<1, TL_ADJ_NW, 2>, ncde_adj_tiled<2, TL_ADJ_NW, 2>, ncde_adj_tiled<4, TL_ADJ_NW, 2>}},
+     {{nullptr, ncde_adj_tiled<2, TL_ADJ_NW, 0, 0, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 0, 0, 1>, ncde_adj_tiled<8, TL_ADJ_NW, 0, 0, 1>},
+      {},
+      {nullptr, ncde_adj_tiled<2, TL_ADJ_NW, 2, 0, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 2, 0, 1>}}},
+    {{{ncde_adj_tiled<1, TL_ADJ_NW, 0, 1>, ncde_adj_tiled<2, TL_ADJ_NW, 0, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 0, 1>, ncde_adj_tiled<8, TL_ADJ_NW, 0, 1>},
+      {},
+      {ncde_adj_tiled<1, TL_ADJ_NW, 2, 1>, ncde_adj_tiled<2, TL_ADJ_NW, 2, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 2, 1>}},
+     {{nullptr, ncde_adj_tiled<2, TL_ADJ_NW, 0, 1, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 0, 1, 1>, ncde_adj_tiled<8, TL_ADJ_NW, 0, 1, 1>},
+      {},
+      {nullptr, ncde_adj_tiled<2, TL_ADJ_NW, 2, 1, 1>, ncde_adj_tiled<4, TL_ADJ_NW, 2, 1, 1>}}}};
+// the BIGH sweep (one wave per SIMD: 128 < H <= 256, or last hidden width 256 -- fp32 records, hidden dW in the global partials):
+// [split-bf16 records]
+const SweepFn kAdjSweepWide[2][5] = {
+    {ncde_adj_tiled<1, 4, 0, 0, 0, 0, 1>, ncde_adj_tiled<2, 4, 0, 0, 0, 0, 1>, ncde_adj_tiled<4, 4, 0, 0, 0, 0, 1>, ncde_adj_tiled<8, 4, 0, 0, 0, 0, 1>,
+     ncde_adj_tiled<16, 4, 0, 0, 0, 0, 1>},
+    {nullptr, ncde_adj_tiled<2, 4, 0, 0, 1, 0, 1>, ncde_adj_tiled<4, 4, 0, 0, 1, 0, 1>, ncde_adj_tiled<8, 4, 0, 0, 1, 0, 1>}};
+// pass B over fp32 records (ncde_dwo_tiled) / split-bf16 records (ncde_dwo_pair).  Rows: original field with 1 / 2 / 4 row tiles per
+// wave; gated field: the first pass, the gate head's own pass (ncde_dwo_pair: both heads in one pass where the two accumulator sets
+// fit the register file, HEAD = 3; at 128 columns one pass per head)
+const PassBFn kAdjDwo[5][5] = {
+    {ncde_dwo_tiled<1>, ncde_dwo_tiled<2>, ncde_dwo_tiled<4>, ncde_dwo_tiled<8>, ncde_dwo_tiled<16, 0, 1>},
+    {ncde_dwo_tiled<1, 0, 2>, ncde_dwo_tiled<2, 0, 2>, ncde_dwo_tiled<4, 0, 2>, ncde_dwo_tiled<8, 0, 2>},
+    {ncde_dwo_tiled<1, 0, 4>, ncde_dwo_tiled<2, 0, 4>, ncde_dwo_tiled<4, 0, 4>, ncde_dwo_tiled<8, 0, 4>},
+    {ncde_dwo_tiled<1, 1>, ncde_dwo_tiled<2, 1>, ncde_dwo_tiled<4, 1>, ncde_dwo_tiled<8, 1>},
+    {ncde_dwo_tiled<1, 2>, ncde_dwo_tiled<2, 2>, ncde_dwo_tiled<4, 2>, ncde_dwo_tiled<8, 2>}};
+const PassBFn kAdjPair[5][5] = {
+    {nullptr, ncde_dwo_pair<2, 0, 1>, ncde_dwo_pair<4, 0, 1>, ncde_dwo_pair<8, 0, 1>},
+    {nullptr, ncde_dwo_pair<2, 0, 2>, ncde_dwo_pair<4, 0, 2>, ncde_dwo_pair<8, 0, 2>},
+    {nullptr, ncde_dwo_pair<2, 0, 4>, ncde_dwo_pair<4, 0, 4>, ncde_dwo_pair<8, 0, 4>},
+    {nullptr, ncde_dwo_pair<2, 3, 1>, ncde_dwo_pair<4, 3, 1>, ncde_dwo_pair<8, 1, 1>},
+    {nullptr, nullptr, nullptr, ncde_dwo_pair<8, 2, 1>}};
+
+// ---- forward plan: what ncde_tiled_forward launches, and its workspace [64 | packed output layer | split-bf16 copy | fault words | coop]
+constexpr int kFwdCoopLdsFloats = 2 * 2 * 2048 + 2 * 2 * 1280 + 2 * 2 * 64 + 2 * 8 * 64 + 8 * 16 + 64 + 320 + 4 * 4 * 256 + 8;      // = CBX .. CFL of ncde_fwd_tiled
+struct FwdPlan {
+    bool direct;        // evaluate / derivative input: layer 0 with its H + C columns zero-padded to a multiple of 16 (in `pack`)
+    int split;          // tiled_fwd_split
+    SweepFn fn, fx;     // the per-workgroup kernel; split-fp16: the split-bf16 kernel that re-executes range-faulted sample tiles
+    size_t lds;         // of fn and fx (direct modes: before the LDS-resident matrices, tiled_direct_residency)
+    int grid;
+    long long npack, pack, pack_bf, fault, end;      // floats of the packed copy; float offsets into the workspace (end: its size)
+    CoopPlan coop;      // the cooperative output phase (ncde_fwd_tiled<.., COOP>): the reverse sweep's groups and weight images
+    SweepFn fc;
+    size_t lds_coop;
+    const char* name;
+};
+FwdPlan tiled_fwd_plan(const NcdeProblem* p) {      // (p: ncde_tiled_supported for pass 0)
+    FwdPlan f{};
+    const bool g = p->field_kind == NCDE_FIELD_MINIMAL;
+    f.direct = p->field_input != NCDE_INPUT_MATMUL;
+    f.split = f.direct ? 0 : tiled_fwd_split(p);
+    const int ns = f.direct ? 1 : tiled_fwd_ns(p);      // sample tiles per workgroup
+    f.lds = tiled_fwd_lds(p, ns);
+    f.grid = (p->batch + ns * 16 - 1) / (ns * 16);
+    const bool small = p->hidden * ns * 16 <= 4 * TL_THREADS;   // state slice of <= 4 elements per thread: fewer live registers
+    if (f.direct) {
+        f.fn = tiled_fwd_direct_fn(g, small);
+        f.npack = (long long)p->layer_out[0] * ((p->layer_in[0] + 15) & ~15);
+        f.name = g ? "ncde_fwd_tiled<NS1,gated,direct>" : "ncde_fwd_tiled<NS1,direct>";
+    } else if (f.split) {
+        // small square hidden stack (H = every width = 32 or 64): hidden fragments resident
+        bool sq = (p->hidden == 32 || p->hidden == 64) && ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr;
+        for (int l = 0; l < p->n_layers; ++l) sq = sq && p->layer_out[l] == p->hidden && p->layer_in[l] == p->hidden;
+        const int resh = !sq ? 0 : (p->hidden == 32 ? 2 : 4);
+        f.fn = f.split == 2 ? tiled_fwd_split_fn<2>(g, small, resh) : tiled_fwd_split_fn<1>(g, small, resh);
+        if (f.split == 2) f.fx = tiled_fwd_split_fn<1>(g, small, resh);
+        f.npack = tiled_pack_floats(p, f.split == 1);
+        if (f.split == 2) f.name = g ? "ncde_fwd_tiled<NS1,gated,fp16x2>" : "ncde_fwd_tiled<NS1,fp16x2>";
+        else f.name = g ? "ncde_fwd_tiled<NS1,gated,bf16>" : "ncde_fwd_tiled<NS1,bf16>";
+    } else {
+        switch (ns) {
+            case 4: f.fn = tiled_fwd_fn<4>(g, small); f.name = g ? "ncde_fwd_tiled<NS4,gated>" : "ncde_fwd_tiled<NS4>"; break;
+            case 2: f.fn = tiled_fwd_fn<2>(g, small); f.name = g ? "ncde_fwd_tiled<NS2,gated>" : "ncde_fwd_tiled<NS2>"; break;
+            default: f.fn = tiled_fwd_fn<1>(g, small); f.name = g ? "ncde_fwd_tiled<NS1,gated>" : "ncde_fwd_tiled<NS1>"; break;
+        }
+        f.npack = tiled_pack_floats(p, false);
+    }
+    long long off = 64;
+    f.pack = off; off += f.npack;
+    if (f.split == 2) {      // split-fp16: its own copy, the split-bf16 copy of the re-execution launch, fault words
+        f.pack_bf = off; off += tiled_pack_floats(p, true);
+        f.fault = off; off += tiled_fault_floats(p);
+        f.coop = tiled_coop_plan(p);
+        f.fc = ncde_fwd_tiled<1, TL_NW, 4, 0, 2, 0, 0, 1>;
+        f.lds_coop = sizeof(float) * ((size_t)16 * (size_t)(2 * p->hidden + 2 * tiled_dmax(p) + p->channels) + (size_t)kFwdCoopLdsFloats);
+        f.coop.ok = f.coop.ok && f.lds_coop <= (size_t)kLdsLimit;
+    }
+    if (f.coop.ok) {      // same groups and packed weight images as the reverse sweep, an exchange area without the partials
+        const CoopDims d{p->hidden, p->channels, 128, f.coop.M, f.coop.G};
+        off = (off + 63) & ~63LL;
+        f.coop.img = off; off += (long long)f.coop.M * (coop_p_words() + coop_t_words());
+        f.coop.x = off; off += d.per_tile_fwd() * f.coop.chunk;
+        f.coop.scale = off; off += 64;
+        f.coop.sync = off; off += 64 + coop_sync_words(f.coop.G, f.coop.chunk) + 64;
+        f.name = "ncde_fwd_tiled<NS1,coop,fp16x2>";
+    }
+    f.end = off;
+    return f;
+}
+
+// ---- adjoint: one launchable sequence of the matmul-input path (or the direct modes' single sweep) -----------------------------------
+struct AdjSeq {
+    bool coop;
+    SweepFn fa;               // the sweep (pass A)
+    int nwv;                  // its waves per workgroup
+    size_t lds;               // (direct modes: before the LDS-resident matrices)
+    PassBFn fb, fb2;          // pass B; fb2: the gate head's own pass (gated field, when the two heads do not share one)
+    dim3 gridB;
+    int threadsB;
+    size_t ldsB;
+    int parts;                // part-groups pass B writes: how many partials per head every reduction of this sequence adds up
+    const char* name;
+};
+// family names: [pass 1, pass 2 (exact discrete backward)][original, gated field]
+const char* const kAdjNameDirect[2][2] = {{"ncde_adj_tiled<direct>", "ncde_adj_tiled<gated,direct>"},
+                                          {"ncde_adj_tiled<direct,discrete>", "ncde_adj_tiled<gated,direct,discrete>"}};
+const char* const kAdjNameBf[2][2] = {{"ncde_adj_tiled<bf16>+ncde_dwo_pair", "ncde_adj_tiled<gated,bf16>+ncde_dwo_pair"},
+                                      {"ncde_adj_tiled<discrete,bf16>+ncde_dwo_pair", "ncde_adj_tiled<gated,discrete,bf16>+ncde_dwo_pair"}};
+const char* const kAdjNameFp32[2][2] = {{"ncde_adj_tiled+ncde_dwo_tiled", "ncde_adj_tiled<gated>+ncde_dwo_tiled"},
+                                        {"ncde_adj_tiled<discrete>+ncde_dwo_tiled", "ncde_adj_tiled<gated,discrete>+ncde_dwo_tiled"}};
+// [pass 1, pass 2][fp32, split-bf16 records] (original field only)
+const char* const kAdjNameWide[2][2] = {{"ncde_adj_tiled<wide>+ncde_dwo_tiled", "ncde_adj_tiled<wide,bf16>+ncde_dwo_pair"},
+                                        {"ncde_adj_tiled<wide,discrete>+ncde_dwo_tiled", "ncde_adj_tiled<wide,discrete,bf16>+ncde_dwo_pair"}};
+const char* const kAdjNameCoop[2] = {"ncde_adj_tiled<coop,fp16x2>+ncde_dwo_h2<fp16x2 records>",
+                                     "ncde_adj_tiled<coop,discrete,fp16x2>+ncde_dwo_h2<fp16x2 records>"};
+
+// The per-workgroup sequence of this problem, or (coop, only where t.coop.ok) the cooperative one: weights resident in registers,
+// activations exchanged through L2 (ncde_coop.h), 2-piece fp16 records folded by ncde_dwo_h2 (16 row tiles per workgroup, records
+// through LDS, the sample-tile pairs of a stage split over t.parts workgroups).
+AdjSeq tiled_adj_seq(const NcdeProblem* p, const TiledAdjPlan& t, bool coop, bool discrete) {
+    AdjSeq s{};
+    const bool g = p->field_kind == NCDE_FIELD_MINIMAL, bf = tiled_adj_bf(p);
+    if (coop) {
+        s.coop = true;
+        s.fa = ncde_adj_tiled<8, 8, 0, 0, 1, 0, 0, 1>;
+        s.nwv = 8;
+        s.lds = tiled_coop_lds(p);
+        s.fb = ncde_dwo_h2;
+        s.gridB = dim3(p->hidden * p->channels / 16 / 16 * t.parts);
+        s.threadsB = 512;
+        s.ldsB = sizeof(float) * 2 * (size_t)(2 * 2048 + 4096 + 2 * (p->hidden / 16) * 256 + 2 * ((p->channels + 15) / 16) * 256 + 2 * 256);      // (ncde_dwo2.hip: two record buffers)
+        s.parts = t.parts;
+        s.name = kAdjNameCoop[discrete];
+        return s;
+    }
+    s.nwv = tiled_adj_nwv(p);
+    s.lds = tiled_adj_lds(p);
+    if (p->field_input != NCDE_INPUT_MATMUL) {      // no records, no pass B: the partials carry every parameter
+        s.fa = g ? ncde_adj_tiled<1, TL_ADJ_NW, 0, 1, 0, 1> : ncde_adj_tiled<1, TL_ADJ_NW, 0, 0, 0, 1>;
+        s.name = kAdjNameDirect[discrete][g];
+        return s;
+    }
+    s.gridB = dim3(p->hidden * p->channels / 16 / t.nrt, t.parts_pw);
+    s.threadsB = 256;
+    s.parts = t.parts_pw;
+    const int c = tiled_pk_col(tiled_adj_pk(p));
+    const int res = tiled_adj_res(p);
+    const PassBFn (*passB)[5] = bf ? kAdjPair : kAdjDwo;
+    s.fb = passB[g ? 3 : (t.nrt == 4 ? 2 : t.nrt - 1)][c];
+    s.fb2 = g ? passB[4][c] : nullptr;
+    if (tiled_adj_bigh(p)) {      // (tiled_adj_ok: original field, matmul input)
+        s.fa = kAdjSweepWide[bf][c];
+        s.name = kAdjNameWide[discrete][bf];
+    } else {
+        s.fa = kAdjSweep[g][bf][res][c];
+        s.name = bf ? kAdjNameBf[discrete][g] : kAdjNameFp32[discrete][g];
+    }
+    return s;
+}
+
+// Runs sequence `s` through every time window, newest first: the sweep W steps (pass A), then pass B folds their records into the
+// output-layer partials at gB.  The cooperative sequence takes one CHUNK of the batch at a time (all of it unless there are more sample
+// tiles than CUs), each chunk through all its windows, and ncde_dwo_h2 keeps adding to gB; the per-workgroup sequence takes the whole
+// batch as one chunk.
+int tiled_adj_run(const NcdeProblem* p, const TiledAdjPlan& t, const AdjSeq& s, const KArgs& a, int n_rsteps, float* gB, hipStream_t st) {
+    if (s.ldsB && ncde_lds_optin((const void*)s.fb, s.ldsB) != hipSuccess) return NCDE_ERR_HIP;
+    if (ncde_lds_optin((const void*)s.fa, s.lds) != hipSuccess) return NCDE_ERR_HIP;
+    const int chunk = s.coop ? t.coop.chunk : t.n_st;
+    for (int t0 = 0; t0 < t.n_st; t0 += chunk) {
+        const int tiles = std::min(chunk, t.n_st - t0);
+        KArgs ac = s.coop ? coop_chunk_args(a, p->batch, t0, tiles) : a;
+        for (int hi = n_rsteps, first = 1; hi >= 1; hi -= t.window, first = 0) {
+            const int lo = std::max(0, hi - t.window), n_sc = (hi - lo) * t.S;
+            ac.win_hi = hi; ac.win_lo = lo; ac.resume = first ? 0 : 1;
+            if (s.coop) {      // (the sync words of the launch and, behind them, the window's cotangent-bound word: KArgs.win_max)
+                ac.dw2_accum = (first && t0 == 0) ? 0 : 1;
+                if (hipMemsetAsync(a.coop_sync, 0, sizeof(unsigned) * (size_t)(coop_sync_words(ac.coop_G, tiles) + 1), st) != hipSuccess) return NCDE_ERR_HIP;
+            }
+            hipLaunchKernelGGL(s.fa, dim3(tiles), dim3(64 * s.nwv), s.lds, st, ac);
+            hipLaunchKernelGGL(s.fb, s.gridB, dim3(s.threadsB), s.ldsB, st, ac, n_sc, tiles, gB);
+            if (s.fb2) hipLaunchKernelGGL(s.fb2, s.gridB, dim3(s.threadsB), s.ldsB, st, ac, n_sc, tiles, gB + (long long)s.parts * t.theta_o);
+            if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
+        }
+    }
+    if (s.coop) coop_mark_in_flight(st);
+    return NCDE_OK;
+}
+
+// Deterministic reductions behind sequence `s` (the one that ran): the sweep's hidden-layer partials, then the s.parts part-group
+// partials of pass B per head.  run_if: only if the cooperative sequence gave up (behind the re-execution by the per-workgroup kernels).
+int tiled_adj_reduce(const NcdeProblem* p, const Layout& y, const TiledAdjPlan& t, const AdjSeq& s, const NcdeGrads* g, const float* gpart,
+                     const float* gB, const unsigned* run_if, hipStream_t st) {
+    auto reduce = [&](const float* src, int n_part, int len, const ReduceSegs& segs) {
+        if (run_if) hipLaunchKernelGGL(ncde_reduce_partials_if, dim3((len + 255) / 256), dim3(256), 0, st, run_if, src, n_part, len, segs);
+        else hipLaunchKernelGGL(ncde_reduce_partials, dim3((len + 255) / 256), dim3(256), 0, st, src, n_part, len, segs);
+    };
+    ReduceSegs segs{};
+    int n = 0;
+    for (int l = 0; l < p->n_layers; ++l) {
+        bool first = true;
+        for (int q = 0; q < l; ++q)
+            if (p->layer_W[q] == p->layer_W[l]) first = false;
+        if (!first) continue;
+        if (!g->grad_layer_W[l] || !g->grad_layer_b[l]) return NCDE_ERR_INVALID;
+        segs.off[n] = y.gW_off[l]; segs.len[n] = p->layer_out[l] * p->layer_in[l]; segs.dst[n] = g->grad_layer_W[l]; ++n;
+        segs.off[n] = y.gb_off[l]; segs.len[n] = p->layer_out[l]; segs.dst[n] = g->grad_layer_b[l]; ++n;
+    }
+    segs.n = n;
+    reduce(gpart, t.n_st, t.gstride, segs);
+    if (!g->grad_Wo || !g->grad_bo) return NCDE_ERR_INVALID;
+    ReduceSegs so{};
+    const int wo_sz = p->hidden * p->channels * y.dlast;
+    so.n = 2;
+    so.off[0] = 0; so.len[0] = wo_sz; so.dst[0] = g->grad_Wo;
+    so.off[1] = wo_sz; so.len[1] = p->hidden * p->channels; so.dst[1] = g->grad_bo;
+    reduce(gB, s.parts, (int)t.theta_o, so);
+    if (p->field_kind == NCDE_FIELD_MINIMAL) {      // the gate head's partials: written by fb2, or by the two-head pass behind the tanh head's
+        if (!g->grad_Wg || !g->grad_bg) return NCDE_ERR_INVALID;
+        so.dst[0] = g->grad_Wg;
+        so.dst[1] = g->grad_bg;
+        reduce(gB + (long long)s.parts * t.theta_o, s.parts, (int)t.theta_o, so);
+    }
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
 }  // namespace
@@ -3337,177 +3612,72 @@ bool ncde_tiled_supported(const NcdeProblem* p, int pass) {
     return tiled_fwd_ns(p) > 0;
 }
 
-// Is the tiled family the better choice?  Measured on MI355X it is wherever it applies: forward cfg5 0.51 s vs 2.54 s
-// generic; backward cfg5 1.38 s vs 13.5 s, cfg4 14.1 ms vs 24.0 ms (the generic kernel keeps its per-workgroup
-// gradient partial in global memory once it no longer fits LDS).  The hook stays for shapes that measure otherwise.
-bool ncde_tiled_preferred(const NcdeProblem* p, int pass) {
-    (void)p; (void)pass;
-    return true;
-}
-
 const char* ncde_tiled_kernel_name(const NcdeProblem* p, int pass) {
     if (!ncde_tiled_supported(p, pass)) return nullptr;
-    const bool gated = p->field_kind == NCDE_FIELD_MINIMAL;
-    if (pass >= 1 && p->field_input != NCDE_INPUT_MATMUL)
-        return pass == 1 ? (gated ? "ncde_adj_tiled<gated,direct>" : "ncde_adj_tiled<direct>") : (gated ? "ncde_adj_tiled<gated,direct,discrete>" : "ncde_adj_tiled<direct,discrete>");
-    if (pass >= 1 && tiled_adj_bigh(p)) {      // 128 < H <= 256: the one-wave-per-SIMD instantiation of the sweep
-        if (tiled_adj_bf(p)) return pass == 1 ? "ncde_adj_tiled<wide,bf16>+ncde_dwo_pair" : "ncde_adj_tiled<wide,discrete,bf16>+ncde_dwo_pair";
-        return pass == 1 ? "ncde_adj_tiled<wide>+ncde_dwo_tiled" : "ncde_adj_tiled<wide,discrete>+ncde_dwo_tiled";
-    }
-    if (pass >= 1 && tiled_adj_bf(p) && !gated && tiled_coop_plan(p).ok)      // weight-stationary output phase across the workgroups of an XCD
-        return pass == 1 ? "ncde_adj_tiled<coop,fp16x2>+ncde_dwo_h2<fp16x2 records>" : "ncde_adj_tiled<coop,discrete,fp16x2>+ncde_dwo_h2<fp16x2 records>";
-    if (pass >= 1 && tiled_adj_bf(p)) {      // split-bf16 records: the pair kernel is pass B
-        if (pass == 1) return gated ? "ncde_adj_tiled<gated,bf16>+ncde_dwo_pair" : "ncde_adj_tiled<bf16>+ncde_dwo_pair";
-        return gated ? "ncde_adj_tiled<gated,discrete,bf16>+ncde_dwo_pair" : "ncde_adj_tiled<discrete,bf16>+ncde_dwo_pair";
-    }
-    if (pass == 1) return gated ? "ncde_adj_tiled<gated>+ncde_dwo_tiled" : "ncde_adj_tiled+ncde_dwo_tiled";
-    if (pass == 2) return gated ? "ncde_adj_tiled<gated,discrete>+ncde_dwo_tiled" : "ncde_adj_tiled<discrete>+ncde_dwo_tiled";
-    if (p->field_input != NCDE_INPUT_MATMUL) return gated ? "ncde_fwd_tiled<NS1,gated,direct>" : "ncde_fwd_tiled<NS1,direct>";
-    const int ns = tiled_fwd_ns(p);
-    if (!gated && tiled_fwd_coop_plan(p).ok) return "ncde_fwd_tiled<NS1,coop,fp16x2>";
-    if (tiled_fwd_split(p) == 2) return gated ? "ncde_fwd_tiled<NS1,gated,fp16x2>" : "ncde_fwd_tiled<NS1,fp16x2>";
-    if (tiled_fwd_bf(p)) return gated ? "ncde_fwd_tiled<NS1,gated,bf16>" : "ncde_fwd_tiled<NS1,bf16>";
-    if (gated) return ns == 4 ? "ncde_fwd_tiled<NS4,gated>" : (ns == 2 ? "ncde_fwd_tiled<NS2,gated>" : "ncde_fwd_tiled<NS1,gated>");
-    return ns == 4 ? "ncde_fwd_tiled<NS4>" : (ns == 2 ? "ncde_fwd_tiled<NS2>" : "ncde_fwd_tiled<NS1>");
+    if (pass == 0) return tiled_fwd_plan(p).name;
+    const TiledAdjPlan t = tiled_adj_plan(p, make_layout(p));
+    return tiled_adj_seq(p, t, t.coop.ok, pass == 2).name;
 }
 
 int64_t ncde_tiled_workspace_bytes(const NcdeProblem* p, int pass) {
     if (!ncde_tiled_supported(p, pass)) return NCDE_ERR_UNSUPPORTED;
-    if (pass == 0 && p->field_input != NCDE_INPUT_MATMUL) return 256 + (int64_t)sizeof(float) * p->layer_out[0] * ((p->layer_in[0] + 15) & ~15);
-    if (pass == 0) {
-        const int split = tiled_fwd_split(p);      // split-fp16: its own copy + the split-bf16 copy of the re-execution launch + fault words
-        const FwdCoopPlan fc = tiled_fwd_coop_plan(p);
-        if (fc.ok) return (int64_t)sizeof(float) * fc.end;
-        if (split == 2) return 256 + (tiled_pack_floats(p, false) + tiled_pack_floats(p, true) + tiled_fault_floats(p)) * (int64_t)sizeof(float);
-        return 256 + tiled_pack_floats(p, split == 1) * (int64_t)sizeof(float);
-    }
-    const Layout y = make_layout(p);
-    return (int64_t)sizeof(float) * tiled_adj_plan(p, y).total;
+    return (int64_t)sizeof(float) * (pass == 0 ? tiled_fwd_plan(p).end : tiled_adj_plan(p, make_layout(p)).total);
 }
 
 int64_t ncde_tiled_status_offset(const NcdeProblem* p, int pass) {
     if (!ncde_tiled_supported(p, pass)) return -1;
-    if (pass == 0) {
-        if (p->field_input != NCDE_INPUT_MATMUL) return -1;
-        const FwdCoopPlan fc = tiled_fwd_coop_plan(p);
-        return fc.ok ? (int64_t)sizeof(float) * (fc.scale + 16) : -1;
-    }
-    if (p->field_input != NCDE_INPUT_MATMUL) return -1;
-    const Layout y = make_layout(p);
-    const TiledAdjPlan t = tiled_adj_plan(p, y);
-    return t.coop ? (int64_t)sizeof(float) * (t.coop_scale + 16) : -1;
-}
-
-// forward instantiation with split output tiles: BF = 1 split-bf16, 2 split-fp16; resh = resident hidden fragments (0 / 2 / 4)
-template <int BF>
-static void (*tiled_fwd_split_fn(bool g, bool small, int resh))(KArgs) {
-    if (resh == 2) return g ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF, 2> : ncde_fwd_tiled<1, TL_NW, 4, 0, BF, 2>;
-    if (resh == 4) return g ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF, 4> : ncde_fwd_tiled<1, TL_NW, 4, 0, BF, 4>;
-    if (g) return small ? ncde_fwd_tiled<1, TL_NW, 4, 1, BF> : ncde_fwd_tiled<1, TL_NW, 16, 1, BF>;
-    return small ? ncde_fwd_tiled<1, TL_NW, 4, 0, BF> : ncde_fwd_tiled<1, TL_NW, 16, 0, BF>;
+    const CoopPlan c = pass == 0 ? tiled_fwd_plan(p).coop : tiled_adj_plan(p, make_layout(p)).coop;
+    return c.ok ? (int64_t)sizeof(float) * (c.scale + 16) : -1;
 }
 
 int ncde_tiled_forward(const NcdeProblem* p, float* out, float* stages, void* ws, size_t ws_bytes, hipStream_t st) {
     if (!ncde_tiled_supported(p, 0)) return NCDE_ERR_UNSUPPORTED;
-    if ((int64_t)ws_bytes < ncde_tiled_workspace_bytes(p, 0)) return NCDE_ERR_WORKSPACE;
+    const FwdPlan f = tiled_fwd_plan(p);
+    if ((int64_t)ws_bytes < (int64_t)sizeof(float) * f.end) return NCDE_ERR_WORKSPACE;
     const Layout y = make_layout(p);
     KArgs a;
     fill_kargs(p, y, &a);
     a.out = out;
     a.stages = stages;
-    const bool direct = p->field_input != NCDE_INPUT_MATMUL;
-    const bool bf = !direct && tiled_fwd_bf(p);
-    const int split = direct ? 0 : tiled_fwd_split(p);
-    float* wsf = (float*)ws + 64;
-    float* pack_bf = wsf + (split == 2 ? tiled_pack_floats(p, false) : 0);      // split-fp16: [h2 copy | bf16 copy | fault words]
-    int* fault = split == 2 ? reinterpret_cast<int*>(pack_bf + tiled_pack_floats(p, true)) : nullptr;
-    if (direct) {      // layer 0 with its H + C columns zero-padded to a multiple of 16
+    float* w = (float*)ws;
+    if (f.direct) {      // layer 0 with its H + C columns zero-padded to a multiple of 16
         const int d0p = (p->layer_in[0] + 15) & ~15, n0 = p->layer_out[0];
-        float* w0 = (float*)ws + 64;
-        hipLaunchKernelGGL(ncde_pad_columns, dim3((n0 * d0p + 255) / 256), dim3(256), 0, st, a.W[0], w0, n0, p->layer_in[0], d0p);
-        a.W[0] = w0;
+        hipLaunchKernelGGL(ncde_pad_columns, dim3((n0 * d0p + 255) / 256), dim3(256), 0, st, a.W[0], w + f.pack, n0, p->layer_in[0], d0p);
+        a.W[0] = w + f.pack;
         a.din[0] = d0p;
-    } else if (split == 2) {
+    } else if (f.split == 2) {
+        int* fault = reinterpret_cast<int*>(w + f.fault);
         const int n_tiles = (p->batch + 15) / 16;
         if (hipMemsetAsync(fault + n_tiles, 0, sizeof(int), st) != hipSuccess) return NCDE_ERR_HIP;
-        tiled_pack_launch(p, &a, wsf, false, st, 2, fault + n_tiles);
+        tiled_pack_launch(p, &a, w + f.pack, false, st, 2, fault + n_tiles);
         a.fault = fault;
-    } else if (tiled_pack_floats(p, bf) > 0) tiled_pack_launch(p, &a, wsf, bf, st);
-    const int ns = direct ? 1 : tiled_fwd_ns(p);
-    const size_t lds = direct ? tiled_direct_residency(p, &a, tiled_fwd_lds(p, ns)) : tiled_fwd_lds(p, ns);
-    const bool small = p->hidden * ns * 16 <= 4 * TL_THREADS;   // state slice of <= 4 elements per thread: fewer live registers
-    void (*fn)(KArgs) = ns == 4 ? (small ? ncde_fwd_tiled<4, TL_NW, 4> : ncde_fwd_tiled<4, TL_NW, 16>)
-                                : (ns == 2 ? (small ? ncde_fwd_tiled<2, TL_NW, 4> : ncde_fwd_tiled<2, TL_NW, 16>)
-                                           : (small ? ncde_fwd_tiled<1, TL_NW, 4> : ncde_fwd_tiled<1, TL_NW, 16>));
-    if (p->field_kind == NCDE_FIELD_MINIMAL)
-        fn = ns == 4 ? ncde_fwd_tiled<4, TL_NW, 16, 1> : (ns == 2 ? ncde_fwd_tiled<2, TL_NW, 16, 1> : ncde_fwd_tiled<1, TL_NW, 16, 1>);
-    void (*fx)(KArgs) = nullptr;      // split-fp16: the split-bf16 instantiation of the same configuration re-executes range-faulted tiles
-    if (bf) {
-        // small square hidden stack (H = every width = 32 or 64): hidden fragments resident
-        bool sq = (p->hidden == 32 || p->hidden == 64) && ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr;
-        for (int l = 0; l < p->n_layers; ++l) sq = sq && p->layer_out[l] == p->hidden && p->layer_in[l] == p->hidden;
-        const bool g = p->field_kind == NCDE_FIELD_MINIMAL;
-        const int resh = !sq ? 0 : (p->hidden == 32 ? 2 : 4);
-        fx = tiled_fwd_split_fn<1>(g, small, resh);
-        fn = split == 2 ? tiled_fwd_split_fn<2>(g, small, resh) : fx;
-    }
-    if (direct) {
-        if (p->field_kind == NCDE_FIELD_MINIMAL) fn = small ? ncde_fwd_tiled<1, TL_NW, 4, 1, 0, 0, 1> : ncde_fwd_tiled<1, TL_NW, 16, 1, 0, 0, 1>;
-        else fn = small ? ncde_fwd_tiled<1, TL_NW, 4, 0, 0, 0, 1> : ncde_fwd_tiled<1, TL_NW, 16, 0, 0, 0, 1>;
-    }
-    const FwdCoopPlan fc = direct ? FwdCoopPlan{} : tiled_fwd_coop_plan(p);
-    const int nwg = (p->batch + ns * 16 - 1) / (ns * 16);
-    if (fc.ok) {      // XCD-cooperative, weight-stationary output phase (ncde_coop.h): the reverse sweep's groups and weight images
-        void (*fc_fn)(KArgs) = ncde_fwd_tiled<1, TL_NW, 4, 0, 2, 0, 0, 1>;
-        const size_t lds_coop = sizeof(float) * ((size_t)16 * (size_t)(2 * p->hidden + 2 * tiled_dmax(p) + p->channels) + (size_t)kFwdCoopLdsFloats);
-        if (ncde_lds_optin((const void*)fc_fn, lds_coop) != hipSuccess) return NCDE_ERR_HIP;
-        if (coop_runtime_ok((const void*)fc_fn, TL_THREADS, lds_coop, fc.chunk, st)) {      // (else: the per-workgroup kernels below, unconditionally)
-            float* w = (float*)ws;
-            unsigned* amax = reinterpret_cast<unsigned*>(w + fc.scale + 8);
-            unsigned* status = reinterpret_cast<unsigned*>(w + fc.scale + 16);
-            if (hipMemsetAsync(amax, 0, sizeof(unsigned), st) != hipSuccess) return NCDE_ERR_HIP;
-            if (hipMemsetAsync(status, 0, sizeof(unsigned), st) != hipSuccess) return NCDE_ERR_HIP;
-            const int n_tiles = (p->batch + 15) / 16;
-            const long long nw = (long long)p->hidden * p->channels * 128;
-            hipLaunchKernelGGL(ncde_coop_absmax, dim3(512), dim3(256), 0, st, a.Wo, nw, amax);
-            hipLaunchKernelGGL(ncde_coop_pack, dim3(1024), dim3(256), 0, st, a.Wo, (const unsigned*)amax, reinterpret_cast<unsigned*>(w + fc.img), w + fc.scale,
-                               p->channels, 128, fc.M);
-            a.coop_img = reinterpret_cast<const unsigned*>(w + fc.img);
-            a.coop_x = w + fc.x;
-            a.coop_scale = w + fc.scale;
-            a.coop_sync = reinterpret_cast<unsigned*>(w + fc.sync);
-            a.coop_M = fc.M;
-            a.coop_G = fc.G;
-            a.coop_status = status;
-            a.coop_inject = (p->flags & NCDE_FLAG_COOP_FAULT_INJECT) ? 1 : 0;
-            a.coop_spin = a.coop_inject ? (1u << 12) : (unsigned)COOP_SPIN_LIMIT;
+    } else if (f.npack > 0) tiled_pack_launch(p, &a, w + f.pack, f.split == 1, st);
+    const size_t lds = f.direct ? tiled_direct_residency(p, &a, f.lds) : f.lds;
+    if (f.coop.ok) {      // XCD-cooperative, weight-stationary output phase (ncde_coop.h)
+        if (ncde_lds_optin((const void*)f.fc, f.lds_coop) != hipSuccess) return NCDE_ERR_HIP;
+        if (coop_zero_words(w, f.coop, st) != hipSuccess) return NCDE_ERR_HIP;
+        if (coop_runtime_ok((const void*)f.fc, TL_THREADS, f.lds_coop, f.coop.chunk, st)) {      // (else: the per-workgroup kernels below, unconditionally)
+            coop_prepare(p, &a, w, f.coop, st);
             // one launch per CHUNK of the batch (all of it unless the batch has more sample tiles than the device has CUs)
-            for (int t0 = 0; t0 < n_tiles; t0 += fc.chunk) {
-                const int tiles_c = std::min(fc.chunk, n_tiles - t0);
-                KArgs ac = a;
-                ac.B = std::min(p->batch - 16 * t0, 16 * tiles_c);
-                ac.coeffs = a.coeffs + (long long)16 * t0 * a.cs_b;
-                ac.z0 = a.z0 + (long long)16 * t0 * a.Hr;
-                ac.out = a.out + (long long)16 * t0 * a.n_out * a.Hr;
-                if (a.stages) { ac.stages = a.stages + (long long)16 * t0 * a.Hr; ac.Brec = p->batch; }
-                if (a.fault) ac.fault = a.fault + t0;
-                ac.coop_G = tiles_c / fc.M;
-                if (hipMemsetAsync(w + fc.sync, 0, sizeof(unsigned) * (size_t)coop_sync_words(ac.coop_G, tiles_c), st) != hipSuccess) return NCDE_ERR_HIP;
-                hipLaunchKernelGGL(fc_fn, dim3(tiles_c), dim3(TL_THREADS), lds_coop, st, ac);
+            for (int t0 = 0, n_tiles = (p->batch + 15) / 16; t0 < n_tiles; t0 += f.coop.chunk) {
+                const int tiles = std::min(f.coop.chunk, n_tiles - t0);
+                const KArgs ac = coop_chunk_args(a, p->batch, t0, tiles);
+                if (hipMemsetAsync(a.coop_sync, 0, sizeof(unsigned) * (size_t)coop_sync_words(ac.coop_G, tiles), st) != hipSuccess) return NCDE_ERR_HIP;
+                hipLaunchKernelGGL(f.fc, dim3(tiles), dim3(TL_THREADS), f.lds_coop, st, ac);
             }
             coop_mark_in_flight(st);
             // Behind it, the per-workgroup kernels with run_if = the status word: they return at once unless the cooperative launch gave
             // up (a workgroup that never became resident: another process's kernels, a CU mask), in which case they redo the solve.
-            a.run_if = status;
+            a.run_if = a.coop_status;
         }
     }
-    if (ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-    hipLaunchKernelGGL(fn, dim3(nwg), dim3(TL_THREADS), lds, st, a);
-    if (split == 2) {      // re-execution of range-faulted sample tiles in split-bf16 (normally none: every workgroup exits at once)
-        tiled_pack_launch(p, &a, pack_bf, true, st);
+    if (ncde_lds_optin((const void*)f.fn, lds) != hipSuccess) return NCDE_ERR_HIP;
+    hipLaunchKernelGGL(f.fn, dim3(f.grid), dim3(TL_THREADS), lds, st, a);
+    if (f.fx) {      // re-execution of range-faulted sample tiles in split-bf16 (normally none: every workgroup exits at once)
+        tiled_pack_launch(p, &a, w + f.pack_bf, true, st);
         a.only_faulted = 1;
-        if (ncde_lds_optin((const void*)fx, lds) != hipSuccess) return NCDE_ERR_HIP;
-        hipLaunchKernelGGL(fx, dim3(nwg), dim3(TL_THREADS), lds, st, a);
+        if (ncde_lds_optin((const void*)f.fx, lds) != hipSuccess) return NCDE_ERR_HIP;
+        hipLaunchKernelGGL(f.fx, dim3(f.grid), dim3(TL_THREADS), lds, st, a);
     }
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
@@ -3527,19 +3697,18 @@ int ncde_tiled_adjoint(const NcdeProblem* p, const float* src, const float* grad
     a.recA = w + t.recA; a.recB = w + t.recB; a.recC = w + t.recC; a.recD = w + t.recD;
     a.gpart = w + t.gpartA;
     a.gstride = t.gstride;
+    a.carry = w + t.carry;
+    const AdjSeq pw = tiled_adj_seq(p, t, false, discrete);      // the per-workgroup sequence: also what a cooperative one falls back to
+    const int n_rsteps = p->output == NCDE_OUT_TIMES ? (discrete ? p->n_steps_fwd : p->n_steps_adj) : p->n_knots - 1;
     if (p->field_input != NCDE_INPUT_MATMUL) {      // evaluate / derivative inputs: one launch of the direct-mode sweep + the reduction
         const int d0p = (p->layer_in[0] + 15) & ~15, n0 = p->layer_out[0];
         hipLaunchKernelGGL(ncde_pad_columns, dim3((n0 * d0p + 255) / 256), dim3(256), 0, st, a.W[0], w + t.pack, n0, p->layer_in[0], d0p);
         a.W[0] = w + t.pack;
         a.din[0] = d0p;
-        a.carry = w + t.carry;
-        const bool g1 = p->field_kind == NCDE_FIELD_MINIMAL;
-        void (*fd)(KArgs) = g1 ? ncde_adj_tiled<1, TL_ADJ_NW, 0, 1, 0, 1> : ncde_adj_tiled<1, TL_ADJ_NW, 0, 0, 0, 1>;
-        const size_t ldsd = tiled_direct_residency(p, &a, tiled_adj_lds(p));      // + LDS-resident copies of the small matrices
-        if (ncde_lds_optin((const void*)fd, ldsd) != hipSuccess) return NCDE_ERR_HIP;
-        const int n_rs = p->output == NCDE_OUT_TIMES ? (discrete ? p->n_steps_fwd : p->n_steps_adj) : p->n_knots - 1;
-        a.win_hi = n_rs; a.win_lo = 0; a.resume = 0;
-        hipLaunchKernelGGL(fd, dim3(t.n_st), dim3(64 * TL_ADJ_NW), ldsd, st, a);
+        const size_t ldsd = tiled_direct_residency(p, &a, pw.lds);      // + LDS-resident copies of the small matrices
+        if (ncde_lds_optin((const void*)pw.fa, ldsd) != hipSuccess) return NCDE_ERR_HIP;
+        a.win_hi = n_rsteps; a.win_lo = 0; a.resume = 0;
+        hipLaunchKernelGGL(pw.fa, dim3(t.n_st), dim3(64 * pw.nwv), ldsd, st, a);
         if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
         if (main_kernel_only) return NCDE_OK;
         return launch_reduce_partials(p, y, g, (const float*)a.gpart, t.n_st, st);
@@ -3552,190 +3721,34 @@ int ncde_tiled_adjoint(const NcdeProblem* p, const float* src, const float* grad
         hipLaunchKernelGGL(ncde_pack_panels_bf, dim3(grid), dim3(256), 0, st, a.Wo, (unsigned*)(w + t.pack_bf), p->hidden, p->channels, dl / 32);
         a.Wo_bf = (const unsigned*)(w + t.pack_bf);
     }
-    const int pk = tiled_adj_pk(p);
-    const bool gated = p->field_kind == NCDE_FIELD_MINIMAL;
-    const bool res = tiled_adj_res(p), bf = tiled_adj_bf(p);
-    void (*fa)(KArgs) = pk == 8 ? ncde_adj_tiled<8, TL_ADJ_NW>
-                                : (pk == 4 ? (res ? ncde_adj_tiled<4, TL_ADJ_NW, 1> : ncde_adj_tiled<4, TL_ADJ_NW>)
-                                           : (pk == 2 ? (res ? ncde_adj_tiled<2, TL_ADJ_NW, 1> : ncde_adj_tiled<2, TL_ADJ_NW>)
-                                                      : (res ? ncde_adj_tiled<1, TL_ADJ_NW, 1> : ncde_adj_tiled<1, TL_ADJ_NW>)));
-    void (*fb)(KArgs, int, int, float*) = pk == 8 ? ncde_dwo_tiled<8> : (pk == 4 ? ncde_dwo_tiled<4> : (pk == 2 ? ncde_dwo_tiled<2> : ncde_dwo_tiled<1>));
-    if (t.nrt == 4) fb = pk == 8 ? ncde_dwo_tiled<8, 0, 4> : (pk == 4 ? ncde_dwo_tiled<4, 0, 4> : (pk == 2 ? ncde_dwo_tiled<2, 0, 4> : ncde_dwo_tiled<1, 0, 4>));
-    if (t.nrt == 2) fb = pk == 8 ? ncde_dwo_tiled<8, 0, 2> : (pk == 4 ? ncde_dwo_tiled<4, 0, 2> : (pk == 2 ? ncde_dwo_tiled<2, 0, 2> : ncde_dwo_tiled<1, 0, 2>));
-    void (*fb2)(KArgs, int, int, float*) = nullptr;
-    if (gated) {
-        fa = pk == 8 ? ncde_adj_tiled<8, TL_ADJ_NW, 0, 1> : (pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 0, 1> : (pk == 2 ? ncde_adj_tiled<2, TL_ADJ_NW, 0, 1> : ncde_adj_tiled<1, TL_ADJ_NW, 0, 1>));
-        fb = pk == 8 ? ncde_dwo_tiled<8, 1> : (pk == 4 ? ncde_dwo_tiled<4, 1> : (pk == 2 ? ncde_dwo_tiled<2, 1> : ncde_dwo_tiled<1, 1>));
-        fb2 = pk == 8 ? ncde_dwo_tiled<8, 2> : (pk == 4 ? ncde_dwo_tiled<4, 2> : (pk == 2 ? ncde_dwo_tiled<2, 2> : ncde_dwo_tiled<1, 2>));
-    }
-    const bool res2 = tiled_adj_res2(p);
-    if (res2 && !bf) {
-        if (gated) fa = pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 2, 1> : (pk == 2 ? ncde_adj_tiled<2, TL_ADJ_NW, 2, 1> : ncde_adj_tiled<1, TL_ADJ_NW, 2, 1>);
-        else fa = pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 2> : (pk == 2 ? ncde_adj_tiled<2, TL_ADJ_NW, 2> : ncde_adj_tiled<1, TL_ADJ_NW, 2>);
-    }
-    if (bf) {
-        if (gated) {
-            fa = pk == 8 ? ncde_adj_tiled<8, TL_ADJ_NW, 0, 1, 1> : (pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 0, 1, 1> : ncde_adj_tiled<2, TL_ADJ_NW, 0, 1, 1>);
-            if (res2) fa = pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 2, 1, 1> : ncde_adj_tiled<2, TL_ADJ_NW, 2, 1, 1>;
-            // both heads in one pass where the two accumulator sets fit the register file; at 128 columns one pass per head
-            if (pk == 8) { fb = ncde_dwo_pair<8, 1, 1>; fb2 = ncde_dwo_pair<8, 2, 1>; }
-            else { fb = pk == 4 ? ncde_dwo_pair<4, 3, 1> : ncde_dwo_pair<2, 3, 1>; fb2 = nullptr; }
-        } else {
-            fa = pk == 8 ? ncde_adj_tiled<8, TL_ADJ_NW, 0, 0, 1> : (pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 0, 0, 1> : ncde_adj_tiled<2, TL_ADJ_NW, 0, 0, 1>);
-            if (res2) fa = pk == 4 ? ncde_adj_tiled<4, TL_ADJ_NW, 2, 0, 1> : ncde_adj_tiled<2, TL_ADJ_NW, 2, 0, 1>;
-            if (t.nrt == 4) fb = pk == 8 ? ncde_dwo_pair<8, 0, 4> : (pk == 4 ? ncde_dwo_pair<4, 0, 4> : ncde_dwo_pair<2, 0, 4>);
-            else if (t.nrt == 2) fb = pk == 8 ? ncde_dwo_pair<8, 0, 2> : (pk == 4 ? ncde_dwo_pair<4, 0, 2> : ncde_dwo_pair<2, 0, 2>);
-            else fb = pk == 8 ? ncde_dwo_pair<8, 0, 1> : (pk == 4 ? ncde_dwo_pair<4, 0, 1> : ncde_dwo_pair<2, 0, 1>);
-        }
-    }
-    const int nwv = tiled_adj_nwv(p);
-    if (pk == 16) {      // last hidden width 256: fp32 records, hidden dW in the workgroups' global partials (zero before the first window)
-        fa = ncde_adj_tiled<16, 4, 0, 0, 0, 0, 1>;
-        fb = ncde_dwo_tiled<16, 0, 1>;
-        if (hipMemsetAsync(w + t.gpartA, 0, sizeof(float) * (size_t)t.n_st * t.gstride, st) != hipSuccess) return NCDE_ERR_HIP;
-    } else if (tiled_adj_bigh(p)) {      // (tiled_adj_ok: original field, matmul input, pk >= 2)
-        if (bf) fa = pk == 8 ? ncde_adj_tiled<8, 4, 0, 0, 1, 0, 1> : (pk == 4 ? ncde_adj_tiled<4, 4, 0, 0, 1, 0, 1> : ncde_adj_tiled<2, 4, 0, 0, 1, 0, 1>);
-        else fa = pk == 8 ? ncde_adj_tiled<8, 4, 0, 0, 0, 0, 1> : (pk == 4 ? ncde_adj_tiled<4, 4, 0, 0, 0, 0, 1> : (pk == 2 ? ncde_adj_tiled<2, 4, 0, 0, 0, 0, 1> : ncde_adj_tiled<1, 4, 0, 0, 0, 0, 1>));
-    }
-    int nwv_launch = nwv;
-    size_t lds_launch = tiled_adj_lds(p);
-    void (*const fa_pw)(KArgs) = fa;      // the per-workgroup sweep of this problem (what a cooperative sequence falls back to)
-    const size_t lds_pw = lds_launch;
-    bool coop = false;
-    if (t.coop) {
-        void (*fc_fn)(KArgs) = ncde_adj_tiled<8, 8, 0, 0, 1, 0, 0, 1>;
-        if (ncde_lds_optin((const void*)fc_fn, tiled_coop_lds(p)) != hipSuccess) return NCDE_ERR_HIP;
-        coop = coop_runtime_ok((const void*)fc_fn, 64 * 8, tiled_coop_lds(p), t.coop_chunk, st);      // (see coop_runtime_ok: else the per-workgroup kernels)
-    }
-    if (coop) {      // XCD-cooperative output phase: weights resident in registers, activations exchanged through L2 (ncde_coop.h)
-        fa = ncde_adj_tiled<8, 8, 0, 0, 1, 0, 0, 1>;
-        nwv_launch = 8;
-        lds_launch = tiled_coop_lds(p);
-        unsigned* amax = reinterpret_cast<unsigned*>(w + t.coop_scale + 8);
-        if (hipMemsetAsync(amax, 0, sizeof(unsigned), st) != hipSuccess) return NCDE_ERR_HIP;
-        a.coop_status = reinterpret_cast<unsigned*>(w + t.coop_scale + 16);      // zeroed ONCE per call: a time-out in one window stops the later ones
-        if (hipMemsetAsync(a.coop_status, 0, sizeof(unsigned), st) != hipSuccess) return NCDE_ERR_HIP;
-        a.coop_inject = (p->flags & NCDE_FLAG_COOP_FAULT_INJECT) ? 1 : 0;
-        a.coop_spin = a.coop_inject ? (1u << 12) : (unsigned)COOP_SPIN_LIMIT;
-        // the hidden-layer weight gradients accumulate in the workgroups' global partials from the first stage on
-        if (hipMemsetAsync(w + t.gpartA, 0, sizeof(float) * (size_t)t.n_st * t.gstride, st) != hipSuccess) return NCDE_ERR_HIP;
-        const long long nw = (long long)p->hidden * p->channels * 128;
-        hipLaunchKernelGGL(ncde_coop_absmax, dim3(512), dim3(256), 0, st, a.Wo, nw, amax);
-        hipLaunchKernelGGL(ncde_coop_pack, dim3(1024), dim3(256), 0, st, a.Wo, (const unsigned*)amax, reinterpret_cast<unsigned*>(w + t.coop_img),
-                           w + t.coop_scale, p->channels, 128, t.coop_M);
-        a.coop_img = reinterpret_cast<const unsigned*>(w + t.coop_img);
-        a.coop_x = w + t.coop_x;
-        a.coop_scale = w + t.coop_scale;
-        a.coop_state = w + t.coop_state;
-        a.coop_sync = reinterpret_cast<unsigned*>(w + t.coop_sync);
-        a.win_max = a.coop_sync + coop_sync_words(t.coop_G, t.coop_chunk);      // (behind the sync words of a FULL chunk; a smaller last chunk uses fewer)
-        a.coop_M = t.coop_M;
-        a.coop_G = t.coop_G;
-    }
-    void (*const fb_pw)(KArgs, int, int, float*) = fb;      // pass B of the per-workgroup sequence, and its grid
-    const dim3 gridB_pw(p->hidden * p->channels / 16 / t.nrt, t.parts_pw);
-    dim3 gridB = gridB_pw;
-    size_t ldsB = 0;
-    int threadsB = 256;
-    if (coop) {      // the cooperative sweep writes 2-piece fp16 records: ncde_dwo_h2 folds them (16 row tiles per workgroup, records through LDS)
-        fb = ncde_dwo_h2;
-        threadsB = 512;
-        gridB = dim3(p->hidden * p->channels / 16 / 16 * t.parts);
-        a.dw2_parts = t.parts;
-        ldsB = sizeof(float) * 2 * (size_t)(2 * 2048 + 4096 + 2 * (p->hidden / 16) * 256 + 2 * ((p->channels + 15) / 16) * 256 + 2 * 256);      // (ncde_dwo2.hip: two record buffers)
-        if (ncde_lds_optin((const void*)fb, ldsB) != hipSuccess) return NCDE_ERR_HIP;
-        a.recS = w + t.recS;
-    }
-    const size_t lds = lds_launch;
-    if (ncde_lds_optin((const void*)fa, lds) != hipSuccess) return NCDE_ERR_HIP;
-    a.carry = w + t.carry;
+    // last hidden width 256 (fp32 records, hidden dW in the workgroups' global partials) and the cooperative sweep: the hidden-layer
+    // weight gradients accumulate in the partials from the first stage on (zero before the first window)
+    const size_t gpart_bytes = sizeof(float) * (size_t)t.n_st * t.gstride;
+    if (tiled_adj_pk(p) == 16 && hipMemsetAsync(a.gpart, 0, gpart_bytes, st) != hipSuccess) return NCDE_ERR_HIP;
     float* gB = w + t.gpartB;
-    float* gB2 = gB + (long long)t.parts * t.theta_o;
-    // time windows, newest first: sweep W steps (pass A), fold their records into the output-layer gradient (pass B)
-    const int n_rsteps = p->output == NCDE_OUT_TIMES ? (discrete ? p->n_steps_fwd : p->n_steps_adj) : p->n_knots - 1;
-    if (coop) {
-        // cooperative sequence: one CHUNK of the batch at a time (all of it unless there are more sample tiles than CUs), each chunk through
-        // all its time windows; the hidden-layer partials are per workgroup (rows t0 .. of gpartA), ncde_dwo_h2 keeps adding to gB
-        for (int t0 = 0, firstc = 1; t0 < t.n_st; t0 += t.coop_chunk, firstc = 0) {
-            const int tiles_c = std::min(t.coop_chunk, t.n_st - t0);
-            KArgs ac = a;
-            ac.B = std::min(p->batch - 16 * t0, 16 * tiles_c);
-            ac.coeffs = a.coeffs + (long long)16 * t0 * a.cs_b;
-            ac.grad_out = a.grad_out + (long long)16 * t0 * a.n_out * a.Hr;
-            ac.grad_z0 = a.grad_z0 + (long long)16 * t0 * a.Hr;
-            if (discrete) { ac.stages = a.stages + (long long)16 * t0 * a.Hr; ac.Brec = p->batch; }
-            else ac.z_out = a.z_out + (long long)16 * t0 * a.n_out * a.Hr;
-            ac.gpart = a.gpart + (long long)t0 * a.gstride;
-            ac.coop_G = tiles_c / t.coop_M;
-            ac.win_max = a.coop_sync + coop_sync_words(ac.coop_G, tiles_c);
-            for (int hi = n_rsteps, first = 1; hi >= 1; hi -= t.window, first = 0) {
-                const int lo = std::max(0, hi - t.window);
-                ac.win_hi = hi; ac.win_lo = lo; ac.resume = first ? 0 : 1;
-                ac.dw2_accum = (first && firstc) ? 0 : 1;
-                // (the sync words of the launch and, behind them, the window's cotangent-bound word: KArgs.win_max)
-                if (hipMemsetAsync(a.coop_sync, 0, sizeof(unsigned) * (size_t)(coop_sync_words(ac.coop_G, tiles_c) + 1), st) != hipSuccess) return NCDE_ERR_HIP;
-                hipLaunchKernelGGL(fa, dim3(tiles_c), dim3(64 * nwv_launch), lds, st, ac);
-                hipLaunchKernelGGL(fb, gridB, dim3(threadsB), ldsB, st, ac, (hi - lo) * t.S, tiles_c, gB);
-                if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-            }
+    if (t.coop.ok) {
+        const AdjSeq cs = tiled_adj_seq(p, t, true, discrete);
+        if (ncde_lds_optin((const void*)cs.fa, cs.lds) != hipSuccess) return NCDE_ERR_HIP;
+        if (coop_zero_words(w, t.coop, st) != hipSuccess) return NCDE_ERR_HIP;
+        if (coop_runtime_ok((const void*)cs.fa, 64 * cs.nwv, cs.lds, t.coop.chunk, st)) {      // (else: the per-workgroup sequence below)
+            if (hipMemsetAsync(a.gpart, 0, gpart_bytes, st) != hipSuccess) return NCDE_ERR_HIP;
+            coop_prepare(p, &a, w, t.coop, st);
+            a.coop_state = w + t.coop_state;
+            a.win_max = a.coop_sync + coop_sync_words(t.coop.G, t.coop.chunk);      // (behind the sync words of a FULL chunk; a smaller last chunk uses fewer)
+            a.dw2_parts = t.parts;
+            a.recS = w + t.recS;
+            int rc = tiled_adj_run(p, t, cs, a, n_rsteps, gB, st);
+            if (rc != NCDE_OK || main_kernel_only) return rc;
+            if ((rc = tiled_adj_reduce(p, y, t, cs, g, a.gpart, gB, nullptr, st)) != NCDE_OK) return rc;
+            // Behind the cooperative sequence: the WHOLE pass again on the per-workgroup kernels, every launch with run_if = the status
+            // word -- each returns at once (a few microseconds per window) unless a cooperative launch gave up, and then they overwrite
+            // every output of this call: grad_z0, the hidden-layer partials, the output-layer partials, the reductions.
+            a.run_if = a.coop_status;
+            if ((rc = tiled_adj_run(p, t, pw, a, n_rsteps, gB, st)) != NCDE_OK) return rc;
+            return tiled_adj_reduce(p, y, t, pw, g, a.gpart, gB, a.run_if, st);
         }
-        coop_mark_in_flight(st);
-    } else
-    for (int hi = n_rsteps, first = 1; hi >= 1; hi -= t.window, first = 0) {
-        const int lo = std::max(0, hi - t.window);
-        a.win_hi = hi; a.win_lo = lo; a.resume = first ? 0 : 1;
-        hipLaunchKernelGGL(fa, dim3(t.n_st), dim3(64 * nwv_launch), lds, st, a);
-        const int n_sc = (hi - lo) * t.S;
-        hipLaunchKernelGGL(fb, gridB, dim3(threadsB), ldsB, st, a, n_sc, t.n_st, gB);
-        if (fb2) hipLaunchKernelGGL(fb2, gridB, dim3(256), 0, st, a, n_sc, t.n_st, gB2);
-        if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
     }
-    if (main_kernel_only) return NCDE_OK;
-    // deterministic reductions: hidden-layer partials of the sweep, then the part-group partials of pass B
-    ReduceSegs segs{};
-    int n = 0;
-    for (int l = 0; l < p->n_layers; ++l) {
-        bool first = true;
-        for (int q = 0; q < l; ++q)
-            if (p->layer_W[q] == p->layer_W[l]) first = false;
-        if (!first) continue;
-        if (!g->grad_layer_W[l] || !g->grad_layer_b[l]) return NCDE_ERR_INVALID;
-        segs.off[n] = y.gW_off[l]; segs.len[n] = p->layer_out[l] * p->layer_in[l]; segs.dst[n] = g->grad_layer_W[l]; ++n;
-        segs.off[n] = y.gb_off[l]; segs.len[n] = p->layer_out[l]; segs.dst[n] = g->grad_layer_b[l]; ++n;
-    }
-    segs.n = n;
-    hipLaunchKernelGGL(ncde_reduce_partials, dim3((t.gstride + 255) / 256), dim3(256), 0, st, (const float*)a.gpart, t.n_st, t.gstride, segs);
-    if (!g->grad_Wo || !g->grad_bo) return NCDE_ERR_INVALID;
-    ReduceSegs so{};
-    const int wo_sz = p->hidden * p->channels * y.dlast;
-    so.n = 2;
-    so.off[0] = 0; so.len[0] = wo_sz; so.dst[0] = g->grad_Wo;
-    so.off[1] = wo_sz; so.len[1] = p->hidden * p->channels; so.dst[1] = g->grad_bo;
-    hipLaunchKernelGGL(ncde_reduce_partials, dim3(((int)t.theta_o + 255) / 256), dim3(256), 0, st, (const float*)gB, t.parts, (int)t.theta_o, so);
-    if (gated) {      // the gate head's partials: written by fb2, or by the two-head pass behind the tanh head's
-        if (!g->grad_Wg || !g->grad_bg) return NCDE_ERR_INVALID;
-        so.dst[0] = g->grad_Wg;
-        so.dst[1] = g->grad_bg;
-        hipLaunchKernelGGL(ncde_reduce_partials, dim3(((int)t.theta_o + 255) / 256), dim3(256), 0, st, (const float*)gB2, t.parts, (int)t.theta_o, so);
-    }
-    if (coop) {
-        // Behind the cooperative sequence: the WHOLE pass again on the per-workgroup kernels, every launch with run_if = the status word
-        // -- each returns at once (a few microseconds per window) unless a cooperative launch gave up, and then they overwrite every
-        // output of this call: grad_z0, the hidden-layer partials, the output-layer partials, the reductions.  (cooperative: original
-        // field only, so there is no second head.)
-        a.run_if = a.coop_status;
-        if (ncde_lds_optin((const void*)fa_pw, lds_pw) != hipSuccess) return NCDE_ERR_HIP;
-        for (int hi = n_rsteps, first = 1; hi >= 1; hi -= t.window, first = 0) {
-            const int lo = std::max(0, hi - t.window);
-            a.win_hi = hi; a.win_lo = lo; a.resume = first ? 0 : 1;
-            hipLaunchKernelGGL(fa_pw, dim3(t.n_st), dim3(64 * nwv), lds_pw, st, a);
-            hipLaunchKernelGGL(fb_pw, gridB_pw, dim3(256), 0, st, a, (hi - lo) * t.S, t.n_st, gB);
-            if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-        }
-        hipLaunchKernelGGL(ncde_reduce_partials_if, dim3((t.gstride + 255) / 256), dim3(256), 0, st, a.run_if, (const float*)a.gpart, t.n_st, t.gstride, segs);
-        so.dst[0] = g->grad_Wo;
-        so.dst[1] = g->grad_bo;
-        hipLaunchKernelGGL(ncde_reduce_partials_if, dim3(((int)t.theta_o + 255) / 256), dim3(256), 0, st, a.run_if, (const float*)gB, t.parts_pw, (int)t.theta_o, so);
-    }
-    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+    const int rc = tiled_adj_run(p, t, pw, a, n_rsteps, gB, st);
+    if (rc != NCDE_OK || main_kernel_only) return rc;
+    return tiled_adj_reduce(p, y, t, pw, g, a.gpart, gB, nullptr, st);
 }

@@ -65,7 +65,11 @@ def run_adjoint_direct(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=
     """Call ncde_adjoint through the C-ABI on a GIVEN forward solution (e.g. the reference's own z_out):
     isolates the adjoint kernel from forward round-off (a last-bit change of z can flip a ReLU mask).
     With `stages` (a stage record [(T-1)*S, B, H]) it calls ncde_backward (exact discrete backward) instead."""
-    import ctypes
+    return collect_adjoint(enqueue_adjoint(prepare_adjoint(case, z_out, flags, device, stages)))
+
+
+def prepare_adjoint(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None):
+    """The device inputs and (NaN-filled) gradient buffers of one run_adjoint_direct call, uploaded on the current stream."""
     from ncde_amd import solver
     m = case["meta"]
     coeffs = torch.from_numpy(case["coeffs"]).to(device)
@@ -88,21 +92,41 @@ def run_adjoint_direct(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=
         g.grad_Wg, g.grad_bg = gbuf[id(spec.Wg)].data_ptr(), gbuf[id(spec.bg)].data_ptr()
     if spec.kind == "gru":
         g.grad_Wr, g.grad_br = gbuf[id(spec.Wr)].data_ptr(), gbuf[id(spec.br)].data_ptr()
-    if stages is not None:
-        rec = torch.from_numpy(np.ascontiguousarray(stages)).to(device)
+    rec = None if stages is None else torch.from_numpy(np.ascontiguousarray(stages)).to(device)
+    return {"p": p, "g": g, "gz0": gz0, "gbuf": gbuf, "func": func, "z_out": z_out, "gout": gout, "rec": rec, "device": device,
+            "keep": (coeffs, z0)}
+
+
+def workspace(prep):
+    """The current stream's workspace arena as the call of `prep` will use it."""
+    from ncde_amd import solver
+    return solver._workspace(prep["p"], 1 if prep["rec"] is None else 2, prep["device"])
+
+
+def enqueue_adjoint(prep):
+    """Enqueue the call of `prep` on the current stream without synchronising (every input already on the device)."""
+    import ctypes
+    p, g, z_out, gout, rec = prep["p"], prep["g"], prep["z_out"], prep["gout"], prep["rec"]
+    ws = workspace(prep)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if rec is not None:
         assert rec.numel() * 4 == _lib.lib().ncde_stage_record_bytes(ctypes.byref(p))
-        ws = solver._workspace(p, 2, device)
-        rc = _lib.lib().ncde_backward(ctypes.byref(p), rec.data_ptr(), gout.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-                                      ws.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = _lib.lib().ncde_backward(ctypes.byref(p), rec.data_ptr(), gout.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel(), stream)
         _lib.check(rc, "ncde_backward")
     else:
-        ws = solver._workspace(p, 1, device)
-        rc = _lib.lib().ncde_adjoint(ctypes.byref(p), z_out.data_ptr(), gout.data_ptr(), ctypes.byref(g), ws.data_ptr(),
-                                     ws.numel(), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        rc = _lib.lib().ncde_adjoint(ctypes.byref(p), z_out.data_ptr(), gout.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel(), stream)
         _lib.check(rc, "ncde_adjoint")
+    return prep
+
+
+def collect_adjoint(prep):
+    """Synchronise and return dict(dz0, kernel, grads{name: array}) of an enqueued call."""
+    import ctypes
     torch.cuda.synchronize()
-    name = (_lib.lib().ncde_kernel_name(ctypes.byref(p), 2 if stages is not None else 1) or b"?").decode()
-    return {"dz0": gz0.cpu().numpy(), "kernel": name, "grads": {k: gbuf[id(v)].cpu().numpy() for k, v in func.p.items() if id(v) in gbuf}}
+    name = (_lib.lib().ncde_kernel_name(ctypes.byref(prep["p"]), 1 if prep["rec"] is None else 2) or b"?").decode()
+    gbuf = prep["gbuf"]
+    return {"dz0": prep["gz0"].cpu().numpy(), "kernel": name,
+            "grads": {k: gbuf[id(v)].cpu().numpy() for k, v in prep["func"].p.items() if id(v) in gbuf}}
 
 
 def coop_status_word(case, pass_, flags=_lib.FLAG_AUTO, device="cuda"):

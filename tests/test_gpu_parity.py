@@ -2428,6 +2428,48 @@ def test_cooperative_calls_on_two_streams_do_not_wait_for_each_other(gpu_lib):
         assert gu.relerr(o.cpu().numpy(), ref) <= TIGHT_Z
 
 
+def test_backward_gated_out_by_another_streams_cooperative_sequence(gpu_lib):
+    """a backward call that finds another stream's cooperative sequence still in flight runs the per-workgroup
+    sequence -- and must reduce the part-group count THAT sequence wrote (here 4, against the cooperative pass B's 16), and leave
+    the status word it advertises at 0.  s1: a long sleep, then a cooperative call (its flight event stays pending); s2 waits for s1
+    (nothing overlaps on the GPU), its workspace arena is filled with NaN, then the same call is refused by the gate."""
+    import gpu_util
+    from ncde_amd import _lib
+    case = _seeded_case("linear", "rk4", False, B=512, L=6, C=80, H=128, HH=128, nl=3, seed=952)
+    ex = case["expect"]
+    assert "coop" in gpu_util.kernel_names(case)[1] and "coop" in gpu_util.kernel_names(case)[2]
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    for stages in (None, case["stage_record"]):
+        ref = gpu_util.run_adjoint_direct(case, ex["z_out"], flags=_lib.FLAG_NO_COOP, stages=stages)
+        # every input on the device before anything is enqueued on s1 (an upload behind the sleep would block the host until it ends)
+        preps = [gpu_util.prepare_adjoint(case, ex["z_out"], stages=stages) for _ in range(2)]
+        for st, prep in zip((s1, s2), preps):
+            with torch.cuda.stream(st):
+                gpu_util.workspace(prep)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s1):
+            torch.cuda._sleep(2_000_000_000)
+            gpu_util.enqueue_adjoint(preps[0])
+        s2.wait_stream(s1)
+        with torch.cuda.stream(s2):
+            gpu_util.workspace(preps[1]).fill_(255)      # (all-ones bytes: NaN floats, a non-zero status word)
+            gpu_util.enqueue_adjoint(preps[1])
+        assert not s1.query(), "the sleep ended before the second call was enqueued: the gate was not exercised"
+        got1, got2 = gpu_util.collect_adjoint(preps[0]), gpu_util.collect_adjoint(preps[1])
+        pass_ = 1 if stages is None else 2
+        with torch.cuda.stream(s2):
+            assert gpu_util.coop_status_word(case, pass_) == 0
+        with torch.cuda.stream(s1):
+            assert gpu_util.coop_status_word(case, pass_) == 0
+        assert np.isfinite(got2["dz0"]).all() and all(np.isfinite(v).all() for v in got2["grads"].values())
+        assert gu.relerr(got2["dz0"], ref["dz0"]) <= 2e-6, gu.relerr(got2["dz0"], ref["dz0"])
+        for k in ref["grads"]:
+            assert gu.relerr(got2["grads"][k], ref["grads"][k]) <= 2e-6, (stages is None, k, gu.relerr(got2["grads"][k], ref["grads"][k]))
+        assert gu.relerr(got1["dz0"], ref["dz0"]) <= 2e-5      # (the cooperative sequence: see test_cooperative_output_phase_vs_oracle)
+        for k in ref["grads"]:
+            assert gu.relerr(got1["grads"][k], ref["grads"][k]) <= 2e-5, (stages is None, k)
+
+
 @pytest.mark.parametrize("B,L,C,H,HH,nl,interp,method,seq", [
     (123, 3, 40, 64, 128, 2, "linear", "rk4", False),       # 8 sample tiles = ONE group of 8 members (2 state-unit blocks each), ragged last tile
     (256, 3, 20, 128, 128, 3, "cubic", "midpoint", True),   # 16 tiles = two groups of 8 (4 blocks per member, one wave each), sequence outputs
