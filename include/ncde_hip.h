@@ -43,8 +43,12 @@ typedef enum NcdeStatus {
 } NcdeStatus;
 
 /* control-path evaluator: replaces LinearInterpolation.derivative (interpolation_linear.py:212-234)
- * and NaturalCubicSpline.derivative (interpolation_cubic.py:315-336) on the default integer grid. */
-typedef enum NcdeInterp { NCDE_INTERP_LINEAR = 0, NCDE_INTERP_CUBIC = 1 } NcdeInterp;
+ * and NaturalCubicSpline.derivative (interpolation_cubic.py:315-336) on the default integer grid.
+ * NCDE_INTERP_QUINTIC is a general piecewise-quintic control (any knot grid through the time plan): the representation of
+ * SmoothLinearInterpolation with match_second_derivatives=True (src/ncde/interpolation.py:6-123) on its refined knot grid
+ * (ncde_prepare_smooth).  It runs on the batch-tiled, generic and variant families only: NCDE_FLAG_FORCE_FAST and the
+ * ncde_dopri5_* entry points answer NCDE_ERR_UNSUPPORTED for it. */
+typedef enum NcdeInterp { NCDE_INTERP_LINEAR = 0, NCDE_INTERP_CUBIC = 1, NCDE_INTERP_QUINTIC = 2 } NcdeInterp;
 
 /* fixed-step solver: replaces Euler / Midpoint / RK4 (3/8 rule) of fixed_grid.py:6-29,
  * rk_common.py:106-114 with options={'step_size': 1}. */
@@ -117,7 +121,9 @@ typedef struct NcdeProblem {
 
     /* control-path coefficients, row-major, element strides:
      *   linear/rectilinear: coeffs[b][t][c], t < T           (linear_interpolation_coeffs output)
-     *   cubic:              coeffs[b][p][4C] = a|b|2c|3d, p < T-1 (natural_cubic_coeffs output)    */
+     *   cubic:              coeffs[b][p][4C] = a|b|2c|3d, p < T-1 (natural_cubic_coeffs output)
+     *   quintic:            coeffs[b][p][6C] = a|b|2c|3d|4e|5f, p < T-1; with f = t - knot[p]:
+     *                       dX/dt = b + f(2c + f(3d + f(4e + f 5f))),  X = a + f(b + f(2c/2 + f(3d/3 + f(4e/4 + f 5f/5))))    */
     const float* coeffs;
     int64_t coeffs_stride_b;
     int64_t coeffs_stride_t;
@@ -335,6 +341,17 @@ int ncde_prepare_cubic(const float* x, int B, int L, int C, float* out, void* wo
  * preparation, whose output the caller pairs with a grid of 2L-1 times).  Cubic: non-uniform natural spline. */
 int ncde_prepare_linear_grid(const float* x, const float* t, int B, int L, int C, int rectilinear_time_index, float* out, void* stream);
 int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+
+/* Smoothed-linear control paths (SmoothLinearInterpolation, src/ncde/interpolation.py:6-123: cubic / quintic matching of the
+ * slopes in (k, k + eps) after every interior knot k of the integer grid) as a piecewise polynomial on the REFINED knot grid
+ * 0, 1, 1+eps, 2, 2+eps, ..., T-2, T-2+eps, T-1  (eps < 1: P = 2T-3 pieces;  eps == 1: the integer grid, P = T-1 pieces).
+ * x: linear coefficients [B, T, C] (device, contiguous), order 3 -> out [B, P, 4C] = a|b|2c|3d (an NCDE_INTERP_CUBIC tensor),
+ * order 5 -> out [B, P, 6C] = a|b|2c|3d|4e|5f (NCDE_INTERP_QUINTIC).  One launch on `stream`, no workspace; the matching
+ * coefficients are evaluated in fp32 in the operation order of _setup_cubic / _setup_quintic_matching_coefficients.
+ * Pieces outside a matching region are the linear piece (higher parts zero).  ncde_smooth_pieces: P, or < 0 for bad arguments. */
+int ncde_smooth_pieces(int T, double eps);
+int ncde_prepare_smooth(const float* x, int B, int T, int C, double eps, int order, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@ import os
 NCDE_ABI_VERSION = 4
 NCDE_MAX_LAYERS = 8
 
-INTERP = {"linear": 0, "cubic": 1}
+INTERP = {"linear": 0, "cubic": 1, "quintic": 2}
+INTERP_PARTS = {"linear": 1, "cubic": 4, "quintic": 6}      # floats per channel of one coefficient row
 METHOD = {"euler": 0, "midpoint": 1, "rk4": 2}
 OUT_INTERVAL, OUT_KNOTS, OUT_TIMES = 0, 1, 2
 FIELD_KIND = {"original": 0, "minimal": 1, "gru": 2}
@@ -115,6 +116,7 @@ EXPORTS = (
     "ncde_version", "ncde_last_error_string", "ncde_num_outputs", "ncde_workspace_bytes",
     "ncde_kernel_name", "ncde_forward", "ncde_adjoint", "ncde_time_kernel",
     "ncde_prepare_workspace_bytes", "ncde_prepare_linear", "ncde_prepare_cubic", "ncde_prepare_linear_grid", "ncde_prepare_cubic_grid",
+    "ncde_smooth_pieces", "ncde_prepare_smooth",
     "ncde_stage_record_bytes", "ncde_forward_record", "ncde_backward",
     "ncde_time_plan_build", "ncde_dopri5_workspace_bytes", "ncde_dopri5_forward", "ncde_dopri5_adjoint",
     "ncde_dopri5_record_bytes", "ncde_dopri5_forward_record", "ncde_dopri5_backward", "ncde_dopri5_kernel_name",
@@ -187,6 +189,10 @@ def lib():
     h.ncde_prepare_linear.restype = ctypes.c_int
     h.ncde_prepare_cubic.argtypes = [vp, i32, i32, i32, vp, vp, sz, vp]
     h.ncde_prepare_cubic.restype = ctypes.c_int
+    h.ncde_smooth_pieces.argtypes = [i32, ctypes.c_double]
+    h.ncde_smooth_pieces.restype = ctypes.c_int
+    h.ncde_prepare_smooth.argtypes = [vp, i32, i32, i32, ctypes.c_double, i32, vp, vp]
+    h.ncde_prepare_smooth.restype = ctypes.c_int
     h.ncde_prepare_linear_grid.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     h.ncde_prepare_linear_grid.restype = ctypes.c_int
     h.ncde_prepare_cubic_grid.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]

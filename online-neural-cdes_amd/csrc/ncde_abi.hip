@@ -59,7 +59,7 @@ int validate(const NcdeProblem* p) {
     if (!p) return fail(NCDE_ERR_INVALID, "problem is NULL");
     if (p->batch < 1 || p->channels < 1 || p->hidden < 1) return fail(NCDE_ERR_INVALID, "batch/channels/hidden must be >= 1");
     if (p->n_knots < 2) return fail(NCDE_ERR_INVALID, "Must have a time dimension of size at least 2 (n_knots=%d)", p->n_knots);
-    if (p->interp != NCDE_INTERP_LINEAR && p->interp != NCDE_INTERP_CUBIC) return fail(NCDE_ERR_INVALID, "unknown interp %d", p->interp);
+    if (p->interp != NCDE_INTERP_LINEAR && p->interp != NCDE_INTERP_CUBIC && p->interp != NCDE_INTERP_QUINTIC) return fail(NCDE_ERR_INVALID, "unknown interp %d", p->interp);
     if (p->method != NCDE_EULER && p->method != NCDE_MIDPOINT && p->method != NCDE_RK4_38)
         return fail(NCDE_ERR_INVALID, "Invalid method %d. Must be one of {euler, midpoint, rk4}", p->method);
     if (p->output != NCDE_OUT_INTERVAL && p->output != NCDE_OUT_KNOTS && p->output != NCDE_OUT_TIMES) return fail(NCDE_ERR_INVALID, "unknown output mode %d", p->output);
@@ -83,10 +83,14 @@ int validate(const NcdeProblem* p) {
         d = p->layer_out[l];
     }
     if (!p->Wo || !p->bo || !p->coeffs || !p->z0) return fail(NCDE_ERR_INVALID, "NULL Wo/bo/coeffs/z0");
-    if (p->coeffs_stride_t < (p->interp == NCDE_INTERP_CUBIC ? 4 : 1) * (int64_t)p->channels)
+    if (p->coeffs_stride_t < (p->interp == NCDE_INTERP_QUINTIC ? 6 : (p->interp == NCDE_INTERP_CUBIC ? 4 : 1)) * (int64_t)p->channels)
         return fail(NCDE_ERR_INVALID, "coeffs_stride_t %lld too small", (long long)p->coeffs_stride_t);
     return NCDE_OK;
 }
+
+// A piecewise-quintic control never runs on a register-resident kernel set (their dX/dt staging knows the linear and cubic rows only):
+// batch-tiled (zero-padded as for any shape), then generic / variant.
+bool fast_supported(const NcdeProblem* p, int pass) { return p->interp != NCDE_INTERP_QUINTIC && ncde_fast_supported(p, pass); }
 
 int generic_supported(const NcdeProblem* p, const Layout& y, int pass) {
     if (pass == 0 && y.lds_fwd > (size_t)kLdsLimit)
@@ -217,7 +221,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, int target = 0) {
     for (int l = 0; l < p->n_layers; ++l) { q.layer_W[l] = fake(P.slot_W[l]); q.layer_b[l] = fake(P.slot_b[l]); }
     q.Wo = fake(P.slot_Wo); q.bo = fake(P.slot_bo);
     if (p->field_kind == NCDE_FIELD_MINIMAL) { q.Wg = fake(P.slot_Wg); q.bg = fake(P.slot_bg); }
-    P.ok = target == 0 ? ncde_tiled_supported(&q, pass) : ncde_fast_supported(&q, pass);
+    P.ok = target == 0 ? ncde_tiled_supported(&q, pass) : fast_supported(&q, pass);
     return P;
 }
 // the padded plan a problem takes, if any: a shape-specialised kernel set first, then the batch-tiled family
@@ -273,7 +277,7 @@ int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
                                          // (multiples of 16 / 4; 2.8x the generic family at cfg2 widths, 10x at cfg5's), else generic / variant
         // (round 4: the shape-specialised kernels walk the plan too -- forward of both shapes, continuous adjoint of (32, 32, 20) nl = 3
         // and of H = 64 / C <= 4; the planned discrete backward stays on the batch-tiled family)
-        const bool fast_ok = !y.variant && !(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_TILED)) && ncde_fast_supported(p, pass);
+        const bool fast_ok = !y.variant && !(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_TILED)) && fast_supported(p, pass);
         if (p->flags & NCDE_FLAG_FORCE_FAST) {
             if (!fast_ok) return fail(NCDE_ERR_UNSUPPORTED, "no shape-specialised kernel for this problem on a general time axis (pass %d)", pass);
             return 1;
@@ -300,7 +304,7 @@ int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
         return 3;
     }
     if ((p->flags & NCDE_FLAG_FORCE_TILED) && ncde_tiled_supported(p, pass)) return 2;   // also ahead of a specialised kernel
-    const bool fast_ok = ncde_fast_supported(p, pass);
+    const bool fast_ok = fast_supported(p, pass);
     if (p->flags & NCDE_FLAG_FORCE_FAST) {
         if (!fast_ok) return fail(NCDE_ERR_UNSUPPORTED, "no shape-specialised kernel for this problem (pass %d)", pass);
         return 1;
@@ -449,6 +453,7 @@ int dopri5_prepare(const NcdeProblem* p, const NcdeTimeSpec* ts, const NcdeAdapt
     q->time_plan = nullptr;
     rc = validate(q);
     if (rc != NCDE_OK) return rc;
+    if (q->interp == NCDE_INTERP_QUINTIC) return fail(NCDE_ERR_UNSUPPORTED, "dopri5 evaluates linear and cubic controls only (piecewise-quintic: fixed-step methods)");
     if (!ts || !ts->t || ts->n_t < 2) return fail(NCDE_ERR_INVALID, "time spec: need >= 2 output times");
     if (opt && (!(opt->rtol > 0.0) || !(opt->atol >= 0.0))) return fail(NCDE_ERR_INVALID, "rtol must be > 0 and atol >= 0");
     char why[200] = "";

@@ -7,6 +7,23 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// Piecewise-quintic control (NCDE_INTERP_QUINTIC): p -> this channel's entry of the piece's row a | b | 2c | 3d | 4e | 5f, parts `cs`
+// floats apart, f = t - knot.  value = false: dX/dt = b + f(2c + f(3d + f(4e + f 5f)));  true: X = a + f(b + f(2c/2 + f(3d/3 + f(4e/4 + f 5f/5)))).
+__device__ __forceinline__ float quintic_eval(const float* p, int cs, float f, bool value) {
+    const float bb = p[cs], c2 = p[2 * cs], d3 = p[3 * cs], e4 = p[4 * cs], f5 = p[5 * cs];
+    if (value) {
+        float inner = 0.25f * e4 + (f5 * f) / 5.0f;
+        inner = d3 / 3.0f + inner * f;
+        inner = 0.5f * c2 + inner * f;
+        inner = bb + inner * f;
+        return p[0] + inner * f;
+    }
+    float inner = e4 + f5 * f;
+    inner = d3 + inner * f;
+    inner = c2 + inner * f;
+    return bb + inner * f;
+}
+
 #define NCDE_TILE 16  // samples per workgroup tile = N of v_mfma_f32_16x16x4_f32
 
 // Kernel argument block (passed by value).

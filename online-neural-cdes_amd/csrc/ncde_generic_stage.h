@@ -25,6 +25,8 @@ __device__ void load_dx(const KArgs& a, int b0, const StageDesc& sd, float* DX, 
             if (a.interp == NCDE_INTERP_LINEAR) {
                 v = p[a.cs_t + c] - p[c];
                 if (sd.kdt != 1.0f) v = v / sd.kdt;   // user knot grid: (c[i+1]-c[i]) / (t[i+1]-t[i]), interpolation_linear.py:198
+            } else if (a.interp == NCDE_INTERP_QUINTIC) {
+                v = quintic_eval(p + c, a.C, frac, false);
             } else {
                 const float bb = p[a.C + c], cc = p[2 * a.C + c], dd = p[3 * a.C + c];
                 const float inner = cc + dd * frac;

@@ -8,6 +8,7 @@
 // All on the default integer time grid, fp32, operation order of the reference (build uses -ffp-contract=off).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "ncde_hip.h"
@@ -628,9 +629,66 @@ __global__ void ncde_cubic_diag_kernel(int L, float* diag_swept) {
 }
 
 
+// Smoothed-linear control path on its refined knot grid (src/ncde/interpolation.py:151-191: the matching polynomial after every
+// interior knot k, built from rows k-1, k, k+1 of the linear coefficients, in the reference's operation order; fp32, no contraction).
+// One thread per (sample, piece, channel).  Piece 0 is linear; eps < 1: piece 1 + 2(k-1) is the matching piece of knot k on
+// [k, k+eps], the next one the linear remainder on [k+eps, k+1]; eps == 1: piece k is the matching piece of knot k.
+struct SmoothScal { float eps, inv_e2, inv_3e2, inv_e3, four_eps, inv_2e3, e2, neg_inv_10e2; };
+__global__ __launch_bounds__(256) void ncde_smooth_coeffs_kernel(const float* __restrict__ x, int B, int T, int C, int P, int order, bool split,
+                                                                 SmoothScal k, float* __restrict__ out) {
+    const int W = order == 3 ? 4 : 6;
+    const long long total = (long long)B * P * C;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int c = (int)(e % C), p = (int)((e / C) % P), b = (int)(e / ((long long)C * P));
+        const int kn = p == 0 ? 0 : (split ? 1 + ((p - 1) >> 1) : p);
+        const bool match = p > 0 && (!split || ((p - 1) & 1) == 0);
+        const float* xr = x + ((long long)b * T + kn) * C + c;
+        const float xk = xr[0], xn = xr[C];
+        float v[6] = {xk, xn - xk, 0.0f, 0.0f, 0.0f, 0.0f};
+        if (p > 0) {
+            const float xp = xr[-C];
+            const float x_eps = xk + k.eps * (xn - xk);
+            const float d_prev = xk - xp, d_next = xn - xk;
+            if (!match) {
+                v[0] = x_eps;
+            } else if (order == 3) {
+                const float Bq = k.inv_e2 * (3.0f * (x_eps - d_prev * k.eps - xk) - k.eps * (d_next - d_prev));
+                const float Aq = k.inv_3e2 * (d_next - d_prev - 2.0f * Bq * k.eps);
+                v[1] = d_prev; v[2] = 2.0f * Bq; v[3] = 3.0f * Aq;
+            } else {
+                const float Cq = k.inv_e3 * (10.0f * (x_eps - d_prev * k.eps - xk) - k.four_eps * (d_next - d_prev));
+                const float Bq = k.inv_2e3 * (2.0f * (d_next - d_prev) - 3.0f * Cq * k.e2);
+                const float Aq = k.neg_inv_10e2 * (6.0f * Bq * k.eps + 3.0f * Cq);
+                v[1] = d_prev; v[3] = 3.0f * Cq; v[4] = 4.0f * Bq; v[5] = 5.0f * Aq;
+            }
+        }
+        float* o = out + ((long long)b * P + p) * (W * C) + c;
+        for (int q = 0; q < W; ++q) o[q * C] = v[q];
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int ncde_smooth_pieces(int T, double eps) {
+    if (T < 2 || !(eps > 0.0) || eps > 1.0) return NCDE_ERR_INVALID;
+    return eps < 1.0 ? 2 * T - 3 : T - 1;
+}
+
+int ncde_prepare_smooth(const float* x, int B, int T, int C, double eps, int order, float* out, void* stream) {
+    if (!x || !out || B < 1 || T < 2 || C < 1 || (order != 3 && order != 5) || !(eps > 0.0) || eps > 1.0) return NCDE_ERR_INVALID;
+    const int P = ncde_smooth_pieces(T, eps);
+    SmoothScal k;      // the reference's Python scalars, evaluated in double and rounded once where they meet an fp32 tensor
+    const double e2 = std::pow(eps, 2.0), e3 = std::pow(eps, 3.0);
+    k.eps = (float)eps; k.inv_e2 = (float)(1.0 / e2); k.inv_3e2 = (float)(1.0 / (3.0 * e2));
+    k.inv_e3 = (float)(1.0 / e3); k.four_eps = (float)(4.0 * eps); k.inv_2e3 = (float)(1.0 / (2.0 * e3));
+    k.e2 = (float)e2; k.neg_inv_10e2 = (float)(-(1.0 / (10.0 * e2)));
+    const long long total = (long long)B * P * C;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(ncde_smooth_coeffs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, B, T, C, P, order, eps < 1.0, k, out);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+}
 
 int64_t ncde_prepare_workspace_bytes(int kind, int B, int L, int C) {
     if (B < 1 || L < 2 || C < 1) return NCDE_ERR_INVALID;

@@ -26,8 +26,9 @@
 
 namespace {
 
-// dX/dt(t) of the tile's samples -> DX[(c>>2)][s][c&3]
-template <int NS, int NT>
+// dX/dt(t) of the tile's samples -> DX[(c>>2)][s][c&3].  QUINTIC = false compiles the piecewise-quintic arm out: the cooperative
+// kernels never see that kind (tiled_coop_plan), and their code stays what it was before the kind existed.
+template <int NS, int NT, bool QUINTIC = true>
 __device__ __forceinline__ void tl_load_dx(const KArgs& a, int b0, int idx, float frac, float kdt, float* DX, int tid) {
     constexpr int NSP = NS * 16;
     const int C = a.C, Cc = a.Cc;      // Cc: channels of the coefficient tensor (< C when the problem was zero-padded)
@@ -40,6 +41,8 @@ __device__ __forceinline__ void tl_load_dx(const KArgs& a, int b0, int idx, floa
             if (a.interp == NCDE_INTERP_LINEAR) {
                 v = p[a.cs_t + c] - p[c];
                 if (kdt != 1.0f) v = v / kdt;      // user knot grid (interpolation_linear.py:231-234); 1 on the default grid
+            } else if (QUINTIC && a.interp == NCDE_INTERP_QUINTIC) {
+                v = quintic_eval(p + c, Cc, frac, false);
             } else {
                 const float bb = p[Cc + c], cc = p[2 * Cc + c], dd = p[3 * Cc + c];
                 const float inner = cc + dd * frac;
@@ -226,6 +229,8 @@ __device__ __forceinline__ void tl_load_cin(const KArgs& a, int b0, const StageD
             if (a.interp == NCDE_INTERP_LINEAR) {
                 const float d = p[a.cs_t + c] - p[c];
                 v = value ? p[c] + (sd.frac * d) / sd.kdt : (sd.kdt != 1.0f ? d / sd.kdt : d);
+            } else if (a.interp == NCDE_INTERP_QUINTIC) {
+                v = quintic_eval(p + c, Cc, sd.frac, value);
             } else {
                 const float aa = p[c], bb = p[Cc + c], cc = p[2 * Cc + c], dd = p[3 * Cc + c];
                 if (value) {
@@ -839,7 +844,7 @@ __global__ __launch_bounds__(64 * NWV) void ncde_fwd_tiled(KArgs a) {
             if constexpr (DIRECT != 0) {
                 tl_load_cin<NS, NT>(a, b0, sd, a.field_input == NCDE_INPUT_EVALUATE, YS, H, tid);
             } else if (a.interp != NCDE_INTERP_LINEAR || idx != cur_idx) {
-                tl_load_dx<NS, NT>(a, b0, idx, sd.frac, sd.kdt, DX, tid);
+                tl_load_dx<NS, NT, COOP == 0>(a, b0, idx, sd.frac, sd.kdt, DX, tid);
                 cur_idx = idx;
                 dx_new = true;
             }
@@ -1704,6 +1709,8 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
                 v = cp[a.cs_t + c] - cp[c];
                 if (value) v = cp[c] + (frac * v) / kdt;
                 else if (kdt != 1.0f) v = v / kdt;
+            } else if (COOP == 0 && a.interp == NCDE_INTERP_QUINTIC) {      // (compiled out of the cooperative sweep: tiled_coop_plan)
+                v = quintic_eval(cp + c, Cc, frac, value);
             } else {
                 const float bb = cp[Cc + c], cc = cp[2 * Cc + c], dd = cp[3 * Cc + c];
                 if (value) {
@@ -3130,6 +3137,7 @@ CoopPlan tiled_coop_plan(const NcdeProblem* p) {
     CoopPlan c{};
     if (p->flags & (NCDE_FLAG_NO_COOP | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_DEBUG_PROFILE)) return c;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL || p->n_layers < 1) return c;      // (any time axis: round 6)
+    if (p->interp == NCDE_INTERP_QUINTIC) return c;      // piecewise-quintic controls: the per-workgroup kernels only
     if (p->layer_out[p->n_layers - 1] != 128 || p->hidden > 128 || p->hidden % 16 || p->channels % 4) return c;
     const int ncq = p->channels / 4;
     if (ncq != 5 && ncq != 10 && ncq != 20) return c;

@@ -39,6 +39,8 @@ __device__ void vr_load_cin(const KArgs& a, int b0, const StageDesc& sd, bool va
             if (a.interp == NCDE_INTERP_LINEAR) {
                 const float d = p[a.cs_t + c] - p[c];
                 v = value ? p[c] + (frac * d) / kdt : (kdt != 1.0f ? d / kdt : d);
+            } else if (a.interp == NCDE_INTERP_QUINTIC) {
+                v = quintic_eval(p + c, a.C, frac, value);
             } else {
                 const float aa = p[c], bb = p[a.C + c], cc = p[2 * a.C + c], dd = p[3 * a.C + c];
                 if (value) {

@@ -5,10 +5,12 @@ Same constructor arguments, same ``state_dict`` layout (``initial_linear.*``, ``
 itself is one fused HIP kernel per direction (see solver.py).  The two tiny Linears outside the solve
 stay ordinary torch modules.
 """
+import functools
+
 import torch
 from torch import nn
 
-from .interpolation import LinearInterpolation, NaturalCubicSpline
+from .interpolation import LinearInterpolation, NaturalCubicSpline, SmoothLinearInterpolation
 from .solver import cdeint
 from .vector_fields import GRUGatedVectorField, MinimalGatedVectorField, OriginalVectorField
 
@@ -17,6 +19,7 @@ SPLINES = {
     "linear": LinearInterpolation,
     "rectilinear": LinearInterpolation,
 }
+SMOOTHED = {"linear_cubic_smoothing": False, "linear_quintic_smoothing": True}      # name -> match_second_derivatives
 VECTOR_FIELDS = {"original": OriginalVectorField, "minimal": MinimalGatedVectorField, "gru": GRUGatedVectorField}
 
 
@@ -42,11 +45,18 @@ class NeuralCDE(nn.Module):
 
         if self.initial_dim > 0:
             self.initial_linear = nn.Linear(self.initial_dim, hidden_dim)
-        if interpolation in ("linear_cubic_smoothing", "linear_quintic_smoothing", "rectilinear_cubic_smoothing"):
-            raise NotImplementedError("smoothed interpolation schemes are outside the fused path (SURVEY.md §2 row 9)")
-        assert interpolation in SPLINES, "Unrecognised interpolation scheme {}".format(interpolation)
-        assert interpolation_eps in (None, 1)
-        self.spline = SPLINES[interpolation]
+        if interpolation == "rectilinear_cubic_smoothing":      # (the reference maps this name to NotImplemented, ncde.py:22)
+            raise NotImplementedError("interpolation 'rectilinear_cubic_smoothing' is not implemented (nor is it in the reference)")
+        if interpolation in SMOOTHED:      # src/ncde/ncde.py:115-121
+            assert interpolation_eps is None or 0 < interpolation_eps <= 1, "interpolation_eps must be None or in (0, 1]"
+            quintic = SMOOTHED[interpolation]
+            # (a partial, not a lambda: the module stays picklable -- torch.save(model) -- like the schemes that store a class)
+            self.spline = functools.partial(SmoothLinearInterpolation, gradient_matching_eps=interpolation_eps,
+                                            match_second_derivatives=quintic)
+        else:
+            assert interpolation in SPLINES, "Unrecognised interpolation scheme {}".format(interpolation)
+            assert interpolation_eps in (None, 1)
+            self.spline = SPLINES[interpolation]
         # the reference asserts solver in ["rk4", "dopri5"] (ncde.py:129); the fixed-step family is what is fused
         assert solver in ("rk4", "dopri5", "midpoint", "euler")
         self.atol, self.rtol = 1e-5, 1e-3

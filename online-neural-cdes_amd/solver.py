@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .interpolation import LinearInterpolation, NaturalCubicSpline
+from .interpolation import LinearInterpolation, NaturalCubicSpline, SmoothLinearInterpolation
 
 _FIXED_METHODS = ("euler", "midpoint", "rk4")
 _ALL_METHODS = ("dopri8", "dopri5", "bosh3", "fehlberg2", "adaptive_heun", "euler", "midpoint", "rk4",
@@ -65,6 +65,10 @@ def _unfused_reason(X, func, z0, t, adjoint, adjoint_params, method=None):
         return None      # tuple-valued z0: refused further down, on either path
     if not hasattr(func, "fused_spec"):
         return "func does not expose fused_spec()"
+    if method == "dopri5" and isinstance(X, SmoothLinearInterpolation) and X.gradient_matching_eps is not None:
+        # (a free-running adaptive solve parts ways between the path's two round-off-equivalent forms -- the class's region rule and
+        # the refined polynomial pieces -- as soon as one step is accepted on one side and rejected on the other: DESIGN.md)
+        return "method='dopri5' on a smoothed-linear control path"
     if method == "dopri5":      # the adaptive kernels evaluate the original field with the matmul input only
         spec = func.fused_spec()
         if spec.kind != "original" or spec.mode != "matmul":
@@ -81,7 +85,7 @@ def _unfused_reason(X, func, z0, t, adjoint, adjoint_params, method=None):
     for buffer in X.buffers():
         if buffer.requires_grad and (not adjoint or id(buffer) in ap):
             return "the control path requires gradients"
-    if z0.is_cuda and (z0.dtype != torch.float32 or X.fused_coeffs.dtype != torch.float32):
+    if z0.is_cuda and (z0.dtype != torch.float32 or X._coeffs.dtype != torch.float32):
         return "tensors are not fp32"
     return None
 
@@ -134,13 +138,16 @@ def _time_plan(X, t, method, step, device):
     tt = torch.as_tensor(t).detach()
     f64 = tt.dtype == torch.float64
     tv = np.ascontiguousarray(_host_times(t).numpy())
-    kn = None if X._default_grid else np.ascontiguousarray(X._t.detach().cpu().double().numpy())
-    key = (method, float(step), tv.tobytes(), f64, None if kn is None else kn.tobytes(), X.n_knots, str(device))
+    # (the grid the kernels walk: X's own knots, except for a smoothed-linear path, whose polynomial pieces sit on a refined grid
+    # while X.n_knots / X.grid_points keep describing the integer one)
+    kn, n_knots = X._plan_grid()
+    kn = None if kn is None else np.ascontiguousarray(kn.detach().cpu().double().numpy())
+    key = (method, float(step), tv.tobytes(), f64, None if kn is None else kn.tobytes(), n_knots, str(device))
     hit = _PLAN_CACHE.get(key)
     if hit is not None:
         return hit
     p = _lib.NcdeProblem()
-    p.abi_version, p.n_knots, p.method = _lib.NCDE_ABI_VERSION, X.n_knots, _lib.METHOD[method]
+    p.abi_version, p.n_knots, p.method = _lib.NCDE_ABI_VERSION, n_knots, _lib.METHOD[method]
     dp = ctypes.POINTER(ctypes.c_double)
     ts = _lib.NcdeTimeSpec(n_t=len(tv), time_is_f64=int(f64), t=tv.ctypes.data_as(dp), step_size=float(step),
                            knots=None if kn is None else kn.ctypes.data_as(dp))
@@ -169,8 +176,8 @@ def build_problem(coeffs, interp, z0, spec, method, output, flags=0, plan=None):
     p.batch, p.hidden = B, H
     if interp == "linear":
         p.n_knots, p.channels = coeffs.shape[1], coeffs.shape[2]
-    else:
-        p.n_knots, p.channels = coeffs.shape[1] + 1, coeffs.shape[2] // 4
+    else:      # piecewise polynomial: one row of a | b | 2c | 3d [| 4e | 5f] per piece
+        p.n_knots, p.channels = coeffs.shape[1] + 1, coeffs.shape[2] // _lib.INTERP_PARTS[interp]
     p.interp = _lib.INTERP[interp]
     p.method = _lib.METHOD[method]
     p.output = output
@@ -320,7 +327,7 @@ class _FusedCdeint(torch.autograd.Function):
         if cfg["plan"] is not None:
             n_out = cfg["plan"][1][0]
         else:
-            n_out = coeffs.shape[1] + (1 if cfg["interp"] == "cubic" else 0) if cfg["output"] == _lib.OUT_KNOTS else 2
+            n_out = coeffs.shape[1] + (0 if cfg["interp"] == "linear" else 1) if cfg["output"] == _lib.OUT_KNOTS else 2
         out = torch.empty(z0.shape[0], n_out, z0.shape[1], dtype=torch.float32, device=z0.device)
         record = (not cfg["adjoint"]) and cfg.get("needs_grad", True) and any(ctx.needs_input_grad)
         stages = None
@@ -639,7 +646,7 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
     r"""Solve ``z_t = z_{t_0} + \int f(z_s) dX_s``; returns ``[batch, len(t), hidden]`` like the reference.
 
     Same arguments as ``torchcde.cdeint`` (solver.py:140): X a LinearInterpolation / NaturalCubicSpline (default integer grid
-    or a user knot grid), ``func`` any ``nn.Module (t, z) -> [..., H, C]``, ``method`` in {euler, midpoint, rk4} (with
+    or a user knot grid) or a SmoothLinearInterpolation (fixed-step methods fused; dopri5 on the unfused solver), ``func`` any ``nn.Module (t, z) -> [..., H, C]``, ``method`` in {euler, midpoint, rk4} (with
     ``options={'step_size': h}``) or dopri5, CUDA tensors, ``t`` any monotone times.
     The FUSED kernels run when ``func`` exposes ``fused_spec()`` (the package's vector fields), tensors are fp32, ``t``
     increases and nothing upstream of the control path needs a gradient: the reference's NeuralCDE setting -- default grid,
@@ -671,8 +678,8 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
         raise NotImplementedError("method '%s': the fixed-step solvers %s and adaptive dopri5 are implemented" % (method, _FIXED_METHODS))
     if adjoint_method is not None and adjoint_method != method:
         raise NotImplementedError("adjoint_method != method is not implemented")
-    if not isinstance(X, (LinearInterpolation, NaturalCubicSpline)):
-        raise NotImplementedError("X must be ncde_amd.LinearInterpolation or ncde_amd.NaturalCubicSpline")
+    if not isinstance(X, (LinearInterpolation, NaturalCubicSpline, SmoothLinearInterpolation)):
+        raise NotImplementedError("X must be ncde_amd.LinearInterpolation, ncde_amd.NaturalCubicSpline or ncde_amd.SmoothLinearInterpolation")
 
     z0_in = z0      # (z0 is flattened further down; the unfused solver takes it as given)
 

@@ -26,6 +26,9 @@ def warn_once(reason):
                       "fused_spec(), fp32 CUDA tensors, increasing output times and a detached control path" % reason, UserWarning)
 
 
+last_dopri5_stats = None      # (forward, backward) step statistics of the latest unfused dopri5 solve, see cdeint_unfused
+
+
 class ControlledField:
     """g(t, z) = f(t, z) dX/dt(t)  (matmul), or f(t, [z, X(t)]) / f(t, [z, dX/dt(t)])  -- solver.py:112-137."""
 
@@ -354,6 +357,12 @@ def cdeint_unfused(X, func, z0, t, adjoint, mode, method, step_size, adjoint_par
                 params.append(p)
     if method == "dopri5":
         stats, stats_b = {}, {}
+        # {nfe, accepted, rejected} of the forward solve / of the adjoint's reverse solves (filled as they run), where a caller can
+        # look at them: on `func` as with the fused solver's dopri5_trace, and on this module for a func that takes no attributes
+        global last_dopri5_stats
+        last_dopri5_stats = (stats, stats_b)
+        if isinstance(func, torch.nn.Module):
+            func.dopri5_stats, func.dopri5_stats_backward = stats, stats_b
         if adjoint:
             cfg = dict(adaptive, field=field, stats=stats, stats_backward=stats_b)
             y = _AdjointDopri5.apply(cfg, z0, t, *params)
