@@ -341,6 +341,13 @@ int ncde_prepare_cubic(const float* x, int B, int L, int C, float* out, void* wo
  * preparation, whose output the caller pairs with a grid of 2L-1 times).  Cubic: non-uniform natural spline. */
 int ncde_prepare_linear_grid(const float* x, const float* t, int B, int L, int C, int rectilinear_time_index, float* out, void* stream);
 int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* Which kernel a builder call with these arguments launches (host-side query, no GPU work; the launch reads the same decision):
+ * kind = NCDE_INTERP_LINEAR -> "ncde_linear_coeffs_lds" (one workgroup per sample, the series staged in LDS) or "ncde_linear_coeffs"
+ * (one thread per series on global memory);  NCDE_INTERP_CUBIC -> "ncde_cubic_coeffs_lds<nsmp=N>" (N samples per workgroup in LDS;
+ * a workgroup that meets a NaN runs the per-series routine) or "ncde_cubic_coeffs" (one thread per series on global memory).
+ * has_grid != 0: a user time grid is passed.  rectilinear_time_index: as for ncde_prepare_linear (ignored for the spline).
+ * NULL for arguments the builders refuse.  The string lives in thread-local storage until the next call. */
+const char* ncde_prepare_kernel_name(int kind, int B, int L, int C, int has_grid, int rectilinear_time_index);
 
 
 /* Smoothed-linear control paths (SmoothLinearInterpolation, src/ncde/interpolation.py:6-123: cubic / quintic matching of the

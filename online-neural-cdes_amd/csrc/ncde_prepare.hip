@@ -10,6 +10,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
 
 #include "ncde_hip.h"
 #include "ncde_host.h"
@@ -287,6 +289,22 @@ __device__ void cubic_series_missing(const float* xs, float* os, float* wb, floa
         wd[p * sC] = nd;
         wb[p * sC] = nb;
         pp = p; p = q; xp = xq; r_prev = r; scaled_prev = scaled; nd_prev = nd; nb_prev = nb;
+    }
+    if (pp == 0) {      // exactly one interval swept (pp is the left knot of the last one; a second interval makes it > 0)
+        // two knots only (the filled ends; nothing observed in between): the reference's length-2 branch (interpolation_cubic.py:16-20),
+        // the straight line b = dx / dt with 2c = 3d = 0 EXACTLY -- the three-point sweep below on two knots gives the same line up to
+        // rounding only (b off by an ulp, 2c / 3d a residue).  Re-expanded around every grid point like any other piece.
+        const float td = tg ? tg[L - 1] - tg[0] : (float)(L - 1) - 0.0f;
+        const float x0 = val(0), b_k = (val(L - 1) - x0) / td;
+        for (int time = 0; time < L - 1; ++time) {
+            const float off = tg ? tg[0] - tg[time] : 0.0f - (float)time;
+            float* o = os + (long long)time * 4 * C;
+            o[0] = x0 + (0.0f - b_k) * off;
+            o[C] = b_k;
+            o[2 * C] = 0.0f;
+            o[3 * C] = 0.0f;
+        }
+        return;
     }
     // last knot (index L-1): diag = (0 + r_prev) * 2, rhs = 0 + scaled_prev
     float kd_next;
@@ -696,18 +714,77 @@ int64_t ncde_prepare_workspace_bytes(int kind, int B, int L, int C) {
     return 256;
 }
 
+// ---- launch plans: which kernel a builder call runs, with how much LDS -- decided in ONE place, read by the launch and by the
+// ncde_prepare_kernel_name query alike (so a test that means to reach a kernel can assert that it does)
+enum PrepareKernel { PREP_LINEAR_LDS, PREP_LINEAR_GLOBAL, PREP_CUBIC_LDS, PREP_CUBIC_GLOBAL };
+struct PreparePlan {
+    PrepareKernel kernel;
+    size_t lds;             // dynamic LDS bytes (0: none)
+    int nsmp, sstride;      // PREP_CUBIC_LDS: samples per workgroup, LDS stride of one sample in floats
+};
+
+static bool prepare_plan(int kind, int B, int L, int C, bool has_grid, int rectilinear_time_index, PreparePlan* p) {
+    if (B < 1 || L < 2 || C < 1) return false;
+    p->lds = 0; p->nsmp = 0; p->sstride = 0;
+    if (kind == NCDE_INTERP_LINEAR) {
+        if (rectilinear_time_index >= C) return false;
+        const bool rect = rectilinear_time_index >= 0;
+        const size_t lds = sizeof(float) * ((size_t)L * C * (rect ? 2 : 3) + 64 * (size_t)C);
+        if (lds <= 64 * 1024 && C <= 256) {   // the series fits LDS: staged, coalesced, scan-parallel variant
+            p->kernel = PREP_LINEAR_LDS;
+            p->lds = lds;
+        } else {
+            p->kernel = PREP_LINEAR_GLOBAL;
+        }
+        return true;
+    }
+    if (kind != NCDE_INTERP_CUBIC) return false;
+    p->kernel = PREP_CUBIC_GLOBAL;
+    // LDS-staged variant: NSMP whole samples per wave (lane <-> (sample, channel)), as many as fit 64 lanes and the LDS budget
+    if (C <= 64 && !has_grid) {      // (constant-coefficient system: the default grid only)
+        const int LC = L * C;
+        int sstride = LC + ((C - (LC % 32)) % 32 + 32) % 32;      // stride == C (mod 32): the lanes of one time step fall on distinct banks
+        sstride = (sstride + 3) & ~3;
+        int nsmp = 64 / C;
+        auto lds_of = [&](int ns) { return sizeof(float) * ((size_t)2 * ns * sstride + 2 * ((L + 3) & ~3)); };
+        // the recurrences are latency chains: prefer several resident workgroups per CU (<= 28 KB each: measured best at cfg4 size) over full waves
+        const char* ev = ncde_dev_env("NCDE_CUBIC_LDS_KB");
+        const size_t budget = (size_t)(ev && atoi(ev) > 0 ? atoi(ev) : 28) * 1024;
+        while (nsmp > 1 && lds_of(nsmp) > budget) --nsmp;
+        if (lds_of(nsmp) <= (size_t)150 * 1024) {
+            p->kernel = PREP_CUBIC_LDS;
+            p->lds = lds_of(nsmp);
+            p->nsmp = nsmp;
+            p->sstride = sstride;
+        }
+    }
+    return true;
+}
+
+const char* ncde_prepare_kernel_name(int kind, int B, int L, int C, int has_grid, int rectilinear_time_index) {
+    PreparePlan p;
+    // the rectilinear preparation leaves no gap the grid could enter: the grid plays no part in the choice for the linear builder
+    if (!prepare_plan(kind, B, L, C, has_grid != 0, rectilinear_time_index, &p)) return nullptr;
+    static thread_local char name[64];
+    switch (p.kernel) {
+        case PREP_LINEAR_LDS: return "ncde_linear_coeffs_lds";
+        case PREP_LINEAR_GLOBAL: return "ncde_linear_coeffs";
+        case PREP_CUBIC_GLOBAL: return "ncde_cubic_coeffs";
+        case PREP_CUBIC_LDS: snprintf(name, sizeof(name), "ncde_cubic_coeffs_lds<nsmp=%d>", p.nsmp); return name;
+    }
+    return nullptr;
+}
+
 int ncde_prepare_linear_grid(const float* x, const float* t, int B, int L, int C, int rectilinear_time_index, float* out, void* stream) {
-    if (!x || !out || B < 1 || L < 2 || C < 1 || rectilinear_time_index >= C) return NCDE_ERR_INVALID;
+    PreparePlan p;
+    if (!x || !out || !prepare_plan(NCDE_INTERP_LINEAR, B, L, C, t != nullptr, rectilinear_time_index, &p)) return NCDE_ERR_INVALID;
     const float* tg = rectilinear_time_index < 0 ? t : nullptr;      // the rectilinear preparation leaves no gap the grid could enter
     const long long n = (long long)B * C;
     const int rect = rectilinear_time_index < 0 ? -1 : rectilinear_time_index;
-    const int T = rect >= 0 ? 2 * L - 1 : L;
-    (void)T;
-    const size_t lds = sizeof(float) * ((size_t)L * C * (rect >= 0 ? 2 : 3) + 64 * (size_t)C);
-    if (lds <= 64 * 1024 && C <= 256) {   // the series fits LDS: staged, coalesced, scan-parallel variant
-        if (ncde_lds_optin((const void*)ncde_linear_coeffs_lds_kernel, lds) != hipSuccess)
+    if (p.kernel == PREP_LINEAR_LDS) {
+        if (ncde_lds_optin((const void*)ncde_linear_coeffs_lds_kernel, p.lds) != hipSuccess)
             return NCDE_ERR_HIP;
-        hipLaunchKernelGGL(ncde_linear_coeffs_lds_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, x, B, L, C, rect, out, tg);
+        hipLaunchKernelGGL(ncde_linear_coeffs_lds_kernel, dim3(B), dim3(256), p.lds, (hipStream_t)stream, x, B, L, C, rect, out, tg);
     } else {
         hipLaunchKernelGGL(ncde_linear_coeffs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, B, L, C, rect, out, tg);
     }
@@ -719,32 +796,20 @@ int ncde_prepare_linear(const float* x, int B, int L, int C, int rectilinear_tim
 }
 
 int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !out || !workspace || B < 1 || L < 2 || C < 1) return NCDE_ERR_INVALID;
+    PreparePlan p;
+    if (!x || !out || !workspace || !prepare_plan(NCDE_INTERP_CUBIC, B, L, C, t != nullptr, -1, &p)) return NCDE_ERR_INVALID;
     if ((int64_t)workspace_bytes < ncde_prepare_workspace_bytes(NCDE_INTERP_CUBIC, B, L, C)) return NCDE_ERR_WORKSPACE;
     float* ws = (float*)workspace;
     float* ws_d = ws + (size_t)B * L * C;
     float* diag = ws_d + (size_t)B * L * C;
     hipLaunchKernelGGL(ncde_cubic_diag_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, L, diag);
     const long long n = (long long)B * C;
-    // LDS-staged variant: NSMP whole samples per wave (lane <-> (sample, channel)), as many as fit 64 lanes and the LDS budget
-    if (C <= 64 && !t) {      // (constant-coefficient system: the default grid only)
-        const int LC = L * C;
-        int sstride = LC + ((C - (LC % 32)) % 32 + 32) % 32;      // stride == C (mod 32): the lanes of one time step fall on distinct banks
-        sstride = (sstride + 3) & ~3;
-        int nsmp = 64 / C;
-        auto lds_of = [&](int ns) { return sizeof(float) * ((size_t)2 * ns * sstride + 2 * ((L + 3) & ~3)); };
-        // the recurrences are latency chains: prefer several resident workgroups per CU (<= 28 KB each: measured best at cfg4 size) over full waves
-        const char* ev = ncde_dev_env("NCDE_CUBIC_LDS_KB");
-        const size_t budget = (size_t)(ev && atoi(ev) > 0 ? atoi(ev) : 28) * 1024;
-        while (nsmp > 1 && lds_of(nsmp) > budget) --nsmp;
-        if (lds_of(nsmp) <= (size_t)150 * 1024) {
-            const size_t lds = lds_of(nsmp);
-            if (ncde_lds_optin((const void*)ncde_cubic_coeffs_lds_kernel, lds) != hipSuccess)
-                return NCDE_ERR_HIP;
-            hipLaunchKernelGGL(ncde_cubic_coeffs_lds_kernel, dim3((unsigned)((B + nsmp - 1) / nsmp)), dim3(CUBIC_NT), lds, (hipStream_t)stream, x, B, L, C,
-                               nsmp, sstride, out, ws, diag, ws_d);
-            return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
-        }
+    if (p.kernel == PREP_CUBIC_LDS) {
+        if (ncde_lds_optin((const void*)ncde_cubic_coeffs_lds_kernel, p.lds) != hipSuccess)
+            return NCDE_ERR_HIP;
+        hipLaunchKernelGGL(ncde_cubic_coeffs_lds_kernel, dim3((unsigned)((B + p.nsmp - 1) / p.nsmp)), dim3(CUBIC_NT), p.lds, (hipStream_t)stream, x, B, L, C,
+                           p.nsmp, p.sstride, out, ws, diag, ws_d);
+        return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
     }
     hipLaunchKernelGGL(ncde_cubic_coeffs_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream, x, B, L, C, out,
                        ws, diag, ws_d, t);

@@ -4,9 +4,10 @@ builders, the step right before the hot path.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.  It is the checker for the
 GPU builders of csrc/ncde_prepare.hip (bit-exact comparison) and builds host-side inputs for the solve oracle.
 
-PARITY PIN: ``oracle/gen_golden.py`` compares every function here with the imported reference (golden g8:
-rectilinear and the spline bit-exact, with and without missing values; NaN linear fill <= 1e-6) and
-tests/test_host_cpu.py re-checks against the committed fixtures on every run.
+PARITY PIN: ``oracle/gen_golden.py`` compares every function here with the imported reference on the default grid (golden g8:
+rectilinear and the spline bit-exact, with and without missing values) and ``oracle/gen_golden_prepare.py`` asserts all of them,
+the NaN linear fill and the ``t=`` forms (user time grid) included, bit-exact on its own inputs; tests/test_host_cpu.py and
+tests/test_prepare_cpu.py re-check against the committed fixtures (g8, g8_coeffs_user_grid: bit-exact) on every run.
 
 Reference lines restated (relative to /root/reference/modules/torchcde/torchcde):
   * rectilinear prep      interpolation_linear.py:85-128
@@ -49,11 +50,13 @@ def rectilinear_prep(x, time_index):
     return np.ascontiguousarray(rep[..., :-1, :])
 
 
-def linear_interpolation_coeffs(x, rectilinear=None):
-    """Host-side mirror of torchcde.linear_interpolation_coeffs on the default integer time grid
-    (interpolation_linear.py:131-180): optional rectilinear preparation (``rectilinear`` = index of the
-    time channel), then every remaining NaN is filled by linear interpolation between its observed
-    neighbours, with the first/last observation extended to the ends; all-NaN channels become zero."""
+def linear_interpolation_coeffs(x, t=None, rectilinear=None):
+    """Host-side mirror of torchcde.linear_interpolation_coeffs (interpolation_linear.py:13-82, 131-180): optional rectilinear
+    preparation (``rectilinear`` = index of the time channel), then every remaining NaN is filled by linear interpolation
+    between its observed neighbours on the grid ``t`` (default: the integer grid), with the first/last observation extended
+    to the ends; all-NaN channels become zero.  fp32 in the reference's operation order (interpolation_linear.py:63-69):
+    ``ratio = (t_k - t_prev) / (t_next - t_prev)``, ``x_k = x_prev + ratio * (x_next - x_prev)``."""
+    f32 = np.float32
     x = np.array(x, dtype=np.float32, copy=True)
     if rectilinear is not None:
         assert isinstance(rectilinear, int) and 0 <= rectilinear < x.shape[-1], "bad time channel index"
@@ -61,27 +64,33 @@ def linear_interpolation_coeffs(x, rectilinear=None):
         x = rectilinear_prep(x, rectilinear)
     if not np.isnan(x).any():
         return x
-    flat = x.reshape(-1, x.shape[-2], x.shape[-1])
-    grid = np.arange(x.shape[-2], dtype=np.float64)
-    for b in range(flat.shape[0]):
-        for c in range(flat.shape[2]):
-            col = flat[b, :, c]
-            bad = np.isnan(col)
-            if not bad.any():
-                continue
-            if bad.all():
-                col[:] = 0.0
-            else:
-                col[bad] = np.interp(grid[bad], grid[~bad], col[~bad].astype(np.float64)).astype(np.float32)
+    L = x.shape[-2]
+    flat = x.reshape(-1, L, x.shape[-1])
+    grid = np.arange(L, dtype=f32) if t is None else np.asarray(t, dtype=f32)
+    assert grid.shape == (L,), "the time dimension of x must equal the length of t"
+    for b, c in zip(*np.nonzero(np.isnan(flat).any(axis=1))):
+        col = flat[b, :, c]
+        obs = np.nonzero(~np.isnan(col))[0]
+        if obs.size == 0:
+            col[:] = 0.0
+            continue
+        col[:obs[0]] = col[obs[0]]
+        col[obs[-1] + 1:] = col[obs[-1]]
+        for p, q in zip(obs[:-1], obs[1:]):
+            if q > p + 1:
+                k = np.arange(p + 1, q)
+                ratio = ((grid[k] - grid[p]) / f32(grid[q] - grid[p])).astype(f32)
+                col[k] = col[p] + (ratio * f32(col[q] - col[p])).astype(f32)
     return x
 
 
-def _natural_cubic_series_missing(x):
-    """One scalar series x[L] with NaNs = missing -> (a, b, 2c, 3d)[L-1] on every unit interval, following
-    interpolation_cubic.py:77-165 (``natural_cubic_coeffs``: ends filled from the first/last observation, spline on
-    the observed knots, then re-expanded around the left end of every unit interval)."""
+def _natural_cubic_series_missing(x, t=None):
+    """One scalar series x[L] with NaNs = missing -> (a, b, 2c, 3d)[L-1] on every interval of the grid t[L] (default: the
+    integer grid), following interpolation_cubic.py:77-165 (``natural_cubic_coeffs``: ends filled from the first/last
+    observation, spline on the observed knots, then re-expanded around the left end of every interval)."""
     f32 = np.float32
     L = x.shape[0]
+    t = np.arange(L, dtype=f32) if t is None else np.asarray(t, dtype=f32)
     obs = np.where(~np.isnan(x))[0]
     if obs.size == 0:
         z = np.zeros(L - 1, dtype=f32)
@@ -90,7 +99,7 @@ def _natural_cubic_series_missing(x):
     x[:obs[0]] = x[obs[0]]
     x[obs[-1] + 1:] = x[obs[-1]]
     kn = np.where(~np.isnan(x))[0]
-    tk = kn.astype(f32)
+    tk = t[kn]
     xk = x[kn]
     m = kn.size
     if m == 2:
@@ -137,7 +146,7 @@ def _natural_cubic_series_missing(x):
     for time in range(L - 1):
         while k + 1 < m - 1 and kn[k + 1] <= time:
             k += 1
-        off = f32(tk[k] - f32(time))
+        off = f32(tk[k] - t[time])
         a_in = f32(f32(f32(f32(0.5) * c_k[k]) - f32(f32(d_k[k] * off) / f32(3))) * off)
         a[time] = f32(a_k[k] + f32(f32(a_in - b_k[k]) * off))
         b[time] = f32(b_k[k] + f32(f32(f32(d_k[k] * off) - c_k[k]) * off))
@@ -146,13 +155,17 @@ def _natural_cubic_series_missing(x):
     return a, b, c2, d3
 
 
-def natural_cubic_coeffs(x):
-    """Natural cubic spline through x[..., L, C] on the integer grid t = 0..L-1; NaNs are missing values.
+def natural_cubic_coeffs(x, t=None):
+    """Natural cubic spline through x[..., L, C] on the grid t[L] (default: the integer grid t = 0..L-1); NaNs are missing values.
 
     Returns [..., L-1, 4C] = a || b || 2c || 3d per piece, the layout NaturalCubicSpline consumes
     (interpolation_cubic.py:189, 294-298).  fp32 arithmetic in the reference's operation order.
     """
     x = np.asarray(x, dtype=np.float32)
+    f32 = np.float32
+    if t is not None:
+        t = np.asarray(t, dtype=f32)
+        assert t.shape == (x.shape[-2],), "the time dimension of x must equal the length of t"
     if np.isnan(x).any():
         lead = x.shape[:-2]
         L, C = x.shape[-2:]
@@ -161,19 +174,23 @@ def natural_cubic_coeffs(x):
         with np.errstate(all="ignore"):
             for i in range(flat.shape[0]):
                 for c in range(C):
-                    a, b, c2, d3 = _natural_cubic_series_missing(flat[i, :, c])
+                    a, b, c2, d3 = _natural_cubic_series_missing(flat[i, :, c], t)
                     out[i, :, c], out[i, :, C + c], out[i, :, 2 * C + c], out[i, :, 3 * C + c] = a, b, c2, d3
         return out.reshape(*lead, L - 1, 4 * C)
     xt = np.swapaxes(x, -1, -2)  # [..., C, L]
     length = xt.shape[-1]
-    f32 = np.float32
     if length == 2:
         a = xt[..., :1]
         b = xt[..., 1:] - xt[..., :1]
+        if t is not None:
+            b = b / (t[1:] - t[:1])
         two_c = np.zeros_like(a)
         three_d = np.zeros_like(a)
     else:
-        recip = np.ones(length - 1, dtype=f32)  # 1/(t[i+1]-t[i]) on the integer grid
+        if t is None:
+            recip = np.ones(length - 1, dtype=f32)  # 1/(t[i+1]-t[i]) on the integer grid
+        else:
+            recip = (f32(1) / (t[1:] - t[:-1])).astype(f32)
         recip_sq = recip * recip
         three_diff = f32(3) * (xt[..., 1:] - xt[..., :-1])
         six_diff = f32(2) * three_diff
