@@ -88,10 +88,6 @@ int validate(const NcdeProblem* p) {
     return NCDE_OK;
 }
 
-// A piecewise-quintic control never runs on a register-resident kernel set (their dX/dt staging knows the linear and cubic rows only):
-// batch-tiled (zero-padded as for any shape), then generic / variant.
-bool fast_supported(const NcdeProblem* p, int pass) { return p->interp != NCDE_INTERP_QUINTIC && ncde_fast_supported(p, pass); }
-
 int generic_supported(const NcdeProblem* p, const Layout& y, int pass) {
     if (pass == 0 && y.lds_fwd > (size_t)kLdsLimit)
         return fail(NCDE_ERR_UNSUPPORTED, "generic forward needs %zu B of LDS (> %d)", y.lds_fwd, kLdsLimit);
@@ -140,9 +136,27 @@ inline int pad_width(int w, int pass) {
     return w <= 16 ? 16 : (w <= 32 ? 32 : (w <= 64 ? 64 : (w <= 128 ? 128 : ((pass != 0 && w <= 256) ? 256 : hru16(w)))));
 }
 
+// Where padding may take a problem: the register-resident kernel sets in order of preference (the smallest channel set that holds the
+// problem first; original field, ONE shared inner layer as the reference's fields have), then -- a null target -- the batch-tiled
+// family (original / minimal-gated field, matmul input).  Measured at B = 4096, T = 99 (profiles/r04_shape_sweep_perf.txt): the
+// specialised kernels at their full padded size take no longer than the SMALLEST batch-tiled shapes (forward 0.6 - 0.9 ms vs 0.7 ms,
+// adjoint 1.8 - 2.0 ms vs 2.1 ms at (4, 32, 16)), so a shape they can hold is always sent there.
+struct PadTarget {
+    int H, HH, C;
+    bool passes[3];      // forward, continuous adjoint, exact discrete backward
+    bool time_plan;      // also on a general time axis
+};
+const PadTarget kPadTargets[] = {
+    {32, 32, 4, {true, true, true}, false},  {32, 32, 8, {true, true, true}, false}, {32, 32, 12, {true, true, true}, false},      // round 6: few channels
+    {32, 32, 20, {true, true, true}, true},  {64, 64, 4, {true, true, true}, true},
+    {32, 32, 40, {true, false, false}, false},      // round 5: a forward-only kernel set
+};
+
+enum class Family { Generic, Fast, Tiled, Variant, Padded };
+
 struct PadPlan {
     bool ok;
-    int inner;                           // family the padded problem runs on: 2 = batch-tiled, 1 = shape-specialised (register-resident)
+    Family inner;                        // family the padded problem runs on: Tiled or Fast
     NcdeProblem q;                       // the padded problem; its parameter pointers are OFFSETS (floats, +1) until bound to a workspace
     int n_seg;
     int dims[12][6];
@@ -152,37 +166,28 @@ struct PadPlan {
     long long param_floats;              // padded parameters (and, for the backward, the same again for their gradients)
 };
 
-// Would padding bring `p` into the batch-tiled family (target 0: original / minimal-gated field, matmul input), or onto one of the
-// shape-specialised kernel sets (target 1: (H, HH, C) = (32, 32, 20), target 2: (64, 64, 4), target 3: (32, 32, 40) forward only; original field, default time axis, ONE
-// shared inner layer as the reference's fields have)?  Measured at B = 4096, T = 99 (profiles/r04_shape_sweep_perf.txt): the
-// specialised kernels at their full padded size take no longer than the SMALLEST batch-tiled shapes (forward 0.6 - 0.9 ms vs 0.7 ms,
-// adjoint 1.8 - 2.0 ms vs 2.1 ms at (4, 32, 16)), so a shape they can hold is always sent there.
-PadPlan make_pad_plan(const NcdeProblem* p, int pass, int target = 0) {
+PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
     PadPlan P{};
     P.ok = false;
-    P.inner = target == 0 ? 2 : 1;
+    P.inner = t ? Family::Fast : Family::Tiled;
     if (p->n_layers < 1 || p->field_input != NCDE_INPUT_MATMUL || p->field_kind == NCDE_FIELD_GRU) return P;
     if (p->hidden > 2048 || p->channels > 4095) return P;
-    // (target 3, round 5: (32, 32, 40) -- a forward-only kernel set: pass 0 on the default time axis; targets 4 - 6, round 6: (32, 32, 4 / 8 /
-    // 12) -- few channels, every pass, default time axis)
-    const int tH = target == 2 ? 64 : 32, tHH = tH, tC = target == 1 ? 20 : (target == 2 ? 4 : (target == 3 ? 40 : 4 * (target - 3)));
-    if (target == 3 && (pass != 0 || p->output == NCDE_OUT_TIMES)) return P;
-    if (target >= 4 && p->output == NCDE_OUT_TIMES) return P;
-    if (target != 0) {
-        if (p->field_kind != NCDE_FIELD_ORIGINAL || p->hidden > tH || p->channels > tC) return P;
+    if (t) {
+        if (pass < 0 || pass > 2 || !t->passes[pass] || (p->output == NCDE_OUT_TIMES && !t->time_plan)) return P;
+        if (p->field_kind != NCDE_FIELD_ORIGINAL || p->hidden > t->H || p->channels > t->C) return P;
         // (any batch-tiled knob is a request for that family; the non-default adjoint variants exist for the exact shapes only)
         if (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | NCDE_FLAG_FORCE_TILED |
-                        NCDE_FLAG_TILED_NS1 | NCDE_FLAG_TILED_NS2 | NCDE_FLAG_TILED_NS4 | 0x00FF0000u | 0x200u)) return P;
+                        NCDE_FLAG_TILED_NS1 | NCDE_FLAG_TILED_NS2 | NCDE_FLAG_TILED_NS4 | NCDE_FLAG_TILED_WINDOW_STEPS(0xFF) | kFlagChainDump)) return P;
         for (int l = 0; l < p->n_layers; ++l) {
-            if (p->layer_out[l] > tHH) return P;
+            if (p->layer_out[l] > t->HH) return P;
             if (l >= 1 && (p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1])) return P;
         }
         if (p->n_layers > 1 && (p->layer_W[1] == p->layer_W[0] || p->layer_b[1] == p->layer_b[0])) return P;
     }
     NcdeProblem& q = P.q;
     q = *p;
-    q.hidden = target == 0 ? hru16(p->hidden) : tH;
-    q.channels = target == 0 ? hru4(p->channels) : tC;
+    q.hidden = t ? t->H : hru16(p->hidden);
+    q.channels = t ? t->C : hru4(p->channels);
     q.reserved_ = (p->hidden << 12) | p->channels;
     int n = 0;
     long long off = 0;
@@ -198,7 +203,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, int target = 0) {
     };
     int din = q.hidden;
     for (int l = 0; l < p->n_layers; ++l) {
-        const int dout = target == 0 ? pad_width(p->layer_out[l], pass) : tHH;
+        const int dout = t ? t->HH : pad_width(p->layer_out[l], pass);
         q.layer_in[l] = din; q.layer_out[l] = dout;
         P.slot_W[l] = add(p->layer_W[l], 1, p->layer_out[l], p->layer_in[l], 1, dout, din);
         P.slot_b[l] = add(p->layer_b[l], 1, 1, p->layer_out[l], 1, 1, dout);
@@ -221,16 +226,16 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, int target = 0) {
     for (int l = 0; l < p->n_layers; ++l) { q.layer_W[l] = fake(P.slot_W[l]); q.layer_b[l] = fake(P.slot_b[l]); }
     q.Wo = fake(P.slot_Wo); q.bo = fake(P.slot_bo);
     if (p->field_kind == NCDE_FIELD_MINIMAL) { q.Wg = fake(P.slot_Wg); q.bg = fake(P.slot_bg); }
-    P.ok = target == 0 ? ncde_tiled_supported(&q, pass) : fast_supported(&q, pass);
+    P.ok = t ? ncde_fast_supported(&q, pass) : ncde_tiled_supported(&q, pass);
     return P;
 }
 // the padded plan a problem takes, if any: a shape-specialised kernel set first, then the batch-tiled family
 PadPlan pick_pad_plan(const NcdeProblem* p, int pass, bool allow_tiled) {
-    for (int target : {4, 5, 6, 1, 2, 3}) {      // (the smallest channel set that holds the problem first)
-        PadPlan P = make_pad_plan(p, pass, target);
+    for (const PadTarget& t : kPadTargets) {
+        PadPlan P = make_pad_plan(p, pass, &t);
         if (P.ok) return P;
     }
-    if (allow_tiled && !ncde_tiled_supported(p, pass)) return make_pad_plan(p, pass, 0);
+    if (allow_tiled && !ncde_tiled_supported(p, pass)) return make_pad_plan(p, pass, nullptr);
     PadPlan none{};
     return none;
 }
@@ -258,61 +263,72 @@ int pad_launch(const PadPlan& P, float* base, int dir, float* const* real_dst, h
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
-// pick the kernel family: 1 = fast (shape-specialised), 2 = tiled (batch-tiled, large hidden), 4 = tiled on the zero-padded problem,
-// 3 = variant, 0 = generic, <0 = error
-int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass);
-int select_family(const NcdeProblem* p, const Layout& y, int pass) {
-    const int fam = select_family_unpadded(p, y, pass);
-    if (p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) return fam;
+// The route of one C-ABI call: the kernel family of (problem, pass) and, for Family::Padded, the padded problem.  Computed ONCE per
+// call (begin_call); every query and launch below reads it.
+struct Route {
+    Family family;
+    PadPlan pad;
+};
+struct Call {
+    NcdeProblem q;      // the caller's problem, normalised
+    Layout y;
+    Route route;
+};
+
+// the family of the problem as it is (no padding): NCDE_OK and *fam, or an error
+int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass, Family* fam);
+int select_route(const NcdeProblem* p, const Layout& y, int pass, Route* r) {
+    const int rc = select_family_unpadded(p, y, pass, &r->family);
+    if (p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) return rc;
     // no specialised kernel of its own: a zero-padded run on a specialised kernel set (also instead of the batch-tiled family, which
     // the smallest shapes do not use well), else -- instead of the generic / variant kernels -- on the batch-tiled family
-    if (fam == 0 || fam == 2 || fam == 3 || fam == NCDE_ERR_UNSUPPORTED) {
-        const bool fallback = fam != 2;
-        if (pick_pad_plan(p, pass, fallback).ok) return 4;
+    if (rc == NCDE_ERR_UNSUPPORTED || (rc == NCDE_OK && r->family != Family::Fast)) {
+        r->pad = pick_pad_plan(p, pass, rc != NCDE_OK || r->family != Family::Tiled);
+        if (r->pad.ok) { r->family = Family::Padded; return NCDE_OK; }
     }
-    return fam;
+    return rc;
 }
-int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass) {
+int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass, Family* fam) {
+    auto take = [&](Family f) { *fam = f; return (int)NCDE_OK; };
+    auto generic = [&]() { *fam = Family::Generic; return generic_supported(p, y, pass); };
     if (p->output == NCDE_OUT_TIMES) {   // general time axis: the plan-driven kernels -- batch-tiled where the shape allows
                                          // (multiples of 16 / 4; 2.8x the generic family at cfg2 widths, 10x at cfg5's), else generic / variant
         // (round 4: the shape-specialised kernels walk the plan too -- forward of both shapes, continuous adjoint of (32, 32, 20) nl = 3
         // and of H = 64 / C <= 4; the planned discrete backward stays on the batch-tiled family)
-        const bool fast_ok = !y.variant && !(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_TILED)) && fast_supported(p, pass);
+        const bool fast_ok = !y.variant && !(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_TILED)) && ncde_fast_supported(p, pass);
         if (p->flags & NCDE_FLAG_FORCE_FAST) {
             if (!fast_ok) return fail(NCDE_ERR_UNSUPPORTED, "no shape-specialised kernel for this problem on a general time axis (pass %d)", pass);
-            return 1;
+            return take(Family::Fast);
         }
-        if (fast_ok) return 1;
+        if (fast_ok) return take(Family::Fast);
         const bool tiled_ok = !(p->flags & NCDE_FLAG_FORCE_GENERIC) && ncde_tiled_supported(p, pass);
         if (p->flags & NCDE_FLAG_FORCE_TILED) {
             if (!tiled_ok) return fail(NCDE_ERR_UNSUPPORTED, "the batch-tiled family does not cover this problem (pass %d)", pass);
-            return 2;
+            return take(Family::Tiled);
         }
-        if (tiled_ok) return 2;
+        if (tiled_ok) return take(Family::Tiled);
         if (y.variant) {
             if (!ncde_variant_supported(p, pass)) return fail(NCDE_ERR_UNSUPPORTED, "vector-field variant outside what ncde_variant.hip covers (pass %d)", pass);
-            return 3;
+            return take(Family::Variant);
         }
-        const int rc = generic_supported(p, y, pass);
-        return rc == NCDE_OK ? 0 : rc;
+        return generic();
     }
     if (y.variant) {   // gated fields / evaluate / derivative inputs: the batch-tiled family knows the minimal-gated field;
                        // everything else runs on their own kernels on the generic structure
-        if (!(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) && ncde_tiled_supported(p, pass)) return 2;
+        if (!(p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) && ncde_tiled_supported(p, pass)) return take(Family::Tiled);
         if ((p->flags & NCDE_FLAG_FORCE_FAST) || !ncde_variant_supported(p, pass))
             return fail(NCDE_ERR_UNSUPPORTED, "vector-field variant outside what ncde_variant.hip covers (pass %d)", pass);
-        return 3;
+        return take(Family::Variant);
     }
-    if ((p->flags & NCDE_FLAG_FORCE_TILED) && ncde_tiled_supported(p, pass)) return 2;   // also ahead of a specialised kernel
-    const bool fast_ok = fast_supported(p, pass);
+    if ((p->flags & NCDE_FLAG_FORCE_TILED) && ncde_tiled_supported(p, pass)) return take(Family::Tiled);   // also ahead of a specialised kernel
+    const bool fast_ok = ncde_fast_supported(p, pass);
     if (p->flags & NCDE_FLAG_FORCE_FAST) {
         if (!fast_ok) return fail(NCDE_ERR_UNSUPPORTED, "no shape-specialised kernel for this problem (pass %d)", pass);
-        return 1;
+        return take(Family::Fast);
     }
-    if (fast_ok && !(p->flags & NCDE_FLAG_FORCE_GENERIC)) return 1;
-    if (!(p->flags & NCDE_FLAG_FORCE_GENERIC) && ncde_tiled_supported(p, pass)) return 2;
-    const int rc = generic_supported(p, y, pass);
-    return rc == NCDE_OK ? 0 : rc;
+    if (fast_ok && !(p->flags & NCDE_FLAG_FORCE_GENERIC)) return take(Family::Fast);
+    if (!(p->flags & NCDE_FLAG_FORCE_GENERIC) && ncde_tiled_supported(p, pass)) return take(Family::Tiled);
+    return generic();
 }
 
 int launch_reduce(const NcdeProblem* p, const Layout& y, const NcdeGrads* g, const float* gpart, int n_part, hipStream_t st) {
@@ -322,35 +338,79 @@ int launch_reduce(const NcdeProblem* p, const Layout& y, const NcdeGrads* g, con
     return NCDE_OK;
 }
 
-int launch_forward(const NcdeProblem* p, const Layout& y, int family, float* out, float* stages, void* ws, size_t ws_bytes,
-                   hipStream_t st) {
-    if (family == 4) {
-        PadPlan P = pick_pad_plan(p, 0, true);
-        if (!P.ok) return fail(NCDE_ERR_UNSUPPORTED, "padded problem outside the aligned kernel families");
-        float* base = (float*)ws;
-        const long long head = pad_head_floats(P, 0);
-        pad_bind(P, p, base);
-        if (pad_launch(P, base, 0, nullptr, st) != NCDE_OK) return fail(NCDE_ERR_HIP, "parameter padding launch failed");
-        const size_t inner_bytes = ws_bytes - sizeof(float) * (size_t)head;
-        const int rc = P.inner == 1 ? ncde_fast_forward(&P.q, out, stages, base + head, inner_bytes, st)
-                                    : ncde_tiled_forward(&P.q, out, stages, base + head, inner_bytes, st);
-        if (rc != NCDE_OK) return fail(rc, "forward (zero-padded problem) launch failed");
-        return NCDE_OK;
+// ---- one dispatch per operation ------------------------------------------------------------------------------------------------
+int64_t route_workspace_bytes(const Call& c, int pass) {
+    const NcdeProblem* p = &c.q;
+    switch (c.route.family) {
+        case Family::Fast: return ncde_fast_workspace_bytes(p, pass);
+        case Family::Tiled: return ncde_tiled_workspace_bytes(p, pass);
+        case Family::Variant: return ncde_variant_workspace_bytes(p, pass);
+        case Family::Padded: {
+            const PadPlan& P = c.route.pad;
+            const int64_t inner = P.inner == Family::Fast ? ncde_fast_workspace_bytes(&P.q, pass) : ncde_tiled_workspace_bytes(&P.q, pass);
+            return inner < 0 ? inner : inner + (int64_t)sizeof(float) * pad_head_floats(P, pass);
+        }
+        case Family::Generic: break;
     }
-    if (family == 1) {
-        const int rc = ncde_fast_forward(p, out, stages, ws, ws_bytes, st);
-        if (rc != NCDE_OK) return fail(rc, "fast forward launch failed");
-        return NCDE_OK;
+    return pass == 0 ? 256 : (int64_t)sizeof(float) * (int64_t)c.y.n_wg * (int64_t)c.y.theta_size + 256;
+}
+
+const char* route_kernel_name(const Call& c, int pass) {
+    const NcdeProblem* p = &c.q;
+    switch (c.route.family) {
+        case Family::Fast: return ncde_fast_kernel_name(p, pass);
+        case Family::Tiled: return ncde_tiled_kernel_name(p, pass);
+        case Family::Variant: return pass == 0 ? "ncde_fwd_variant" : (pass == 1 ? "ncde_adj_variant" : "ncde_adj_variant<discrete>");
+        case Family::Padded:      // (on the zero-padded problem)
+            return c.route.pad.inner == Family::Fast ? ncde_fast_kernel_name(&c.route.pad.q, pass) : ncde_tiled_kernel_name(&c.route.pad.q, pass);
+        case Family::Generic: break;
     }
-    if (family == 3) {
-        const int rc = ncde_variant_forward(p, out, stages, st);
-        if (rc != NCDE_OK) return fail(rc, "variant forward launch failed");
-        return NCDE_OK;
-    }
-    if (family == 2) {
-        const int rc = ncde_tiled_forward(p, out, stages, ws, ws_bytes, st);
-        if (rc != NCDE_OK) return fail(rc, "tiled forward launch failed");
-        return NCDE_OK;
+    return pass == 0 ? "ncde_fwd_generic" : (pass == 1 ? "ncde_adj_generic" : "ncde_adj_generic<discrete>");
+}
+
+// byte offset of the cooperative launch sequence's status word, or < 0: only the batch-tiled family launches cooperative kernels
+int64_t route_status_offset(const Call& c, int pass) {
+    if (c.route.family == Family::Tiled) return ncde_tiled_status_offset(&c.q, pass);
+    if (c.route.family != Family::Padded || c.route.pad.inner != Family::Tiled) return -1;
+    const int64_t off = ncde_tiled_status_offset(&c.route.pad.q, pass);
+    return off < 0 ? off : off + (int64_t)sizeof(float) * pad_head_floats(c.route.pad, pass);
+}
+
+// the workspace the route needs against what the caller passed (`always`: the pass writes its workspace whatever the family)
+int check_workspace(const Call& c, int pass, const void* ws, size_t ws_bytes, bool always) {
+    const int64_t need = route_workspace_bytes(c, pass);
+    if ((always || need > 0) && (!ws || (int64_t)ws_bytes < need)) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", ws_bytes, (long long)need);
+    return NCDE_OK;
+}
+
+int launch_forward(Call& c, float* out, float* stages, void* ws, size_t ws_bytes, hipStream_t st) {
+    const NcdeProblem* p = &c.q;
+    const Layout& y = c.y;
+    switch (c.route.family) {
+        case Family::Padded: {
+            PadPlan& P = c.route.pad;
+            float* base = (float*)ws;
+            const long long head = pad_head_floats(P, 0);
+            pad_bind(P, p, base);
+            if (pad_launch(P, base, 0, nullptr, st) != NCDE_OK) return fail(NCDE_ERR_HIP, "parameter padding launch failed");
+            const size_t inner_bytes = ws_bytes - sizeof(float) * (size_t)head;
+            const int rc = P.inner == Family::Fast ? ncde_fast_launch(&P.q, 0, out, stages, nullptr, nullptr, nullptr, base + head, inner_bytes, st, false)
+                                                   : ncde_tiled_forward(&P.q, out, stages, base + head, inner_bytes, st);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "forward (zero-padded problem) launch failed");
+        }
+        case Family::Fast: {
+            const int rc = ncde_fast_launch(p, 0, out, stages, nullptr, nullptr, nullptr, ws, ws_bytes, st, false);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "fast forward launch failed");
+        }
+        case Family::Variant: {
+            const int rc = ncde_variant_forward(p, out, stages, st);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "variant forward launch failed");
+        }
+        case Family::Tiled: {
+            const int rc = ncde_tiled_forward(p, out, stages, ws, ws_bytes, st);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "tiled forward launch failed");
+        }
+        case Family::Generic: break;
     }
     KArgs a;
     fill_kargs(p, y, &a);
@@ -363,55 +423,57 @@ int launch_forward(const NcdeProblem* p, const Layout& y, int family, float* out
 }
 
 // discrete = false: continuous adjoint, `src` = z_out; discrete = true: exact backward, `src` = the stage record
-int launch_adjoint(const NcdeProblem* p, const Layout& y, int family, const float* src, const float* grad_out,
-                   const NcdeGrads* g, void* ws, size_t ws_bytes, hipStream_t st, bool main_kernel_only, bool discrete) {
-    if (family == 4) {
-        PadPlan P = pick_pad_plan(p, discrete ? 2 : 1, true);
-        if (!P.ok) return fail(NCDE_ERR_UNSUPPORTED, "padded problem outside the aligned kernel families");
-        float* base = (float*)ws;
-        const long long head = pad_head_floats(P, 1);
-        pad_bind(P, p, base);
-        if (pad_launch(P, base, 0, nullptr, st) != NCDE_OK) return fail(NCDE_ERR_HIP, "parameter padding launch failed");
-        float* gbase = base + P.param_floats;      // padded gradients, same layout as the padded parameters
-        NcdeGrads gq{};
-        gq.grad_z0 = g->grad_z0;                   // real row width: written in place
-        float* real_dst[12] = {nullptr};
-        for (int l = 0; l < p->n_layers; ++l) {
-            gq.grad_layer_W[l] = gbase + P.off[P.slot_W[l]]; gq.grad_layer_b[l] = gbase + P.off[P.slot_b[l]];
-            real_dst[P.slot_W[l]] = g->grad_layer_W[l]; real_dst[P.slot_b[l]] = g->grad_layer_b[l];
+int launch_adjoint(Call& c, const float* src, const float* grad_out, const NcdeGrads* g, void* ws, size_t ws_bytes, hipStream_t st,
+                   bool main_kernel_only, bool discrete) {
+    const NcdeProblem* p = &c.q;
+    const Layout& y = c.y;
+    const int pass = discrete ? 2 : 1;
+    const char* null_grad = "NcdeGrads: NULL destination for a parameter gradient";
+    switch (c.route.family) {
+        case Family::Padded: {
+            PadPlan& P = c.route.pad;
+            float* base = (float*)ws;
+            const long long head = pad_head_floats(P, 1);
+            pad_bind(P, p, base);
+            if (pad_launch(P, base, 0, nullptr, st) != NCDE_OK) return fail(NCDE_ERR_HIP, "parameter padding launch failed");
+            float* gbase = base + P.param_floats;      // padded gradients, same layout as the padded parameters
+            NcdeGrads gq{};
+            gq.grad_z0 = g->grad_z0;                   // real row width: written in place
+            float* real_dst[12] = {nullptr};
+            for (int l = 0; l < p->n_layers; ++l) {
+                gq.grad_layer_W[l] = gbase + P.off[P.slot_W[l]]; gq.grad_layer_b[l] = gbase + P.off[P.slot_b[l]];
+                real_dst[P.slot_W[l]] = g->grad_layer_W[l]; real_dst[P.slot_b[l]] = g->grad_layer_b[l];
+            }
+            gq.grad_Wo = gbase + P.off[P.slot_Wo]; gq.grad_bo = gbase + P.off[P.slot_bo];
+            real_dst[P.slot_Wo] = g->grad_Wo; real_dst[P.slot_bo] = g->grad_bo;
+            if (p->field_kind == NCDE_FIELD_MINIMAL) {
+                gq.grad_Wg = gbase + P.off[P.slot_Wg]; gq.grad_bg = gbase + P.off[P.slot_bg];
+                real_dst[P.slot_Wg] = g->grad_Wg; real_dst[P.slot_bg] = g->grad_bg;
+            }
+            const size_t inner_bytes = ws_bytes - sizeof(float) * (size_t)head;
+            const int rc = P.inner == Family::Fast ? ncde_fast_launch(&P.q, pass, nullptr, nullptr, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only)
+                                                   : ncde_tiled_adjoint(&P.q, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only, discrete);
+            if (rc != NCDE_OK) return fail(rc, "adjoint (zero-padded problem) launch failed");
+            if (main_kernel_only) return NCDE_OK;
+            const int rc2 = pad_launch(P, gbase, 1, real_dst, st);
+            if (rc2 == NCDE_ERR_INVALID) return fail(rc2, "%s", null_grad);
+            return rc2 == NCDE_OK ? NCDE_OK : fail(rc2, "gradient un-padding launch failed");
         }
-        gq.grad_Wo = gbase + P.off[P.slot_Wo]; gq.grad_bo = gbase + P.off[P.slot_bo];
-        real_dst[P.slot_Wo] = g->grad_Wo; real_dst[P.slot_bo] = g->grad_bo;
-        if (p->field_kind == NCDE_FIELD_MINIMAL) {
-            gq.grad_Wg = gbase + P.off[P.slot_Wg]; gq.grad_bg = gbase + P.off[P.slot_bg];
-            real_dst[P.slot_Wg] = g->grad_Wg; real_dst[P.slot_bg] = g->grad_bg;
+        case Family::Fast: {
+            const int rc = ncde_fast_launch(p, pass, nullptr, nullptr, src, grad_out, g, ws, ws_bytes, st, main_kernel_only);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "fast adjoint launch failed");
         }
-        const size_t inner_bytes = ws_bytes - sizeof(float) * (size_t)head;
-        const int rc = P.inner == 1 ? ncde_fast_adjoint(&P.q, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only, discrete)
-                                    : ncde_tiled_adjoint(&P.q, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only, discrete);
-        if (rc != NCDE_OK) return fail(rc, "adjoint (zero-padded problem) launch failed");
-        if (main_kernel_only) return NCDE_OK;
-        const int rc2 = pad_launch(P, gbase, 1, real_dst, st);
-        if (rc2 == NCDE_ERR_INVALID) return fail(rc2, "NcdeGrads: NULL destination for a parameter gradient");
-        if (rc2 != NCDE_OK) return fail(rc2, "gradient un-padding launch failed");
-        return NCDE_OK;
-    }
-    if (family == 1) {
-        const int rc = ncde_fast_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete);
-        if (rc != NCDE_OK) return fail(rc, "fast adjoint launch failed");
-        return NCDE_OK;
-    }
-    if (family == 3) {
-        const int rc = ncde_variant_adjoint(p, src, grad_out, g, ws, st, main_kernel_only, discrete);
-        if (rc == NCDE_ERR_INVALID) return fail(rc, "NcdeGrads: NULL destination for a parameter gradient");
-        if (rc != NCDE_OK) return fail(rc, "variant adjoint launch failed");
-        return NCDE_OK;
-    }
-    if (family == 2) {
-        const int rc = ncde_tiled_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete);
-        if (rc == NCDE_ERR_INVALID) return fail(rc, "NcdeGrads: NULL destination for a parameter gradient");
-        if (rc != NCDE_OK) return fail(rc, "tiled adjoint launch failed");
-        return NCDE_OK;
+        case Family::Variant: {
+            const int rc = ncde_variant_adjoint(p, src, grad_out, g, ws, st, main_kernel_only, discrete);
+            if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "variant adjoint launch failed");
+        }
+        case Family::Tiled: {
+            const int rc = ncde_tiled_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete);
+            if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "tiled adjoint launch failed");
+        }
+        case Family::Generic: break;
     }
     KArgs a;
     fill_kargs(p, y, &a);
@@ -425,6 +487,22 @@ int launch_adjoint(const NcdeProblem* p, const Layout& y, int family, const floa
     if (main_kernel_only) return NCDE_OK;
     return launch_reduce(p, y, g, (const float*)ws, y.n_wg, st);
 }
+
+// The front end of every C-ABI call that dispatches: normalise the caller's struct, validate it, check the call's own arguments
+// (`args_ok(problem)`: NCDE_OK or a fail(...)), lay out the parameter gradients, route.
+template <class ArgsOk>
+int begin_call(const NcdeProblem* in, int pass, Call* c, ArgsOk&& args_ok) {
+    int rc = normalize(in, &c->q);
+    if (rc != NCDE_OK) return rc;
+    rc = validate(&c->q);
+    if (rc != NCDE_OK) return rc;
+    rc = args_ok(c->q);
+    if (rc != NCDE_OK) return rc;
+    c->y = make_layout(&c->q);
+    return select_route(&c->q, c->y, pass, &c->route);
+}
+int no_args(const NcdeProblem&) { return NCDE_OK; }
+int pass_in_range(int pass) { return pass < 0 || pass > 2 ? fail(NCDE_ERR_INVALID, "pass %d outside {0, 1, 2}", pass) : (int)NCDE_OK; }
 
 }  // namespace
 
@@ -568,47 +646,16 @@ int ncde_time_plan_build(const NcdeProblem* p, const NcdeTimeSpec* ts, void* hos
 }
 
 int64_t ncde_workspace_bytes(const NcdeProblem* p, int pass) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
-    if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, pass);
-    if (fam < 0) return fam;
-    if (fam == 1) return ncde_fast_workspace_bytes(p, pass);
-    if (fam == 4) {
-        const PadPlan P = pick_pad_plan(p, pass, true);
-        const int64_t inner = P.inner == 1 ? ncde_fast_workspace_bytes(&P.q, pass) : ncde_tiled_workspace_bytes(&P.q, pass);
-        return inner < 0 ? inner : inner + (int64_t)sizeof(float) * pad_head_floats(P, pass);
-    }
-    if (fam == 2) return ncde_tiled_workspace_bytes(p, pass);
-    if (fam == 3) return ncde_variant_workspace_bytes(p, pass);
-    if (pass == 0) return 256;
-    return (int64_t)sizeof(float) * (int64_t)y.n_wg * (int64_t)y.theta_size + 256;
+    Call c;
+    const int rc = begin_call(p, pass, &c, no_args);
+    return rc != NCDE_OK ? rc : route_workspace_bytes(c, pass);
 }
 
 int64_t ncde_coop_status_offset(const NcdeProblem* p, int pass) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
+    Call c;
+    const int rc = begin_call(p, pass, &c, [&](const NcdeProblem&) { return pass_in_range(pass); });
     if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (pass < 0 || pass > 2) return fail(NCDE_ERR_INVALID, "pass %d outside {0, 1, 2}", pass);
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, pass);
-    if (fam < 0) return fam;
-    int64_t off = -1;
-    if (fam == 2) off = ncde_tiled_status_offset(p, pass);
-    else if (fam == 4) {
-        const PadPlan P = pick_pad_plan(p, pass, true);
-        if (P.inner == 2) {
-            off = ncde_tiled_status_offset(&P.q, pass);
-            if (off >= 0) off += (int64_t)sizeof(float) * pad_head_floats(P, pass);
-        }
-    }
+    const int64_t off = route_status_offset(c, pass);
     if (off < 0) return fail(NCDE_ERR_UNSUPPORTED, "this problem / pass launches no cooperative kernel");
     return off;
 }
@@ -626,102 +673,56 @@ int64_t ncde_stage_record_bytes(const NcdeProblem* p) {
 }
 
 const char* ncde_kernel_name(const NcdeProblem* p, int pass) {
-    NcdeProblem q_;
-    if (normalize(p, &q_) != NCDE_OK) return nullptr;
-    p = &q_;
-    if (validate(p) != NCDE_OK) return nullptr;
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, pass);
-    if (fam < 0) return nullptr;
-    if (fam == 4) {      // (on the zero-padded problem)
-        const PadPlan P = pick_pad_plan(p, pass, true);
-        return P.inner == 1 ? ncde_fast_kernel_name(&P.q, pass) : ncde_tiled_kernel_name(&P.q, pass);
-    }
-    if (fam == 2) return ncde_tiled_kernel_name(p, pass);
-    if (fam == 3) return pass == 0 ? "ncde_fwd_variant" : (pass == 1 ? "ncde_adj_variant" : "ncde_adj_variant<discrete>");
-    return fam == 1 ? ncde_fast_kernel_name(p, pass) : (pass == 0 ? "ncde_fwd_generic" : (pass == 1 ? "ncde_adj_generic" : "ncde_adj_generic<discrete>"));
+    Call c;
+    return begin_call(p, pass, &c, no_args) == NCDE_OK ? route_kernel_name(c, pass) : nullptr;
 }
 
 int ncde_forward(const NcdeProblem* p, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
-    if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (!out) return fail(NCDE_ERR_INVALID, "out is NULL");
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, 0);
-    if (fam < 0) return fam;
-    const int64_t need = ncde_workspace_bytes(p, 0);
-    if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", workspace_bytes, (long long)need);
-    return launch_forward(p, y, fam, out, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+    Call c;
+    int rc = begin_call(p, 0, &c, [&](const NcdeProblem&) { return out ? (int)NCDE_OK : fail(NCDE_ERR_INVALID, "out is NULL"); });
+    if (rc == NCDE_OK) rc = check_workspace(c, 0, workspace, workspace_bytes, false);
+    return rc != NCDE_OK ? rc : launch_forward(c, out, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int ncde_forward_record(const NcdeProblem* p, float* out, float* stages, void* workspace, size_t workspace_bytes, void* stream) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
-    if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (!out || !stages) return fail(NCDE_ERR_INVALID, "out/stages is NULL");
-    if (p->flags & NCDE_FLAG_DEBUG_PROFILE) return fail(NCDE_ERR_UNSUPPORTED, "no instrumented recording forward");
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, 0);
-    if (fam < 0) return fam;
-    const int64_t need = ncde_workspace_bytes(p, 0);
-    if (need > 0 && (!workspace || (int64_t)workspace_bytes < need)) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", workspace_bytes, (long long)need);
-    return launch_forward(p, y, fam, out, stages, workspace, workspace_bytes, (hipStream_t)stream);
+    Call c;
+    int rc = begin_call(p, 0, &c, [&](const NcdeProblem& q) {
+        if (!out || !stages) return fail(NCDE_ERR_INVALID, "out/stages is NULL");
+        if (q.flags & NCDE_FLAG_DEBUG_PROFILE) return fail(NCDE_ERR_UNSUPPORTED, "no instrumented recording forward");
+        return (int)NCDE_OK;
+    });
+    if (rc == NCDE_OK) rc = check_workspace(c, 0, workspace, workspace_bytes, false);
+    return rc != NCDE_OK ? rc : launch_forward(c, out, stages, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int ncde_backward(const NcdeProblem* p, const float* stages, const float* grad_out, const NcdeGrads* grads, void* workspace,
                   size_t workspace_bytes, void* stream) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
-    if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (!stages || !grad_out || !grads || !grads->grad_z0) return fail(NCDE_ERR_INVALID, "NULL stages/grad_out/grads");
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, 2);
-    if (fam < 0) return fam;
-    const int64_t need = ncde_workspace_bytes(p, 2);
-    if (!workspace || (int64_t)workspace_bytes < need) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", workspace_bytes, (long long)need);
-    return launch_adjoint(p, y, fam, stages, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, true);
+    Call c;
+    int rc = begin_call(p, 2, &c, [&](const NcdeProblem&) {
+        return (stages && grad_out && grads && grads->grad_z0) ? (int)NCDE_OK : fail(NCDE_ERR_INVALID, "NULL stages/grad_out/grads");
+    });
+    if (rc == NCDE_OK) rc = check_workspace(c, 2, workspace, workspace_bytes, true);
+    return rc != NCDE_OK ? rc : launch_adjoint(c, stages, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, true);
 }
 
 int ncde_adjoint(const NcdeProblem* p, const float* z_out, const float* grad_out, const NcdeGrads* grads, void* workspace,
                  size_t workspace_bytes, void* stream) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
-    if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (!z_out || !grad_out || !grads || !grads->grad_z0) return fail(NCDE_ERR_INVALID, "NULL z_out/grad_out/grads");
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, 1);
-    if (fam < 0) return fam;
-    const int64_t need = ncde_workspace_bytes(p, 1);
-    if (!workspace || (int64_t)workspace_bytes < need) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", workspace_bytes, (long long)need);
-    return launch_adjoint(p, y, fam, z_out, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, false);
+    Call c;
+    int rc = begin_call(p, 1, &c, [&](const NcdeProblem&) {
+        return (z_out && grad_out && grads && grads->grad_z0) ? (int)NCDE_OK : fail(NCDE_ERR_INVALID, "NULL z_out/grad_out/grads");
+    });
+    if (rc == NCDE_OK) rc = check_workspace(c, 1, workspace, workspace_bytes, true);
+    return rc != NCDE_OK ? rc : launch_adjoint(c, z_out, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, false);
 }
 
 int ncde_time_kernel(const NcdeProblem* p, int pass, float* out, const float* grad_out, const NcdeGrads* grads, void* workspace,
                      size_t workspace_bytes, void* stream, int iters, float* ms_per_launch) {
-    NcdeProblem q_;
-    int rc = normalize(p, &q_);
+    Call c;
+    int rc = begin_call(p, pass, &c, [&](const NcdeProblem&) {
+        if (iters < 1 || !ms_per_launch) return fail(NCDE_ERR_INVALID, "iters < 1 or NULL result");
+        return pass_in_range(pass);
+    });
     if (rc != NCDE_OK) return rc;
-    p = &q_;
-    rc = validate(p);
-    if (rc != NCDE_OK) return rc;
-    if (iters < 1 || !ms_per_launch) return fail(NCDE_ERR_INVALID, "iters < 1 or NULL result");
-    if (pass < 0 || pass > 2) return fail(NCDE_ERR_INVALID, "pass %d outside {0, 1, 2}", pass);
-    const Layout y = make_layout(p);
-    const int fam = select_family(p, y, pass);
-    if (fam < 0) return fam;
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
@@ -729,8 +730,8 @@ int ncde_time_kernel(const NcdeProblem* p, int pass, float* out, const float* gr
     // one untimed launch (also sets function attributes), then `iters` timed ones
     for (int it = -1; it < iters; ++it) {
         if (it == 0) HIP_TRY(hipEventRecord(e0, st));
-        if (pass == 0) rc = launch_forward(p, y, fam, out, nullptr, workspace, workspace_bytes, st);
-        else rc = launch_adjoint(p, y, fam, out, grad_out, grads, workspace, workspace_bytes, st, true, pass == 2);
+        if (pass == 0) rc = launch_forward(c, out, nullptr, workspace, workspace_bytes, st);
+        else rc = launch_adjoint(c, out, grad_out, grads, workspace, workspace_bytes, st, true, pass == 2);
         if (rc != NCDE_OK) return rc;
     }
     HIP_TRY(hipEventRecord(e1, st));

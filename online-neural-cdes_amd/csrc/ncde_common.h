@@ -113,6 +113,9 @@ struct KArgs {
     int coop_inject;         // NCDE_FLAG_COOP_FAULT_INJECT: workgroup 1 skips its first arrival (tests the time-out path)
 };
 
+// every kernel of the library that takes its arguments as one KArgs
+typedef void (*NcdeKernel)(KArgs);
+
 // ---- time plan (built on the host by ncde_time_plan_build, csrc/ncde_timeplan.hip; layout in 4-byte words) -------------
 //   header  [8]                     : magic, S, n_fwd, n_adj, n_out, off_fwd, off_out, off_adj
 //   forward step  [3 + 3S] x n_fwd  : dt (f32), first output row emitted after the step, number of such rows,

@@ -2703,14 +2703,8 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
 // ------------------------------------------------------------------------------------------------
 // dispatch tables
 // ------------------------------------------------------------------------------------------------
-struct Shape {
-    int H, HH, C;
-};
-
-using FwdFn = void (*)(KArgs);
-
 template <int H, int HH, int C, int NW>
-FwdFn pick_fwd(int interp, int method) {
+NcdeKernel pick_fwd(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_fwd_fast<H, HH, C, NW, I, M>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -2724,7 +2718,7 @@ FwdFn pick_fwd(int interp, int method) {
 }
 
 template <int H, int HH, int C, int NW, int HP>
-FwdFn pick_fwd_split(int interp, int method, int n_layers) {
+NcdeKernel pick_fwd_split(int interp, int method, int n_layers) {
     // (the unrolled three-layer instantiations live in ncde_fast_fwd3.hip: the one unit built with MFMA results in VGPRs)
     if (n_layers == 3 && NW == 4 && ((H == 32 && HH == 32 && C == 20) || (H == 64 && HH == 64 && C == 4))) return ncde_fast_fwd3(H, interp, method, HP);
 #define NCDE_PICK(I, M) \
@@ -2739,12 +2733,12 @@ FwdFn pick_fwd_split(int interp, int method, int n_layers) {
     return nullptr;
 }
 template <int H, int HH, int C, int NW>
-FwdFn pick_fwd_bf3(int interp, int method, int n_layers, int hp) {
+NcdeKernel pick_fwd_bf3(int interp, int method, int n_layers, int hp) {
     return hp ? pick_fwd_split<H, HH, C, NW, 1>(interp, method, n_layers) : pick_fwd_split<H, HH, C, NW, 0>(interp, method, n_layers);
 }
 
 template <int H, int HH, int C, int NL, int NW>
-FwdFn pick_adj(int interp, int method) {
+NcdeKernel pick_adj(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_adj_fast<H, HH, C, NL, NW, I, M>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -2758,7 +2752,7 @@ FwdFn pick_adj(int interp, int method) {
 }
 
 template <int H, int HH, int C, int NL>
-FwdFn pick_adj2(int interp, int method) {
+NcdeKernel pick_adj2(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_adj_fast2<H, HH, C, NL, I, M>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -2786,12 +2780,12 @@ size_t adj2_lds_bytes(int interp) {
 #define NCDE_ADJ3_HP1(NL_, C_, I_, M_, P_, D_) ncde_adj_fast3<NL_, C_, I_, M_, P_, D_, 1>
 #define NCDE_ADJ3_HP1_AVAILABLE 1
 #else
-#define NCDE_ADJ3_HP1(NL_, C_, I_, M_, P_, D_) static_cast<FwdFn>(nullptr)
+#define NCDE_ADJ3_HP1(NL_, C_, I_, M_, P_, D_) static_cast<NcdeKernel>(nullptr)
 #define NCDE_ADJ3_HP1_AVAILABLE 0
 #endif
 
 template <int NL, int C>
-FwdFn pick_adj3(int interp, int method, int hp) {
+NcdeKernel pick_adj3(int interp, int method, int hp) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return hp == 2 ? ncde_adj_fast3<NL, C, I, M, 0, 0, 2> : (hp == 1 ? NCDE_ADJ3_HP1(NL, C, I, M, 0, 0) : ncde_adj_fast3<NL, C, I, M>);
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -2805,7 +2799,7 @@ FwdFn pick_adj3(int interp, int method, int hp) {
 }
 
 template <int NL, int C>
-FwdFn pick_adj3_disc(int interp, int method, int hp) {
+NcdeKernel pick_adj3_disc(int interp, int method, int hp) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return hp == 2 ? ncde_adj_fast3<NL, C, I, M, 0, 1, 2> : (hp == 1 ? NCDE_ADJ3_HP1(NL, C, I, M, 0, 1) : ncde_adj_fast3<NL, C, I, M, 0, 1>);
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -2843,54 +2837,24 @@ size_t adj_lds_bytes(int interp) {
     return sizeof(float) * (size_t)(2 * H * 16 + 3 * 16 * DXW + NW * HH * 16 + NW * NTILE * HT * 256 + NW * NTILE * 16 + NW * PRIV);
 }
 
+// One row per kernel set that has a forward of its own.  Only (32, 32, 20) also has adjoints: ncde_adj_fast / fast2 / fast3 / fast4 for
+// kAdjLayers layers here, ncde_adj_fast3 for the other layer counts in ncde_fast_nl.hip, the PLAN = 1 instances in ncde_fast_plan.hip.
 struct FastEntry {
-    Shape shape;
-    int nw;
-    FwdFn (*fwd)(int, int);
-    const char* fwd_name;
-    FwdFn (*fwd_bf3)(int, int, int, int);  // split-GEMM variants (default: split-fp16; NCDE_FLAG_SPLIT_BF16: split-bf16); NCDE_FLAG_FP32_MFMA selects `fwd`
-    const char* fwd_bf3_name;
-    const char* fwd_h2_name;
-    int nw_bf3;
-    int adj_layers;                 // n_layers the adjoint instantiation is built for (0 = none)
-    FwdFn (*adj)(int, int);
-    size_t (*adj_lds)(int);
-    const char* adj_name;
-    FwdFn (*adj2)(int, int);        // wave-specialised variant, fp32 chain (NCDE_FLAG_ADJOINT_V2)
-    size_t (*adj2_lds)(int);
-    const char* adj2_name;
-    FwdFn (*adj3)(int, int, int);   // wave-specialised variant, split GEMMs (default); last argument: 1 = split-fp16, 0 = split-bf16
-    size_t (*adj3_lds)(int, int);
-    const char* adj3_name;
-    const char* adj3_h2_name;       // HP = 1
-    const char* adj3_f2_name;       // HP = 2
-    FwdFn (*adj3_disc)(int, int, int);   // same kernel transposing the discretised solve (ncde_backward)
-    const char* adj3_disc_name;
-    const char* adj3_disc_h2_name;
-    const char* adj3_disc_f2_name;
+    int H, HH, C;
+    NcdeKernel (*fwd)(int interp, int method);                            // fp32-input MFMA (NCDE_FLAG_FP32_MFMA)
+    NcdeKernel (*fwd_split)(int interp, int method, int n_layers, int hp);   // split GEMMs: hp 1 = split-fp16 (default), 0 = split-bf16
+    bool adjoint;
 };
-
 const FastEntry kFast[] = {
-    // BASELINE cfg2 / cfg3
-    {{32, 32, 20}, 4, pick_fwd<32, 32, 20, 4>, "ncde_fwd_fast<H32,HH32,C20,NW4>",
-     pick_fwd_bf3<32, 32, 20, 4>, "ncde_fwd_fast_bf3<H32,HH32,C20,NW4,bf16x3>", "ncde_fwd_fast_bf3<H32,HH32,C20,NW4,fp16x2>", 4,
-     3, pick_adj<32, 32, 20, 3, 4>, adj_lds_bytes<32, 32, 20, 3, 4>, "ncde_adj_fast<H32,HH32,C20,NL3,NW4>",
-     pick_adj2<32, 32, 20, 3>, adj2_lds_bytes<32, 32, 20, 3>, "ncde_adj_fast2<H32,HH32,C20,NL3,chain+grad>",
-     pick_adj3<3, 20>, adj3_lds_bytes<3, 20>, "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,fp16x2>",
-     "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,fwd-side fp16x2 + bf16x3>",
-     pick_adj3_disc<3, 20>, "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,bf16x3,discrete>", "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,fp16x2,discrete>",
-     "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,fwd-side fp16x2 + bf16x3,discrete>"},
-    // BASELINE cfg4 (adjoint: generic family for now -- the per-wave LDS images do not fit at HH=64)
-    {{64, 64, 4}, 4, pick_fwd<64, 64, 4, 4>, "ncde_fwd_fast<H64,HH64,C4,NW4>",
-     pick_fwd_bf3<64, 64, 4, 4>, "ncde_fwd_fast_bf3<H64,HH64,C4,NW4,bf16x3>", "ncde_fwd_fast_bf3<H64,HH64,C4,NW4,fp16x2>", 4, 0, nullptr, nullptr, nullptr,
-     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {32, 32, 20, pick_fwd<32, 32, 20, 4>, pick_fwd_bf3<32, 32, 20, 4>, true},       // BASELINE cfg2 / cfg3
+    // BASELINE cfg4 (adjoint: ncde_fast64.hip -- the per-wave LDS images of ncde_adj_fast3 do not fit at HH = 64)
+    {64, 64, 4, pick_fwd<64, 64, 4, 4>, pick_fwd_bf3<64, 64, 4, 4>, false},
     // round 5: the forward alone for up to 40 channels at H, HH <= 32 (its 160 + 80 registers of output-layer operands fit the one
     // wave per SIMD the forward runs at; the adjoint's chain / gradient waves, two per SIMD, have no room for them): inference and the
     // forward half of a training step of such shapes leave the batch-tiled family.  Default time axis only.
-    {{32, 32, 40}, 4, pick_fwd<32, 32, 40, 4>, "ncde_fwd_fast<H32,HH32,C40,NW4>",
-     pick_fwd_bf3<32, 32, 40, 4>, "ncde_fwd_fast_bf3<H32,HH32,C40,NW4,bf16x3>", "ncde_fwd_fast_bf3<H32,HH32,C40,NW4,fp16x2>", 4, 0, nullptr, nullptr, nullptr,
-     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+    {32, 32, 40, pick_fwd<32, 32, 40, 4>, pick_fwd_bf3<32, 32, 40, 4>, false},
 };
+constexpr int kAdjLayers = 3;
 
 const FastEntry* find_entry(const NcdeProblem* p) {
     // structure the fast family understands: layer 0 is H->HH, every further layer is ONE shared HH->HH
@@ -2899,30 +2863,13 @@ const FastEntry* find_entry(const NcdeProblem* p) {
     for (int l = 1; l < p->n_layers; ++l)
         if (p->layer_out[l] != HH || p->layer_in[l] != HH || p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return nullptr;
     for (const FastEntry& e : kFast)
-        if (e.shape.H == p->hidden && e.shape.HH == HH && e.shape.C == p->channels) return &e;
+        if (e.H == p->hidden && e.HH == HH && e.C == p->channels) return &e;
     return nullptr;
 }
 
-// the decoupled-chain adjoint (ncde_fast4.hip): selectable (NCDE_FLAG_ADJOINT_V4), not the default -- measured slower
-bool use_v4(const NcdeProblem* p, const FastEntry* e, bool discrete) {
-    if (e->shape.H != 32 || e->shape.HH != 32) return false;
-    if (!(p->flags & NCDE_FLAG_ADJOINT_V4) || (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | 0x200u))) return false;
-    if (discrete && (p->flags & NCDE_FLAG_DEBUG_PROFILE)) return false;
-    return ncde_fast4_pick(p->n_layers, p->channels, p->interp, p->method, discrete, (p->flags & NCDE_FLAG_DEBUG_PROFILE) != 0) != nullptr;
-}
-
-}  // namespace
-
-// (32, 32, 20) with a layer count besides the entry's own: the further instantiations of ncde_adj_fast3 in ncde_fast_nl.hip
-static int nl_hp(const NcdeProblem* p) { return (p->flags & (NCDE_FLAG_SPLIT_BF16 | NCDE_FLAG_FP32_MFMA)) ? 0 : 2; }
-static bool use_nl(const NcdeProblem* p, const FastEntry* e, int pass) {
-    if (pass < 1 || !e || e->adj3 == nullptr || e->adj_layers == p->n_layers) return false;
-    if (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | 0x200u)) return false;
-    return ncde_fast_adj3_nl(p->n_layers, p->interp, p->method, nl_hp(p), pass == 2) != nullptr;
-}
 // (H, HH) = (32, 32) with C = 4 / 8 / 12 (round 6, ncde_fast_c.hip): the same kernel templates instantiated for few channels, every
 // layer count 1 .. 4, forward + continuous adjoint + exact discrete backward; default time axis, default / split-bf16 arithmetic
-static int c_set(const NcdeProblem* p) {
+int c_set(const NcdeProblem* p) {
     if (p->hidden != 32 || p->n_layers < 1 || p->n_layers > 4 || p->layer_out[0] != 32 || p->layer_in[0] != 32) return 0;
     if (p->channels != 4 && p->channels != 8 && p->channels != 12) return 0;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL || p->output == NCDE_OUT_TIMES) return 0;
@@ -2930,277 +2877,193 @@ static int c_set(const NcdeProblem* p) {
         if (p->layer_out[l] != 32 || p->layer_in[l] != 32 || p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return 0;
     if (p->n_layers > 1 && (p->layer_W[1] == p->layer_W[0] || p->layer_b[1] == p->layer_b[0])) return 0;
     if (p->flags & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_ADJOINT_SPLIT_FP16 |
-                    NCDE_FLAG_DEBUG_PROFILE | 0x200u)) return 0;
+                    NCDE_FLAG_DEBUG_PROFILE | kFlagChainDump)) return 0;
     return p->channels;
 }
-static NcdeFastCKernel c_fwd(int C, int interp, int method, int hp) {
+NcdeKernel c_fwd(int C, int interp, int method, int hp) {
     return C == 4 ? ncde_fast_c4_fwd(interp, method, hp) : (C == 8 ? ncde_fast_c8_fwd(interp, method, hp) : ncde_fast_c12_fwd(interp, method, hp));
 }
-static NcdeFastCKernel c_adj(int C, int nl, int interp, int method, int hp, bool disc) {
+NcdeKernel c_adj(int C, int nl, int interp, int method, int hp, bool disc) {
     return C == 4 ? ncde_fast_c4_adj(nl, interp, method, hp, disc) : (C == 8 ? ncde_fast_c8_adj(nl, interp, method, hp, disc) : ncde_fast_c12_adj(nl, interp, method, hp, disc));
 }
-static size_t c_adj_lds(int C, int nl, int interp, int hp) {
+size_t c_adj_lds(int C, int nl, int interp, int hp) {
     return C == 4 ? ncde_fast_c4_adj_lds(nl, interp, hp) : (C == 8 ? ncde_fast_c8_adj_lds(nl, interp, hp) : ncde_fast_c12_adj_lds(nl, interp, hp));
 }
-static bool use_c(const NcdeProblem* p, int pass) {
-    const int C = c_set(p);
-    if (!C) return false;
-    if (pass == 0) return c_fwd(C, p->interp, p->method, 1) != nullptr;
-    return c_adj(C, p->n_layers, p->interp, p->method, nl_hp(p), pass == 2) != nullptr && c_adj(C, p->n_layers, p->interp, p->method, 0, pass == 2) != nullptr;
+
+// ---- reported names: the one place ---------------------------------------------------------------------------------------------
+// shape index: the rows of kFast, then the few-channel sets
+int shape_index(int H, int C) { return H == 64 ? 1 : (C == 20 ? 0 : (C == 40 ? 2 : 2 + C / 4)); }
+#define NCDE_FWD_NAME(H, C, ARITH, SUFFIX) "ncde_fwd_fast_bf3<H" #H ",HH" #H ",C" #C ",NW4," ARITH SUFFIX ">"
+#define NCDE_FWD_NAMES(H, C)                                                                                            \
+    {{"ncde_fwd_fast<H" #H ",HH" #H ",C" #C ",NW4>", nullptr}, {NCDE_FWD_NAME(H, C, "bf16x3", ""), NCDE_FWD_NAME(H, C, "bf16x3", ",time plan")}, \
+     {NCDE_FWD_NAME(H, C, "fp16x2", ""), NCDE_FWD_NAME(H, C, "fp16x2", ",time plan")}}
+// [shape][0 fp32-input MFMA, 1 split-bf16, 2 split-fp16][time plan]
+const char* const kFwdNames[6][3][2] = {NCDE_FWD_NAMES(32, 20), NCDE_FWD_NAMES(64, 4), NCDE_FWD_NAMES(32, 40),
+                                        NCDE_FWD_NAMES(32, 4), NCDE_FWD_NAMES(32, 8), NCDE_FWD_NAMES(32, 12)};
+#define NCDE_ADJ3_NAME(C, NL, ARITH, SUFFIX) "ncde_adj_fast3<H32,HH32,C" #C ",NL" #NL ",chain+grad," ARITH SUFFIX ">"
+#define NCDE_ADJ3_ARITH(C, NL, ARITH) {NCDE_ADJ3_NAME(C, NL, ARITH, ""), NCDE_ADJ3_NAME(C, NL, ARITH, ",discrete"), NCDE_ADJ3_NAME(C, NL, ARITH, ",time plan")}
+#define NCDE_ADJ3_LAYERS(C, NL) {NCDE_ADJ3_ARITH(C, NL, "bf16x3"), NCDE_ADJ3_ARITH(C, NL, "fp16x2"), NCDE_ADJ3_ARITH(C, NL, "fwd-side fp16x2 + bf16x3")}
+#define NCDE_ADJ3_NAMES(C) {NCDE_ADJ3_LAYERS(C, 1), NCDE_ADJ3_LAYERS(C, 2), NCDE_ADJ3_LAYERS(C, 3), NCDE_ADJ3_LAYERS(C, 4)}
+// [shape (2: none)][n_layers - 1][hp][0 continuous, 1 discrete, 2 time plan]
+const char* const kAdj3Names[6][4][3][3] = {NCDE_ADJ3_NAMES(20), {}, {}, NCDE_ADJ3_NAMES(4), NCDE_ADJ3_NAMES(8), NCDE_ADJ3_NAMES(12)};
+
+// The HP template argument of the split-GEMM kernels -- the one place that reads it off the flags.  Forward: 1 = split-fp16 (default),
+// 0 = split-bf16 (NCDE_FLAG_SPLIT_BF16; NCDE_FLAG_FP32_MFMA runs the fp32-input kernel, which has no HP).  ncde_adj_fast3: 2 = the
+// forward-side GEMMs of the chain waves split-fp16 (default), 0 = all split-bf16, 1 = everything split-fp16 (NCDE_FLAG_ADJOINT_SPLIT_FP16,
+// experimental: DESIGN.md section 5.4c; development builds, and the entry's own layer count, only).  A kernel with hp != 0 reports
+// range faults and is followed by the hp = 0 instance on the faulted workgroups.
+int fast_hp(uint32_t flags, int pass, bool own_layers) {
+    if (flags & NCDE_FLAG_SPLIT_BF16) return 0;
+    if (pass == 0) return (flags & NCDE_FLAG_FP32_MFMA) ? 0 : 1;
+    if (!own_layers) return (flags & NCDE_FLAG_FP32_MFMA) ? 0 : 2;
+    if (flags & kFlagChainDump) return 0;
+    return (NCDE_ADJ3_HP1_AVAILABLE != 0 && (flags & NCDE_FLAG_ADJOINT_SPLIT_FP16)) ? 1 : 2;
 }
-static const char* c_name(const NcdeProblem* p, int pass) {
-    static char buf[3][5][3][2][96];      // [channel set][layers][pass][split]: filled on first use (idempotent: racing threads write the same bytes)
-    const int C = p->channels, ci = C == 4 ? 0 : (C == 8 ? 1 : 2), bf = (p->flags & NCDE_FLAG_SPLIT_BF16) ? 1 : 0;
-    char* b = buf[ci][p->n_layers][pass][bf];
-    if (!b[0]) {
-        char tmp[96];
-        if (pass == 0) snprintf(tmp, sizeof(tmp), "ncde_fwd_fast_bf3<H32,HH32,C%d,NW4,%s>", C, bf ? "bf16x3" : "fp16x2");
-        else snprintf(tmp, sizeof(tmp), "ncde_adj_fast3<H32,HH32,C%d,NL%d,chain+grad,%s%s>", C, p->n_layers, bf ? "bf16x3" : "fwd-side fp16x2 + bf16x3", pass == 2 ? ",discrete" : "");
-        memcpy(b, tmp, sizeof(tmp));
+
+constexpr uint32_t kDevVariantFlags = NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | kFlagChainDump;
+
+// forward: the few-channel sets, the PLAN = 1 instances (general time axis), else the entry's own
+void plan_forward(const NcdeProblem* p, const Layout& y, int cset, const FastEntry* e, FastPlan* P) {
+    const uint32_t f = p->flags;
+    const bool planned = p->output == NCDE_OUT_TIMES, fp32 = (f & NCDE_FLAG_FP32_MFMA) != 0, prof = (f & NCDE_FLAG_DEBUG_PROFILE) != 0;
+    const int hp = fast_hp(f, 0, true), shape = cset ? shape_index(32, cset) : (e ? shape_index(e->H, e->C) : 0);
+    auto pick = [&](int h) -> NcdeKernel {
+        if (cset) return c_fwd(cset, p->interp, p->method, h);
+        if (planned) return ncde_fast_plan_fwd(e->H == 32 ? 0 : 1, p->interp, p->method, h);
+        return e->fwd_split(p->interp, p->method, p->n_layers, h);
+    };
+    if (!cset) {
+        if (!e) return;
+        // (the plan-walking instances: split GEMMs of the two BASELINE shapes; the forward-only C = 40 set has none)
+        if (planned && ((f & (kDevVariantFlags | NCDE_FLAG_FP32_MFMA)) || e->C == 40)) return;
     }
-    return b;
-}
-// H = HH = 64, C <= 4: the in-sweep adjoint of ncde_fast64.hip (the entry's own adjoint slots are empty; C < 4 has no entry at all)
-static bool use_h64(const NcdeProblem* p, int pass) { return pass >= 1 && ncde_fast64_supported(p, pass); }
-
-// general time axis (NcdeProblem.time_plan): the PLAN = 1 instances of ncde_fast_plan.hip -- forward of both shapes (split GEMMs,
-// runtime layer count), continuous adjoint of (32, 32, 20) with nl = 3; (64, 64, <= 4): ncde_fast64.hip's own planned instances
-static bool planned_ok(const NcdeProblem* p, const FastEntry* e, int pass) {
-    if (p->flags & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | 0x200u)) return false;
-    if (e != nullptr && e->shape.C == 40) return false;      // (the forward-only C <= 40 set has no plan-walking instances)
-    if (pass == 0) return e != nullptr && ncde_fast_plan_fwd(e->shape.H == 32 ? 0 : 1, p->interp, p->method, 1) != nullptr;
-    if (pass == 1) return e != nullptr && e->shape.H == 32 && ncde_fast_plan_adj3(p->n_layers, p->interp, p->method, 2) != nullptr;
-    return false;
-}
-
-bool ncde_fast_supported(const NcdeProblem* p, int pass) {
-    if (use_h64(p, pass)) return true;
-    if (use_c(p, pass)) return true;
-    const FastEntry* e = find_entry(p);
-    if (p->output == NCDE_OUT_TIMES) return planned_ok(p, e, pass);
-    if (!e) return false;
-    if (pass == 0) return true;
-    if (use_nl(p, e, pass)) return true;
-    if (pass == 2) return e->adj3_disc != nullptr && e->adj_layers == p->n_layers;
-    return e->adj != nullptr && e->adj_layers == p->n_layers;
-}
-
-const char* ncde_fast_kernel_name(const NcdeProblem* p, int pass) {
-    if (use_h64(p, pass)) return ncde_fast64_kernel_name(p, pass);
-    if (use_c(p, pass)) return c_name(p, pass);
-    if (!ncde_fast_supported(p, pass)) return nullptr;
-    const FastEntry* e = find_entry(p);
-    if (p->output == NCDE_OUT_TIMES) {
-        const bool bf = (p->flags & NCDE_FLAG_SPLIT_BF16) != 0;
-        if (pass == 0) return e->shape.H == 32 ? (bf ? "ncde_fwd_fast_bf3<H32,HH32,C20,NW4,bf16x3,time plan>" : "ncde_fwd_fast_bf3<H32,HH32,C20,NW4,fp16x2,time plan>")
-                                               : (bf ? "ncde_fwd_fast_bf3<H64,HH64,C4,NW4,bf16x3,time plan>" : "ncde_fwd_fast_bf3<H64,HH64,C4,NW4,fp16x2,time plan>");
-        return bf ? "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,bf16x3,time plan>" : "ncde_adj_fast3<H32,HH32,C20,NL3,chain+grad,fwd-side fp16x2 + bf16x3,time plan>";
+    P->main = {fp32 ? e->fwd(p->interp, p->method) : pick(hp), 256, 0};
+    if ((cset || planned) && !P->main.fn) return;
+    P->ok = true;
+    P->name = kFwdNames[shape][fp32 ? 0 : 1 + hp][planned];
+    if (hp) P->redo = {pick(0), 256, 0};
+    if (prof) {      // phase-cycle counters -> head of the workspace [n_wg][NW][4] u64; instrumented: (32, 32, 20), linear, rk4 only
+        P->main.fn = nullptr;
+        P->redo.fn = nullptr;
+        P->tail_off = 0;
+        if (e->H == 32 && e->C == 20 && p->interp == NCDE_INTERP_LINEAR && p->method == NCDE_RK4_38)
+            P->main.fn = fp32 ? ncde_fwd_fast<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>
+                              : (p->n_layers != 3 ? ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>
+                                                  : (hp ? ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 3, 1>
+                                                        : ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 3>));
     }
-    if (use_nl(p, e, pass)) return ncde_fast_adj3_nl_name(p->n_layers, nl_hp(p), pass == 2);
-    const bool h2f = !(p->flags & NCDE_FLAG_SPLIT_BF16);
-    const bool h2 = h2f && NCDE_ADJ3_HP1_AVAILABLE != 0 && (p->flags & NCDE_FLAG_ADJOINT_SPLIT_FP16);
-    const bool f2 = h2f && !h2 && !(p->flags & 0x200u);
-    if (pass == 0) return ((p->flags & NCDE_FLAG_FP32_MFMA) == 0 && e->fwd_bf3) ? (h2f ? e->fwd_h2_name : e->fwd_bf3_name) : e->fwd_name;
-    if (use_v4(p, e, pass == 2)) return pass == 2 ? "ncde_adj_fast4<H32,HH32,C20,NL3,y-waves+cotangent-waves(bf16x3),discrete>"
-                                                  : "ncde_adj_fast4<H32,HH32,C20,NL3,y-waves+cotangent-waves(bf16x3)>";
-    if (pass == 2) return h2 ? e->adj3_disc_h2_name : (f2 ? e->adj3_disc_f2_name : e->adj3_disc_name);
-    if (p->flags & NCDE_FLAG_ADJOINT_V1) return e->adj_name;
-    if ((p->flags & NCDE_FLAG_ADJOINT_V2) && e->adj2) return e->adj2_name;
-    return e->adj3 ? (h2 ? e->adj3_h2_name : (f2 ? e->adj3_f2_name : e->adj3_name)) : (e->adj2 ? e->adj2_name : e->adj_name);
+    ncde_fast_plan_workspace(P, 256 + (prof ? (int64_t)y.n_wg * 8 * 4 * 8 : 0), hp != 0);
 }
 
-// range-fault words of the split-fp16 kernels, one per workgroup, at the tail of the workspace
-static int64_t fault_bytes(const Layout& y) { return ((int64_t)y.n_wg * 4 + 255) & ~(int64_t)255; }
+// adjoint / exact discrete backward of the (32, 32, C) sets (H = 64: ncde_fast64_plan)
+void plan_adjoint(const NcdeProblem* p, const Layout& y, int pass, int cset, const FastEntry* e, FastPlan* P) {
+    const uint32_t f = p->flags;
+    const bool disc = pass == 2, planned = p->output == NCDE_OUT_TIMES;
+    const bool prof = (f & NCDE_FLAG_DEBUG_PROFILE) != 0, dump = (f & kFlagChainDump) != 0;
+    const int interp = p->interp, method = p->method, nl = p->n_layers;
+    if (!cset && (!e || !e->adjoint)) return;
+    const bool own_layers = !cset && !planned && nl == kAdjLayers;
+    int hp = fast_hp(f, pass, own_layers);
+    if (!own_layers) {
+        // ncde_adj_fast3 alone, hp 2 / 0: few channels (ncde_fast_c.hip), the general time axis (ncde_fast_plan.hip: continuous adjoint,
+        // kAdjLayers layers), another layer count (ncde_fast_nl.hip).  No development variants.
+        if (!cset && ((f & kDevVariantFlags) || (planned && (disc || (f & NCDE_FLAG_FP32_MFMA))))) return;
+        auto inst = [&](int h) -> FastLaunch {
+            if (cset) return {c_adj(cset, nl, interp, method, h, disc), 512, c_adj_lds(cset, nl, interp, h)};
+            if (planned) return {ncde_fast_plan_adj3(nl, interp, method, h), 512, ncde_fast_plan_adj3_lds(nl, interp, method, h)};
+            return {ncde_fast_adj3_nl(nl, interp, method, h, disc), 512, ncde_fast_adj3_nl_lds(nl, interp, h)};
+        };
+        P->main = inst(hp);
+        if (hp) P->redo = inst(0);
+        if (!P->main.fn || (hp && !P->redo.fn)) return;
+        P->name = kAdj3Names[shape_index(32, p->channels)][nl - 1][hp][planned ? 2 : disc];
+    } else {
+        // the entry's own layer count: ncde_adj_fast3 (default; always for the discrete backward), the single-role ncde_adj_fast
+        // (NCDE_FLAG_ADJOINT_V1), ncde_adj_fast2 with an fp32 chain (NCDE_FLAG_ADJOINT_V2), the decoupled-chain ncde_adj_fast4
+        // (NCDE_FLAG_ADJOINT_V4: selectable, measured slower -- DESIGN.md section 5.4b), and their instrumented variants
+        const bool v1 = !disc && (f & NCDE_FLAG_ADJOINT_V1), v3 = disc || (!v1 && !(f & NCDE_FLAG_ADJOINT_V2));
+        const bool lin_rk4 = interp == NCDE_INTERP_LINEAR && method == NCDE_RK4_38, cub_mid = interp == NCDE_INTERP_CUBIC && method == NCDE_MIDPOINT;
+        NcdeKernel k4 = nullptr;
+        if ((f & NCDE_FLAG_ADJOINT_V4) && !(f & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | kFlagChainDump)) && !(disc && prof))
+            k4 = ncde_fast4_pick(nl, p->channels, interp, method, disc, prof);
+        if (k4) {
+            hp = 0;
+            P->main = {k4, 512, ncde_fast4_lds_bytes(nl, p->channels, interp)};
+            P->name = disc ? "ncde_adj_fast4<H32,HH32,C20,NL3,y-waves+cotangent-waves(bf16x3),discrete>" : "ncde_adj_fast4<H32,HH32,C20,NL3,y-waves+cotangent-waves(bf16x3)>";
+        } else {
+            if (!v3) hp = 0;
+            P->main.fn = disc ? pick_adj3_disc<3, 20>(interp, method, hp)
+                              : (v1 ? pick_adj<32, 32, 20, 3, 4>(interp, method) : (v3 ? pick_adj3<3, 20>(interp, method, hp) : pick_adj2<32, 32, 20, 3>(interp, method)));
+            P->main.block = v1 ? 256 : 512;
+            // (with the chain dump the LDS size is still the one of the kernel the other flags select)
+            P->main.lds = v1 ? adj_lds_bytes<32, 32, 20, 3, 4>(interp) : (v3 ? adj3_lds_bytes<3, 20>(interp, hp) : adj2_lds_bytes<32, 32, 20, 3>(interp));
+            P->name = v3 ? kAdj3Names[0][nl - 1][hp][disc] : (v1 ? "ncde_adj_fast<H32,HH32,C20,NL3,NW4>" : "ncde_adj_fast2<H32,HH32,C20,NL3,chain+grad>");
+            if (hp && !prof) P->redo = {disc ? pick_adj3_disc<3, 20>(interp, method, 0) : pick_adj3<3, 20>(interp, method, 0), 512, adj3_lds_bytes<3, 20>(interp, 0)};
+            if (dump)      // per-stage chain values of workgroup 0 -> development tail: cubic + midpoint, continuous adjoint only
+                P->main.fn = (disc || !cub_mid) ? nullptr
+                             : (v1 ? ncde_adj_fast<32, 32, 20, 3, 4, NCDE_INTERP_CUBIC, NCDE_MIDPOINT, 2> : ncde_adj_fast2<32, 32, 20, 3, NCDE_INTERP_CUBIC, NCDE_MIDPOINT, 2>);
+            if (prof)      // phase-cycle counters -> development tail [n_wg][NW][6] u64: linear + rk4, continuous adjoint only
+                P->main.fn = (disc || dump || !lin_rk4) ? nullptr
+                             : (v3 ? (hp == 2 ? ncde_adj_fast3<3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0, 2>
+                                              : (hp == 1 ? NCDE_ADJ3_HP1(3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0) : ncde_adj_fast3<3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>))
+                                   : (v1 ? ncde_adj_fast<32, 32, 20, 3, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1> : ncde_adj_fast2<32, 32, 20, 3, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>));
+        }
+    }
+    P->ok = true;
+    P->reduce = true;
+    const int64_t partials = (int64_t)sizeof(float) * (int64_t)y.n_wg * (int64_t)y.theta_size + 256;
+    if (prof || dump) P->tail_off = partials;
+    ncde_fast_plan_workspace(P, partials + (prof ? (int64_t)y.n_wg * 8 * 6 * 8 + 256 : 0) + (dump ? (int64_t)p->n_knots * 4 * 5 * 64 * 4 + 256 : 0), hp != 0);
+}
 
-int64_t ncde_fast_workspace_bytes(const NcdeProblem* p, int pass) {
-    if (use_h64(p, pass)) return ncde_fast64_workspace_bytes(p, pass);
-    // (the few-channel instances of ncde_fast_c.hip use the generic layout below: partials + fault words)
-    if (!ncde_fast_supported(p, pass)) return NCDE_ERR_UNSUPPORTED;
+}  // namespace
+
+FastPlan ncde_fast_plan(const NcdeProblem* p, int pass) {
+    FastPlan P{};
+    P.fault_off = P.tail_off = -1;
+    // (a piecewise-quintic control never runs here: the dX/dt staging of these kernels knows the linear and cubic rows only)
+    if (pass < 0 || pass > 2 || p->interp == NCDE_INTERP_QUINTIC) return P;
     const Layout y = make_layout(p);
-    if (pass == 0) return ((p->flags & NCDE_FLAG_DEBUG_PROFILE) ? 256 + (int64_t)y.n_wg * 8 * 4 * 8 : 256) + fault_bytes(y);
-    return (int64_t)sizeof(float) * (int64_t)y.n_wg * (int64_t)y.theta_size + 256 +
-           ((p->flags & NCDE_FLAG_DEBUG_PROFILE) ? (int64_t)y.n_wg * 8 * 6 * 8 + 256 : 0) +
-           ((p->flags & 0x200u) ? (int64_t)p->n_knots * 4 * 5 * 64 * 4 + 256 : 0) + fault_bytes(y);
+    P.grid = y.n_wg;
+    if (pass >= 1 && ncde_fast64_plan(p, pass, y, &P)) return P;      // H = HH = 64, C <= 4: the in-sweep adjoint of ncde_fast64.hip
+    const int cset = c_set(p);
+    const FastEntry* e = cset ? nullptr : find_entry(p);
+    if (pass == 0) plan_forward(p, y, cset, e, &P);
+    else plan_adjoint(p, y, pass, cset, e, &P);
+    if (!P.ok) P.name = nullptr;
+    return P;
 }
 
-int ncde_fast_forward(const NcdeProblem* p, float* out, float* stages, void* ws, size_t ws_bytes, hipStream_t st) {
-    (void)ws_bytes;
-    if (use_c(p, 0)) {      // few channels: ncde_fast_c.hip's instances, the launch protocol of the split-fp16 forward below
-        const Layout y = make_layout(p);
-        KArgs a;
-        fill_kargs(p, y, &a);
+// THE launch of a register-resident kernel: main kernel (LDS opt-in), the re-execution of range-faulted workgroups where the plan has
+// one (normally no workgroup: each exits at once), then the reduce of the per-workgroup gradient partials.
+int ncde_fast_launch(const NcdeProblem* p, int pass, float* out, float* stages, const float* src, const float* grad_out,
+                     const NcdeGrads* g, void* ws, size_t ws_bytes, hipStream_t st, bool main_kernel_only) {
+    const FastPlan P = ncde_fast_plan(p, pass);
+    if (!P.ok || !P.main.fn) return NCDE_ERR_UNSUPPORTED;
+    if ((int64_t)ws_bytes < P.ws_bytes) return NCDE_ERR_WORKSPACE;
+    const Layout y = make_layout(p);
+    KArgs a;
+    fill_kargs(p, y, &a);
+    if (pass == 0) {
         a.out = out;
         a.stages = stages;
-        const int hp = (p->flags & NCDE_FLAG_SPLIT_BF16) ? 0 : 1;
-        a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, 0) - fault_bytes(y)) : nullptr;
-        hipLaunchKernelGGL(c_fwd(p->channels, p->interp, p->method, hp), dim3(y.n_wg), dim3(256), 0, st, a);
-        if (hp) {      // re-execution of range-faulted tiles in split-bf16 (normally none: every workgroup exits at once)
-            a.only_faulted = 1;
-            hipLaunchKernelGGL(c_fwd(p->channels, p->interp, p->method, 0), dim3(y.n_wg), dim3(256), 0, st, a);
-        }
-        return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
-    }
-    const FastEntry* e = find_entry(p);
-    if (!e) return NCDE_ERR_UNSUPPORTED;
-    FwdFn fn = e->fwd(p->interp, p->method);
-    if (!fn) return NCDE_ERR_UNSUPPORTED;
-    const Layout y = make_layout(p);
-    KArgs a;
-    fill_kargs(p, y, &a);
-    a.out = out;
-    a.stages = stages;
-    const bool bf3 = (p->flags & NCDE_FLAG_FP32_MFMA) == 0 && e->fwd_bf3 != nullptr;
-    const int hp = (bf3 && !(p->flags & NCDE_FLAG_SPLIT_BF16)) ? 1 : 0;
-    if (bf3) fn = e->fwd_bf3(p->interp, p->method, p->n_layers, hp);
-    const bool planned = p->output == NCDE_OUT_TIMES;
-    if (planned) {
-        if (!planned_ok(p, e, 0)) return NCDE_ERR_UNSUPPORTED;
-        fn = ncde_fast_plan_fwd(e->shape.H == 32 ? 0 : 1, p->interp, p->method, hp);
-    }
-    a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, 0) - fault_bytes(y)) : nullptr;
-    if (p->flags & NCDE_FLAG_DEBUG_PROFILE) {  // phase-cycle counters -> workspace [n_wg][NW][4] u64
-        if (!(e->shape.H == 32 && e->shape.C == 20 && p->interp == NCDE_INTERP_LINEAR && p->method == NCDE_RK4_38)) return NCDE_ERR_UNSUPPORTED;
-        fn = bf3 ? (p->n_layers == 3 ? (hp ? ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 3, 1>
-                                           : ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 3>)
-                                     : ncde_fwd_fast_bf3<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>)
-                 : ncde_fwd_fast<32, 32, 20, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>;
-        a.gpart = (float*)ws;
-    }
-    hipLaunchKernelGGL(fn, dim3(y.n_wg), dim3(64 * (bf3 ? e->nw_bf3 : e->nw)), 0, st, a);
-    if (hp && !(p->flags & NCDE_FLAG_DEBUG_PROFILE)) {  // re-execution of range-faulted tiles (normally none: every workgroup exits at once)
-        a.only_faulted = 1;
-        FwdFn fx = planned ? ncde_fast_plan_fwd(e->shape.H == 32 ? 0 : 1, p->interp, p->method, 0) : e->fwd_bf3(p->interp, p->method, p->n_layers, 0);
-        hipLaunchKernelGGL(fx, dim3(y.n_wg), dim3(64 * e->nw_bf3), 0, st, a);
-    }
-    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
-}
-
-int ncde_fast_adjoint(const NcdeProblem* p, const float* z_out, const float* grad_out, const NcdeGrads* g, void* ws,
-                      size_t ws_bytes, hipStream_t st, bool main_kernel_only, bool discrete) {
-    if (use_h64(p, discrete ? 2 : 1)) return ncde_fast64_adjoint(p, z_out, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete);
-    if (!ncde_fast_supported(p, discrete ? 2 : 1)) return NCDE_ERR_UNSUPPORTED;
-    if (use_c(p, discrete ? 2 : 1)) {      // few channels: the same kernel template and launch protocol as the other layer counts below
-        const int hp = nl_hp(p);
-        const Layout y = make_layout(p);
-        KArgs a;
-        fill_kargs(p, y, &a);
+    } else {
         a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
-        if (discrete) { a.stages = const_cast<float*>(z_out); a.discrete = 1; }
-        else a.z_out = z_out;
+        if (pass == 2) { a.stages = const_cast<float*>(src); a.discrete = 1; }
+        else a.z_out = src;
         a.gpart = (float*)ws;
-        a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, discrete ? 2 : 1) - fault_bytes(y)) : nullptr;
-        for (int pass_hp : {hp, 0}) {      // main launch, then (hp = 2) the split-bf16 instance on range-faulted tiles only
-            NcdeFastCKernel fn = c_adj(p->channels, p->n_layers, p->interp, p->method, pass_hp, discrete);
-            const size_t lds = c_adj_lds(p->channels, p->n_layers, p->interp, pass_hp);
-            if (!fn || ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-            hipLaunchKernelGGL(fn, dim3(y.n_wg), dim3(512), lds, st, a);
-            if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-            if (hp == 0) break;
-            a.only_faulted = 1;
-        }
-        if (main_kernel_only) return NCDE_OK;
-        return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
     }
-    const FastEntry* e = find_entry(p);
-    if (p->output == NCDE_OUT_TIMES) {      // general time axis: the PLAN = 1 instances of the same kernel template, same launch protocol
-        if (discrete || !planned_ok(p, e, 1)) return NCDE_ERR_UNSUPPORTED;
-        const int hp = (p->flags & NCDE_FLAG_SPLIT_BF16) ? 0 : 2;
-        const Layout y = make_layout(p);
-        KArgs a;
-        fill_kargs(p, y, &a);
-        a.grad_out = grad_out; a.grad_z0 = g->grad_z0; a.z_out = z_out;
-        a.gpart = (float*)ws;
-        a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, 1) - fault_bytes(y)) : nullptr;
-        for (int pass_hp : {hp, 0}) {
-            NcdeFastPlanKernel fn = ncde_fast_plan_adj3(p->n_layers, p->interp, p->method, pass_hp);
-            const size_t lds = ncde_fast_plan_adj3_lds(p->n_layers, p->interp, p->method, pass_hp);
-            if (!fn || ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-            hipLaunchKernelGGL(fn, dim3(y.n_wg), dim3(512), lds, st, a);
-            if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-            if (hp == 0) break;
-            a.only_faulted = 1;
-        }
-        if (main_kernel_only) return NCDE_OK;
-        return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
-    }
-    if (use_nl(p, e, discrete ? 2 : 1)) {      // another layer count of the same kernel template: same launch protocol as below
-        const int hp = nl_hp(p);
-        const Layout y = make_layout(p);
-        KArgs a;
-        fill_kargs(p, y, &a);
-        a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
-        if (discrete) { a.stages = const_cast<float*>(z_out); a.discrete = 1; }
-        else a.z_out = z_out;
-        a.gpart = (float*)ws;
-        a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, discrete ? 2 : 1) - fault_bytes(y)) : nullptr;
-        for (int pass_hp : {hp, 0}) {      // main launch, then (hp = 2) the split-bf16 instance on range-faulted tiles only
-            NcdeFastNlKernel fn = ncde_fast_adj3_nl(p->n_layers, p->interp, p->method, pass_hp, discrete);
-            const size_t lds = ncde_fast_adj3_nl_lds(p->n_layers, p->interp, pass_hp);
-            if (!fn || ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-            hipLaunchKernelGGL(fn, dim3(y.n_wg), dim3(512), lds, st, a);
-            if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-            if (hp == 0) break;
-            a.only_faulted = 1;
-        }
-        if (main_kernel_only) return NCDE_OK;
-        return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
-    }
-    const bool v1 = !discrete && ((p->flags & NCDE_FLAG_ADJOINT_V1) != 0 || (e->adj2 == nullptr && e->adj3 == nullptr));
-    const bool v3 = discrete || (!v1 && e->adj3 != nullptr && !(p->flags & NCDE_FLAG_ADJOINT_V2));
-    const bool v2 = !v1 && !v3;
-    // hp = the kernel's HP: 2 (default) forward-side GEMMs of the chain waves split-fp16, 0 (NCDE_FLAG_SPLIT_BF16) all split-bf16,
-    // 1 (NCDE_FLAG_ADJOINT_SPLIT_FP16, experimental: DESIGN.md section 5.4c) everything split-fp16
-    const int hp = (!v3 || (p->flags & (NCDE_FLAG_SPLIT_BF16 | 0x200u))) ? 0
-                   : ((NCDE_ADJ3_HP1_AVAILABLE != 0 && (p->flags & NCDE_FLAG_ADJOINT_SPLIT_FP16)) ? 1 : 2);
-    FwdFn fn = discrete ? e->adj3_disc(p->interp, p->method, hp)
-                        : (v1 ? e->adj(p->interp, p->method) : (v3 ? e->adj3(p->interp, p->method, hp) : e->adj2(p->interp, p->method)));
-    if (!fn) return NCDE_ERR_UNSUPPORTED;
-    if (discrete && (p->flags & (NCDE_FLAG_DEBUG_PROFILE | 0x200u))) return NCDE_ERR_UNSUPPORTED;
-    const Layout y = make_layout(p);
-    KArgs a;
-    fill_kargs(p, y, &a);
-    a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
-    if (discrete) { a.stages = const_cast<float*>(z_out); a.discrete = 1; }
-    else a.z_out = z_out;
-    a.gpart = (float*)ws;
-    if (use_v4(p, e, discrete)) {
-        const bool prof = (p->flags & NCDE_FLAG_DEBUG_PROFILE) != 0;
-        NcdeFast4Kernel k4 = ncde_fast4_pick(p->n_layers, p->channels, p->interp, p->method, discrete, prof);
-        if (prof) a.out = (float*)ws + (size_t)y.n_wg * y.theta_size + 64;
-        const size_t lds4 = ncde_fast4_lds_bytes(p->n_layers, p->channels, p->interp);
-        if (ncde_lds_optin((const void*)k4, lds4) != hipSuccess) return NCDE_ERR_HIP;
-        hipLaunchKernelGGL(k4, dim3(y.n_wg), dim3(512), lds4, st, a);
+    if (P.fault_off >= 0) a.fault = reinterpret_cast<int*>(static_cast<char*>(ws) + P.fault_off);
+    if (P.tail_off >= 0) (pass == 0 ? a.gpart : a.out) = reinterpret_cast<float*>(static_cast<char*>(ws) + P.tail_off);
+    for (const FastLaunch* l : {&P.main, &P.redo}) {
+        if (!l->fn) break;
+        if (l->lds && ncde_lds_optin((const void*)l->fn, l->lds) != hipSuccess) return NCDE_ERR_HIP;
+        hipLaunchKernelGGL(l->fn, dim3(P.grid), dim3(l->block), l->lds, st, a);
         if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-        if (main_kernel_only) return NCDE_OK;
-        return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
-    }
-    if (p->flags & 0x200u) {  // development: per-stage chain values of workgroup 0 -> tail of the workspace
-        if (!(e->shape.H == 32 && e->shape.C == 20 && p->interp == NCDE_INTERP_CUBIC && p->method == NCDE_MIDPOINT)) return NCDE_ERR_UNSUPPORTED;
-        fn = !v1 ? ncde_adj_fast2<32, 32, 20, 3, NCDE_INTERP_CUBIC, NCDE_MIDPOINT, 2> : ncde_adj_fast<32, 32, 20, 3, 4, NCDE_INTERP_CUBIC, NCDE_MIDPOINT, 2>;
-        a.out = (float*)ws + (size_t)y.n_wg * y.theta_size + 64;
-    }
-    if (p->flags & NCDE_FLAG_DEBUG_PROFILE) {  // phase-cycle counters -> tail of the workspace [n_wg][NW][6] u64
-        if (!(e->shape.H == 32 && e->shape.C == 20 && p->interp == NCDE_INTERP_LINEAR && p->method == NCDE_RK4_38)) return NCDE_ERR_UNSUPPORTED;
-        fn = v3 ? (hp == 2 ? ncde_adj_fast3<3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0, 2>
-                           : (hp == 1 ? NCDE_ADJ3_HP1(3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0) : ncde_adj_fast3<3, 20, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>))
-                : (v2 ? ncde_adj_fast2<32, 32, 20, 3, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1> : ncde_adj_fast<32, 32, 20, 3, 4, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1>);
-        a.out = (float*)ws + (size_t)y.n_wg * y.theta_size + 64;
-    }
-    const size_t lds = v1 ? e->adj_lds(p->interp) : (v3 ? e->adj3_lds(p->interp, hp) : e->adj2_lds(p->interp));
-    if (ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-    a.fault = hp ? reinterpret_cast<int*>(static_cast<char*>(ws) + ncde_fast_workspace_bytes(p, discrete ? 2 : 1) - fault_bytes(y)) : nullptr;
-    hipLaunchKernelGGL(fn, dim3(y.n_wg), dim3(v1 ? 64 * e->nw : 512), lds, st, a);
-    if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-    if (hp && !(p->flags & NCDE_FLAG_DEBUG_PROFILE)) {  // re-execution of range-faulted tiles in split-bf16 (normally none: every workgroup exits at once)
-        FwdFn fx = discrete ? e->adj3_disc(p->interp, p->method, 0) : e->adj3(p->interp, p->method, 0);
-        const size_t ldx = e->adj3_lds(p->interp, 0);
-        if (ncde_lds_optin((const void*)fx, ldx) != hipSuccess) return NCDE_ERR_HIP;
         a.only_faulted = 1;
-        hipLaunchKernelGGL(fx, dim3(y.n_wg), dim3(512), ldx, st, a);
-        if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
     }
-    if (main_kernel_only) return NCDE_OK;
-    return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
+    if (!P.reduce || main_kernel_only) return NCDE_OK;
+    return launch_reduce_partials(p, y, g, (const float*)ws, P.grid, st);
 }
 
 #endif  // NCDE_FAST_KERNELS_ONLY

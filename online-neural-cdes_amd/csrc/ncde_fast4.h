@@ -4,7 +4,6 @@
 
 #include "ncde_common.h"
 
-typedef void (*NcdeFast4Kernel)(KArgs);
 // kernel for (n_layers, channels) at H = HH = 32, or nullptr when that shape is not instantiated
-NcdeFast4Kernel ncde_fast4_pick(int n_layers, int channels, int interp, int method, bool discrete, bool profile);
+NcdeKernel ncde_fast4_pick(int n_layers, int channels, int interp, int method, bool discrete, bool profile);
 size_t ncde_fast4_lds_bytes(int n_layers, int channels, int interp);

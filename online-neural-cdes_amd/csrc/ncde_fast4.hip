@@ -774,7 +774,7 @@ __global__ __launch_bounds__(512, F4_LB) void ncde_adj_fast4(KArgs a) {
 }
 
 template <int NL, int C>
-NcdeFast4Kernel pick4(int interp, int method, bool disc, bool prof) {
+NcdeKernel pick4(int interp, int method, bool disc, bool prof) {
     if (prof) {
         if (interp == NCDE_INTERP_LINEAR && method == NCDE_RK4_38 && !disc) return ncde_adj_fast4<NL, C, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0>;
         return nullptr;
@@ -793,7 +793,7 @@ NcdeFast4Kernel pick4(int interp, int method, bool disc, bool prof) {
 
 }  // namespace
 
-NcdeFast4Kernel ncde_fast4_pick(int n_layers, int channels, int interp, int method, bool discrete, bool profile) {
+NcdeKernel ncde_fast4_pick(int n_layers, int channels, int interp, int method, bool discrete, bool profile) {
     if (n_layers == 3 && channels == 20) return pick4<3, 20>(interp, method, discrete, profile);
     return nullptr;
 }

@@ -785,21 +785,19 @@ __global__ __launch_bounds__(256, 1) void ncde_adj_h64(KArgs a) {
     }
 }
 
-using F64Fn = void (*)(KArgs);
-
 template <int NS, int HPF, int DISC>
-F64Fn pick_method(int method) {
+NcdeKernel pick_method(int method) {
     if (method == NCDE_RK4_38) return ncde_adj_h64<NCDE_RK4_38, NS, HPF, DISC>;
     if (method == NCDE_MIDPOINT) return ncde_adj_h64<NCDE_MIDPOINT, NS, HPF, DISC>;
     return ncde_adj_h64<NCDE_EULER, NS, HPF, DISC>;
 }
 template <int HPF>
-F64Fn pick_planned(int method) {      // general time axis: one sample tile per workgroup, continuous adjoint
+NcdeKernel pick_planned(int method) {      // general time axis: one sample tile per workgroup, continuous adjoint
     if (method == NCDE_RK4_38) return ncde_adj_h64<NCDE_RK4_38, 1, HPF, 0, 1>;
     if (method == NCDE_MIDPOINT) return ncde_adj_h64<NCDE_MIDPOINT, 1, HPF, 0, 1>;
     return ncde_adj_h64<NCDE_EULER, 1, HPF, 0, 1>;
 }
-F64Fn pick_kernel(int method, int ns, int hpf, bool disc) {
+NcdeKernel pick_kernel(int method, int ns, int hpf, bool disc) {
     if (disc) {
         if (ns == 2) return hpf == 1 ? pick_method<2, 1, 1>(method) : pick_method<2, 2, 1>(method);
         return hpf == 1 ? pick_method<1, 1, 1>(method) : pick_method<1, 2, 1>(method);
@@ -823,11 +821,7 @@ int f64_ns(const NcdeProblem* p) {
     return ns;
 }
 int f64_hpf(const NcdeProblem* p) { return (p->flags & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_SPLIT_BF16)) ? 2 : 1; }
-int64_t f64_fault_bytes(int n_wg) { return ((int64_t)n_wg * 4 + 255) & ~(int64_t)255; }
-
-}  // namespace
-
-bool ncde_fast64_supported(const NcdeProblem* p, int pass) {
+bool f64_supported(const NcdeProblem* p, int pass) {
     if (pass != 1 && pass != 2) return false;
     if (p->hidden != 64 || p->channels > 4 || p->n_layers < 1 || p->n_layers > kF64MaxLayers) return false;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL) return false;
@@ -841,49 +835,27 @@ bool ncde_fast64_supported(const NcdeProblem* p, int pass) {
     return f64_lds_bytes(p, 1) <= (size_t)kLdsLimit;
 }
 
-const char* ncde_fast64_kernel_name(const NcdeProblem* p, int pass) {
-    if (!ncde_fast64_supported(p, pass)) return nullptr;
-    const int ns = f64_ns(p), hpf = f64_hpf(p);
-    if (pass == 2) return hpf == 1 ? (ns == 2 ? "ncde_adj_h64<H64,HH64,NS2,in-sweep,fwd-side fp16x2 + fp32,discrete>" : "ncde_adj_h64<H64,HH64,NS1,in-sweep,fwd-side fp16x2 + fp32,discrete>")
-                                   : (ns == 2 ? "ncde_adj_h64<H64,HH64,NS2,in-sweep,fp32,discrete>" : "ncde_adj_h64<H64,HH64,NS1,in-sweep,fp32,discrete>");
-    return hpf == 1 ? (ns == 2 ? "ncde_adj_h64<H64,HH64,NS2,in-sweep,fwd-side fp16x2 + fp32>" : "ncde_adj_h64<H64,HH64,NS1,in-sweep,fwd-side fp16x2 + fp32>")
-                    : (ns == 2 ? "ncde_adj_h64<H64,HH64,NS2,in-sweep,fp32>" : "ncde_adj_h64<H64,HH64,NS1,in-sweep,fp32>");
-}
+#define NCDE_F64_NAME(NS, ARITH, SUFFIX) "ncde_adj_h64<H64,HH64,NS" #NS ",in-sweep," ARITH SUFFIX ">"
+#define NCDE_F64_NAMES(SUFFIX) \
+    {{NCDE_F64_NAME(1, "fwd-side fp16x2 + fp32", SUFFIX), NCDE_F64_NAME(2, "fwd-side fp16x2 + fp32", SUFFIX)}, {NCDE_F64_NAME(1, "fp32", SUFFIX), NCDE_F64_NAME(2, "fp32", SUFFIX)}}
+const char* const kF64Names[2][2][2] = {NCDE_F64_NAMES(""), NCDE_F64_NAMES(",discrete")};      // [discrete][HPF - 1][NS - 1]
 
-int64_t ncde_fast64_workspace_bytes(const NcdeProblem* p, int pass) {
-    if (!ncde_fast64_supported(p, pass)) return NCDE_ERR_UNSUPPORTED;
-    const Layout y = make_layout(p);
-    const int n_wg = (p->batch + 16 * f64_ns(p) - 1) / (16 * f64_ns(p));
-    return (int64_t)sizeof(float) * (int64_t)n_wg * (int64_t)y.theta_size + 256 + f64_fault_bytes(n_wg);
-}
+}  // namespace
 
-int ncde_fast64_adjoint(const NcdeProblem* p, const float* src, const float* grad_out, const NcdeGrads* g, void* ws, size_t ws_bytes,
-                        hipStream_t st, bool main_kernel_only, bool discrete) {
-    if (!ncde_fast64_supported(p, discrete ? 2 : 1)) return NCDE_ERR_UNSUPPORTED;
-    if ((int64_t)ws_bytes < ncde_fast64_workspace_bytes(p, discrete ? 2 : 1)) return NCDE_ERR_WORKSPACE;
-    const Layout y = make_layout(p);
+bool ncde_fast64_plan(const NcdeProblem* p, int pass, const Layout& y, FastPlan* P) {
+    if (!f64_supported(p, pass)) return false;
     const int ns = f64_ns(p), hpf = f64_hpf(p);
-    const int n_wg = (p->batch + 16 * ns - 1) / (16 * ns);
-    KArgs a;
-    fill_kargs(p, y, &a);
-    a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
-    if (discrete) { a.stages = const_cast<float*>(src); a.discrete = 1; }
-    else a.z_out = src;
-    a.gpart = (float*)ws;
-    a.fault = hpf == 1 ? reinterpret_cast<int*>(static_cast<char*>(ws) + sizeof(float) * (size_t)n_wg * y.theta_size + 256) : nullptr;
+    const bool discrete = pass == 2, planned = p->output == NCDE_OUT_TIMES;
     const size_t lds = f64_lds_bytes(p, ns);
-    const bool planned = p->output == NCDE_OUT_TIMES;
-    F64Fn fn = planned ? (hpf == 1 ? pick_planned<1>(p->method) : pick_planned<2>(p->method)) : pick_kernel(p->method, ns, hpf, discrete);
-    if (ncde_lds_optin((const void*)fn, lds) != hipSuccess) return NCDE_ERR_HIP;
-    hipLaunchKernelGGL(fn, dim3(n_wg), dim3(256), lds, st, a);
-    if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-    if (hpf == 1) {      // re-execution of range-faulted workgroups with fp32-input MFMA (normally none: every workgroup exits at once)
-        F64Fn fx = planned ? pick_planned<2>(p->method) : pick_kernel(p->method, ns, 2, discrete);
-        if (ncde_lds_optin((const void*)fx, lds) != hipSuccess) return NCDE_ERR_HIP;
-        a.only_faulted = 1;
-        hipLaunchKernelGGL(fx, dim3(n_wg), dim3(256), lds, st, a);
-        if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
-    }
-    if (main_kernel_only) return NCDE_OK;
-    return launch_reduce_partials(p, y, g, (const float*)ws, n_wg, st);
+    auto pick = [&](int h) { return planned ? (h == 1 ? pick_planned<1>(p->method) : pick_planned<2>(p->method)) : pick_kernel(p->method, ns, h, discrete); };
+    P->ok = true;
+    P->name = kF64Names[discrete][hpf - 1][ns - 1];
+    P->grid = (p->batch + 16 * ns - 1) / (16 * ns);
+    P->main = {pick(hpf), 256, lds};
+    // re-execution of range-faulted workgroups with fp32-input MFMA (normally none: every workgroup exits at once)
+    P->redo = {hpf == 1 ? pick(2) : nullptr, 256, lds};
+    ncde_fast_plan_workspace(P, (int64_t)sizeof(float) * (int64_t)P->grid * (int64_t)y.theta_size + 256, hpf == 1);
+    P->tail_off = -1;
+    P->reduce = true;
+    return true;
 }

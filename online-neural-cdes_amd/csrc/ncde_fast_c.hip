@@ -13,7 +13,7 @@
 // (still inside the anonymous namespace ncde_fast.hip opened; its closing brace sits in the part left out)
 constexpr int FC = NCDE_FAST_C;
 template <int HP>
-NcdeFastCKernel c_fwd_pick(int interp, int method) {
+NcdeKernel c_fwd_pick(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_fwd_fast_bf3<32, 32, FC, 4, I, M, 0, 0, HP>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -26,7 +26,7 @@ NcdeFastCKernel c_fwd_pick(int interp, int method) {
     return nullptr;
 }
 template <int NL, int DISC>
-NcdeFastCKernel c_adj_pick(int interp, int method, int hp) {
+NcdeKernel c_adj_pick(int interp, int method, int hp) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return hp == 2 ? ncde_adj_fast3<NL, FC, I, M, 0, DISC, 2> : ncde_adj_fast3<NL, FC, I, M, 0, DISC, 0>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -44,7 +44,7 @@ NcdeFastCKernel c_adj_pick(int interp, int method, int hp) {
 #define NCDE_CAT(a, b, c) NCDE_CAT_(a, b, c)
 #define NCDE_CFN(name) NCDE_CAT(ncde_fast_c, NCDE_FAST_C, name)
 
-NcdeFastCKernel NCDE_CFN(_fwd)(int interp, int method, int hp) { return hp ? c_fwd_pick<1>(interp, method) : c_fwd_pick<0>(interp, method); }
+NcdeKernel NCDE_CFN(_fwd)(int interp, int method, int hp) { return hp ? c_fwd_pick<1>(interp, method) : c_fwd_pick<0>(interp, method); }
 size_t NCDE_CFN(_adj_lds)(int n_layers, int interp, int hp) {
     switch (n_layers) {
         case 1: return adj3_lds_bytes<1, FC>(interp, hp);
@@ -54,7 +54,7 @@ size_t NCDE_CFN(_adj_lds)(int n_layers, int interp, int hp) {
         default: return (size_t)-1;
     }
 }
-NcdeFastCKernel NCDE_CFN(_adj)(int n_layers, int interp, int method, int hp, bool discrete) {
+NcdeKernel NCDE_CFN(_adj)(int n_layers, int interp, int method, int hp, bool discrete) {
     if (hp != 0 && hp != 2) return nullptr;
     if (NCDE_CFN(_adj_lds)(n_layers, interp, hp) > (size_t)kLdsLimit) return nullptr;
     switch (n_layers) {

@@ -6,6 +6,5 @@
 #pragma once
 #include "ncde_common.h"
 
-typedef void (*NcdeFastFwd3Kernel)(KArgs);
 // hidden = 32: the (32, 32, 20) set, 64: the (64, 64, 4) set; hp = 1: split-fp16 (default), 0: split-bf16; nullptr for anything else
-NcdeFastFwd3Kernel ncde_fast_fwd3(int hidden, int interp, int method, int hp);
+NcdeKernel ncde_fast_fwd3(int hidden, int interp, int method, int hp);

@@ -6,7 +6,7 @@
 
 // (still inside the anonymous namespace ncde_fast.hip opened; its closing brace sits in the part left out)
 template <int H, int HH, int C, int HP>
-NcdeFastFwd3Kernel fwd3_pick(int interp, int method) {
+NcdeKernel fwd3_pick(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_fwd_fast_bf3<H, HH, C, 4, I, M, 0, 3, HP>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -20,7 +20,7 @@ NcdeFastFwd3Kernel fwd3_pick(int interp, int method) {
 }
 }  // namespace
 
-NcdeFastFwd3Kernel ncde_fast_fwd3(int hidden, int interp, int method, int hp) {
+NcdeKernel ncde_fast_fwd3(int hidden, int interp, int method, int hp) {
     if (hidden == 32) return hp ? fwd3_pick<32, 32, 20, 1>(interp, method) : fwd3_pick<32, 32, 20, 0>(interp, method);
     if (hidden == 64) return hp ? fwd3_pick<64, 64, 4, 1>(interp, method) : fwd3_pick<64, 64, 4, 0>(interp, method);
     return nullptr;

@@ -8,7 +8,7 @@
 
 // (still inside the anonymous namespace ncde_fast.hip opened; its closing brace sits in the part left out)
 template <int NL, int DISC>
-NcdeFastNlKernel nl_pick(int interp, int method, int hp) {
+NcdeKernel nl_pick(int interp, int method, int hp) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return hp == 2 ? ncde_adj_fast3<NL, 20, I, M, 0, DISC, 2> : ncde_adj_fast3<NL, 20, I, M, 0, DISC, 0>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -24,7 +24,7 @@ NcdeFastNlKernel nl_pick(int interp, int method, int hp) {
 }
 }  // namespace
 
-NcdeFastNlKernel ncde_fast_adj3_nl(int n_layers, int interp, int method, int hp, bool discrete) {
+NcdeKernel ncde_fast_adj3_nl(int n_layers, int interp, int method, int hp, bool discrete) {
     if (hp != 0 && hp != 2) return nullptr;
     if (ncde_fast_adj3_nl_lds(n_layers, interp, hp) > (size_t)kLdsLimit) return nullptr;
     switch (n_layers) {
@@ -41,15 +41,4 @@ size_t ncde_fast_adj3_nl_lds(int n_layers, int interp, int hp) {
         case 4: return adj3_lds_bytes<4, 20>(interp, hp);
         default: return (size_t)-1;
     }
-}
-const char* ncde_fast_adj3_nl_name(int n_layers, int hp, bool discrete) {
-    static const char* kNames[3][2][2] = {
-        {{"ncde_adj_fast3<H32,HH32,C20,NL1,chain+grad,bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL1,chain+grad,bf16x3,discrete>"},
-         {"ncde_adj_fast3<H32,HH32,C20,NL1,chain+grad,fwd-side fp16x2 + bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL1,chain+grad,fwd-side fp16x2 + bf16x3,discrete>"}},
-        {{"ncde_adj_fast3<H32,HH32,C20,NL2,chain+grad,bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL2,chain+grad,bf16x3,discrete>"},
-         {"ncde_adj_fast3<H32,HH32,C20,NL2,chain+grad,fwd-side fp16x2 + bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL2,chain+grad,fwd-side fp16x2 + bf16x3,discrete>"}},
-        {{"ncde_adj_fast3<H32,HH32,C20,NL4,chain+grad,bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL4,chain+grad,bf16x3,discrete>"},
-         {"ncde_adj_fast3<H32,HH32,C20,NL4,chain+grad,fwd-side fp16x2 + bf16x3>", "ncde_adj_fast3<H32,HH32,C20,NL4,chain+grad,fwd-side fp16x2 + bf16x3,discrete>"}}};
-    const int i = n_layers == 1 ? 0 : (n_layers == 2 ? 1 : 2);
-    return kNames[i][hp == 2 ? 1 : 0][discrete ? 1 : 0];
 }

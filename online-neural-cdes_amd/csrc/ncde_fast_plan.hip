@@ -8,7 +8,7 @@
 
 // (still inside the anonymous namespace ncde_fast.hip opened)
 template <int H, int HH, int C, int HP>
-NcdeFastPlanKernel plan_fwd_pick(int interp, int method) {
+NcdeKernel plan_fwd_pick(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_fwd_fast_bf3<H, HH, C, 4, I, M, 0, 0, HP, 1>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -21,7 +21,7 @@ NcdeFastPlanKernel plan_fwd_pick(int interp, int method) {
     return nullptr;
 }
 template <int HP>
-NcdeFastPlanKernel plan_adj3_pick(int interp, int method) {
+NcdeKernel plan_adj3_pick(int interp, int method) {
 #define NCDE_PICK(I, M) \
     if (interp == I && method == M) return ncde_adj_fast3<3, 20, I, M, 0, 0, HP, 1>;
     NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
@@ -35,7 +35,7 @@ NcdeFastPlanKernel plan_adj3_pick(int interp, int method) {
 }
 }  // namespace
 
-NcdeFastPlanKernel ncde_fast_plan_fwd(int shape, int interp, int method, int hp) {
+NcdeKernel ncde_fast_plan_fwd(int shape, int interp, int method, int hp) {
     if (shape == 0) return hp ? plan_fwd_pick<32, 32, 20, 1>(interp, method) : plan_fwd_pick<32, 32, 20, 0>(interp, method);
     if (shape == 1) return hp ? plan_fwd_pick<64, 64, 4, 1>(interp, method) : plan_fwd_pick<64, 64, 4, 0>(interp, method);
     return nullptr;
@@ -45,7 +45,7 @@ size_t ncde_fast_plan_adj3_lds(int n_layers, int interp, int method, int hp) {
     const int S = method == NCDE_RK4_38 ? 4 : (method == NCDE_MIDPOINT ? 2 : 1);
     return adj3_lds_bytes<3, 20>(interp, hp, S);
 }
-NcdeFastPlanKernel ncde_fast_plan_adj3(int n_layers, int interp, int method, int hp) {
+NcdeKernel ncde_fast_plan_adj3(int n_layers, int interp, int method, int hp) {
     if (n_layers != 3 || (hp != 0 && hp != 2)) return nullptr;
     if (ncde_fast_plan_adj3_lds(n_layers, interp, method, hp) > (size_t)kLdsLimit) return nullptr;
     return hp == 2 ? plan_adj3_pick<2>(interp, method) : plan_adj3_pick<0>(interp, method);

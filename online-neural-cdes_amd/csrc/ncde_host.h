@@ -1,4 +1,5 @@
-// Host-side helpers shared by ncde_abi.hip and ncde_fast.hip: parameter-gradient layout, K4 launch.
+// Host-side pieces shared by ncde_abi.hip and the kernel families: the internal chain-dump flag, the LDS opt-in, the parameter-gradient
+// Layout of a problem, the KArgs fields common to every family (fill_kargs) and the launch of the partials reduce (K4).
 #pragma once
 #include <mutex>
 #include <map>
@@ -19,6 +20,11 @@ struct ReduceSegs {
 extern "C" __global__ void ncde_reduce_partials(const float* gpart, int n_part, int theta_size, ReduceSegs segs);
 
 constexpr int kLdsLimit = 160 * 1024;
+
+// Internal flag (not in include/ncde_hip.h): the development adjoint kernels of the (32, 32, 20) set (ncde_adj_fast / ncde_adj_fast2,
+// cubic + midpoint only) also write the per-stage chain values of workgroup 0 to the tail of the workspace, and every split-GEMM
+// choice of that set falls back to split-bf16.  A problem that carries it is never zero-padded onto a kernel set.
+constexpr uint32_t kFlagChainDump = 0x200u;
 
 // Development switches are environment variables ONLY in builds with -DNCDE_DEV_KNOBS; the shipped library is stateless and
 // reads nothing but its arguments.

@@ -511,3 +511,22 @@ def test_time_plan_refuses_a_grid_it_cannot_index():
     X = ncde_amd.LinearInterpolation(torch.zeros(2, 5, 3))
     with pytest.raises((ValueError, AssertionError, ncde_amd._lib.NcdeError), match="more than a time plan can hold"):
         solver._time_plan(X, torch.tensor([0.0, 4.0]), "rk4", 1e-9, "cpu")
+
+
+def test_dispatch_table_matches_the_recorded_one():
+    """tests/golden/dispatch_table.json: rows of tools/dispatch_table.py's grid (every distinct kernel name and error text it produces),
+    recorded from the library as it was before the register-resident launchers and the ABI front end were rewritten around one plan /
+    one route per call.  Kernel name, workspace bytes, status-word offset and the error text of each failing query: every field of
+    every row."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("dispatch_table", os.path.join(ROOT, "tools", "dispatch_table.py"))
+    dt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dt)
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "dispatch_table.json")))
+    assert tuple(fx["keys"]) == dt.KEYS and len(fx["rows"]) > 1000
+    h = dt.load(_lib.LIB_PATH)
+    nk = len(fx["keys"])
+    for row in fx["rows"]:
+        case = dict(zip(fx["keys"], row[:nk]))
+        assert dt.query(h, case) == row[nk:], case
