@@ -317,6 +317,25 @@ int ncde_forward_record(const NcdeProblem* p, float* out, float* stages, void* w
 int ncde_backward(const NcdeProblem* p, const float* stages, const float* grad_out, const NcdeGrads* grads, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* ---- gradient of the control path: what adjoint=False + autograd hands to a coefficient tensor that requires grad (a stacked CDE
+ * feeds layer i's hidden sequence to layer i+1 as linear coefficients, src/ncde/stacked.py:7-131).  ncde_backward_control is
+ * ncde_backward that ALSO writes dL/dcoeffs: per recorded stage g[b, c] = sum_h cot[b, h] M[b, h, c] (M = tanh(Wo x_L + bo), cot = the
+ * stage cotangent the sweep already forms) is computed from the sweep's records by ncde_dctl_tiled -- fp32-input MFMA, one workgroup per
+ * stage and 16-sample tile -- and folded by ncde_dctl_fold onto the coefficient rows the stage read (linear: +-g / knot spacing into rows
+ * idx + 1 / idx;  cubic: g, g frac, g frac^2 into b, 2c, 3d).  No float atomics: grad_coeffs is bit-reproducible.
+ *   stages      the record of ncde_forward_record (its layout does not depend on the kernel family: the forward keeps its usual route)
+ *   grad_coeffs dense, shaped like the coefficients ([B, T, C] linear, [B, T-1, 4C] cubic), fully written
+ *   grads       receives what ncde_backward writes
+ * The call always runs the batch-tiled family's per-workgroup kernels over fp32 records, zero-padded like any shape -- exactly
+ * ncde_backward with flags = NCDE_FLAG_FORCE_TILED | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_NO_COOP (of the caller's flags only
+ * NCDE_FLAG_TILED_WINDOW_STEPS(n) is kept), then pass C per time window.  Supported: original field, matmul input, NCDE_INTERP_LINEAR /
+ * _CUBIC, every method / output mode / time plan.  Gated fields, evaluate / derivative inputs, the quintic kind and shapes beyond the
+ * batch-tiled backward answer NCDE_ERR_UNSUPPORTED. */
+int64_t ncde_control_workspace_bytes(const NcdeProblem* p);   /* < 0: status code */
+const char* ncde_control_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_backward_control(const NcdeProblem* p, const float* stages, const float* grad_out, const NcdeGrads* grads, float* grad_coeffs,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Timing helper for benchmarks: runs `iters` back-to-back launches of the dominant kernel of the given
  * pass on `stream`, bracketed by HIP events on that same stream, and returns the mean milliseconds per
  * launch in *ms_per_launch (this call DOES synchronise).  pass = 1: `out` is z_out; pass = 2: `out` is the stage record. */

@@ -122,6 +122,7 @@ EXPORTS = (
     "ncde_time_plan_build", "ncde_dopri5_workspace_bytes", "ncde_dopri5_forward", "ncde_dopri5_adjoint",
     "ncde_dopri5_record_bytes", "ncde_dopri5_forward_record", "ncde_dopri5_backward", "ncde_dopri5_kernel_name",
     "ncde_coop_status_offset",
+    "ncde_control_workspace_bytes", "ncde_control_kernel_name", "ncde_backward_control",
 )
 
 _LIB = None
@@ -183,6 +184,12 @@ def lib():
     h.ncde_forward_record.restype = ctypes.c_int
     h.ncde_backward.argtypes = [P, vp, vp, G, vp, sz, vp]
     h.ncde_backward.restype = ctypes.c_int
+    h.ncde_control_workspace_bytes.argtypes = [P]
+    h.ncde_control_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_control_kernel_name.argtypes = [P]
+    h.ncde_control_kernel_name.restype = ctypes.c_char_p
+    h.ncde_backward_control.argtypes = [P, vp, vp, G, vp, vp, sz, vp]
+    h.ncde_backward_control.restype = ctypes.c_int
     i32 = ctypes.c_int
     h.ncde_prepare_workspace_bytes.argtypes = [i32, i32, i32, i32]
     h.ncde_prepare_workspace_bytes.restype = ctypes.c_int64

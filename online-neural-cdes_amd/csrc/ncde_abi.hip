@@ -423,8 +423,9 @@ int launch_forward(Call& c, float* out, float* stages, void* ws, size_t ws_bytes
 }
 
 // discrete = false: continuous adjoint, `src` = z_out; discrete = true: exact backward, `src` = the stage record
+// grad_coeffs != NULL (ncde_backward_control: the route is the batch-tiled family, as it is or zero-padded): also dL/dcoeffs
 int launch_adjoint(Call& c, const float* src, const float* grad_out, const NcdeGrads* g, void* ws, size_t ws_bytes, hipStream_t st,
-                   bool main_kernel_only, bool discrete) {
+                   bool main_kernel_only, bool discrete, float* grad_coeffs = nullptr) {
     const NcdeProblem* p = &c.q;
     const Layout& y = c.y;
     const int pass = discrete ? 2 : 1;
@@ -452,7 +453,7 @@ int launch_adjoint(Call& c, const float* src, const float* grad_out, const NcdeG
             }
             const size_t inner_bytes = ws_bytes - sizeof(float) * (size_t)head;
             const int rc = P.inner == Family::Fast ? ncde_fast_launch(&P.q, pass, nullptr, nullptr, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only)
-                                                   : ncde_tiled_adjoint(&P.q, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only, discrete);
+                                                   : ncde_tiled_adjoint(&P.q, src, grad_out, &gq, base + head, inner_bytes, st, main_kernel_only, discrete, grad_coeffs);
             if (rc != NCDE_OK) return fail(rc, "adjoint (zero-padded problem) launch failed");
             if (main_kernel_only) return NCDE_OK;
             const int rc2 = pad_launch(P, gbase, 1, real_dst, st);
@@ -469,7 +470,7 @@ int launch_adjoint(Call& c, const float* src, const float* grad_out, const NcdeG
             return rc == NCDE_OK ? NCDE_OK : fail(rc, "variant adjoint launch failed");
         }
         case Family::Tiled: {
-            const int rc = ncde_tiled_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete);
+            const int rc = ncde_tiled_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete, grad_coeffs);
             if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
             return rc == NCDE_OK ? NCDE_OK : fail(rc, "tiled adjoint launch failed");
         }
@@ -502,6 +503,37 @@ int begin_call(const NcdeProblem* in, int pass, Call* c, ArgsOk&& args_ok) {
     return select_route(&c->q, c->y, pass, &c->route);
 }
 int no_args(const NcdeProblem&) { return NCDE_OK; }
+
+// ---- control-path gradients ----------------------------------------------------------------------------------------------------------
+// The front end of the ncde_control_* queries and of ncde_backward_control: the exact discrete backward on the batch-tiled family's
+// per-workgroup kernels over fp32 records -- whatever the shape would select otherwise -- as it is or zero-padded.  Of the caller's
+// flags only NCDE_FLAG_TILED_WINDOW_STEPS(n) is kept.
+constexpr uint32_t kControlFlags = NCDE_FLAG_FORCE_TILED | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_NO_COOP;
+template <class ArgsOk>
+int begin_control(const NcdeProblem* in, Call* c, ArgsOk&& args_ok) {
+    int rc = normalize(in, &c->q);
+    if (rc != NCDE_OK) return rc;
+    NcdeProblem& q = c->q;
+    rc = validate(&q);
+    if (rc != NCDE_OK) return rc;
+    rc = args_ok(q);
+    if (rc != NCDE_OK) return rc;
+    if (q.field_kind != NCDE_FIELD_ORIGINAL || q.field_input != NCDE_INPUT_MATMUL)
+        return fail(NCDE_ERR_UNSUPPORTED, "control-path gradients: the original vector field with the matmul input only (field_kind %d, field_input %d)", q.field_kind, q.field_input);
+    if (q.interp == NCDE_INTERP_QUINTIC) return fail(NCDE_ERR_UNSUPPORTED, "control-path gradients: linear and cubic controls only (piecewise-quintic: not implemented)");
+    q.flags = (q.flags & NCDE_FLAG_TILED_WINDOW_STEPS(0xFF)) | kControlFlags;
+    c->y = make_layout(&q);
+    c->route.family = Family::Tiled;
+    if (ncde_tiled_control_workspace_bytes(&q) >= 0) return NCDE_OK;
+    c->route.family = Family::Padded;
+    c->route.pad = make_pad_plan(&q, 2, nullptr);
+    if (c->route.pad.ok && ncde_tiled_control_workspace_bytes(&c->route.pad.q) >= 0) return NCDE_OK;
+    return fail(NCDE_ERR_UNSUPPORTED, "control-path gradients: hidden=%d, channels=%d, %d layers is beyond the batch-tiled backward", q.hidden, q.channels, q.n_layers);
+}
+int64_t control_workspace_bytes(const Call& c) {
+    if (c.route.family == Family::Tiled) return ncde_tiled_control_workspace_bytes(&c.q);
+    return ncde_tiled_control_workspace_bytes(&c.route.pad.q) + (int64_t)sizeof(float) * pad_head_floats(c.route.pad, 2);
+}
 int pass_in_range(int pass) { return pass < 0 || pass > 2 ? fail(NCDE_ERR_INVALID, "pass %d outside {0, 1, 2}", pass) : (int)NCDE_OK; }
 
 }  // namespace
@@ -703,6 +735,30 @@ int ncde_backward(const NcdeProblem* p, const float* stages, const float* grad_o
     });
     if (rc == NCDE_OK) rc = check_workspace(c, 2, workspace, workspace_bytes, true);
     return rc != NCDE_OK ? rc : launch_adjoint(c, stages, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, true);
+}
+
+int64_t ncde_control_workspace_bytes(const NcdeProblem* p) {
+    Call c;
+    const int rc = begin_control(p, &c, no_args);
+    return rc != NCDE_OK ? rc : control_workspace_bytes(c);
+}
+
+const char* ncde_control_kernel_name(const NcdeProblem* p) {
+    Call c;
+    if (begin_control(p, &c, no_args) != NCDE_OK) return nullptr;
+    return ncde_tiled_control_kernel_name(c.route.family == Family::Tiled ? &c.q : &c.route.pad.q);
+}
+
+int ncde_backward_control(const NcdeProblem* p, const float* stages, const float* grad_out, const NcdeGrads* grads, float* grad_coeffs,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    Call c;
+    const int rc = begin_control(p, &c, [&](const NcdeProblem&) {
+        return (stages && grad_out && grads && grads->grad_z0 && grad_coeffs) ? (int)NCDE_OK : fail(NCDE_ERR_INVALID, "NULL stages/grad_out/grads/grad_coeffs");
+    });
+    if (rc != NCDE_OK) return rc;
+    const int64_t need = control_workspace_bytes(c);
+    if (!workspace || (int64_t)workspace_bytes < need) return fail(NCDE_ERR_WORKSPACE, "workspace %zu B < %lld B", workspace_bytes, (long long)need);
+    return launch_adjoint(c, stages, grad_out, grads, workspace, workspace_bytes, (hipStream_t)stream, false, true, grad_coeffs);
 }
 
 int ncde_adjoint(const NcdeProblem* p, const float* z_out, const float* grad_out, const NcdeGrads* grads, void* workspace,

@@ -2921,6 +2921,102 @@ __global__ __launch_bounds__(256) void ncde_reduce_partials_if(const unsigned* r
 }
 
 // ------------------------------------------------------------------------------------------------
+// pass C: dL/d(dX/dt) of every recorded stage, folded onto the control path's coefficients (ncde_backward_control)
+// ------------------------------------------------------------------------------------------------
+// With f = M(z) dX/dt, M = tanh(Wo x_L + bo) viewed [H, C], the stage cotangent cot[h] (record C) sends
+//   g[b, c] = sum_h cot[b, h] M[b, h, c]
+// to the dX/dt the stage read.  ncde_dctl_tiled: one workgroup per (recorded stage, 16-sample tile) -- nothing here is serial in
+// time.  The tile's x_L (record A, fp32) stays in registers as the B operand; the four waves stream the packed row tiles of Wo
+// (wave w: state rows 4 hb .. 4 hb + 3 for hb = w, w + 4, ...), recompute P = Wo_tile x_L + bo with the fp32-input MFMA exactly as
+// ncde_dwo_tiled does, and contract tanh(P) with cot over h: per lane over its hb, then over the four h of a tile (lanes 16 apart),
+// then over the waves through LDS in a fixed order.  Zero rows of Wo / bo (padded state units and channels) give M = 0 exactly.
+// gdx[(sc * n_st + tile)][sample][c], c < C (the padded channel count).
+template <int PK>
+__global__ __launch_bounds__(256) void ncde_dctl_tiled(KArgs a, float* __restrict__ gdx) {
+    constexpr int CQB = 8;      // channel quads per barrier pair
+    __shared__ __attribute__((aligned(16))) float red[4][CQB][64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 15, lk = lane >> 4;
+    const int C = a.C, H = a.H, ncq = C >> 2, nhb = H >> 2, dlast = 16 * PK;
+    const long long t = blockIdx.x;      // = sc * n_st + sample tile: the record index
+    f32x4 xa[PK];
+    const float* ra = a.recA + t * (dlast * 16) + (lk * 16 + li) * 4;
+#pragma unroll
+    for (int i = 0; i < PK; ++i) xa[i] = *reinterpret_cast<const f32x4*>(ra + i * 256);
+    const float* rc = a.recC + t * (H * 16);
+    float* gt = gdx + t * (16 * C);
+    for (int cq0 = 0; cq0 < ncq; cq0 += CQB) {
+        const int ncb = ncq - cq0 < CQB ? ncq - cq0 : CQB;
+        for (int q = 0; q < ncb; ++q) {
+            const int cq = cq0 + q;
+            f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int hb = wave; hb < nhb; hb += 4) {
+                const Panel<PK> Wp = tl_load_panel_packed<PK>(a.Wo_pk + (long long)(hb * ncq + cq) * (PK * 256), lane);
+                f32x4 acc = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * C + 4 * cq);
+                const float cot = rc[(4 * hb + lk) * 16 + li];
+#pragma unroll
+                for (int i = 0; i < PK; ++i)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) acc = mfma16(Wp.v[i][e], xa[i][e], acc);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) g[r] += cot * tanh_dev(acc[r]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                g[r] += __shfl_xor(g[r], 16, 64);
+                g[r] += __shfl_xor(g[r], 32, 64);
+            }
+            if (lk == 0) *reinterpret_cast<f32x4*>(&red[wave][q][li * 4]) = g;
+        }
+        __syncthreads();
+        for (int e = tid; e < ncb * 64; e += 256) {
+            const int q = e >> 6, s = (e >> 2) & 15, r = e & 3;
+            gt[s * C + 4 * (cq0 + q) + r] = (red[0][q][e & 63] + red[1][q][e & 63]) + (red[2][q][e & 63] + red[3][q][e & 63]);
+        }
+        __syncthreads();
+    }
+}
+
+// ncde_dctl_fold: one thread per (sample, real channel) walks the window's stages in record order (newest first) and adds each g to
+// the coefficient rows that stage read -- linear: dX = (row[idx+1] - row[idx]) / kdt;  cubic: dX = b + (2c + 3d frac) frac, nothing into
+// a.  A thread owns its (b, c) column of grad_coeffs, the windows arrive in stream order: plain loads and stores, the same sums in the
+// same order every run.  grad_coeffs is dense ([B, T, Cc] / [B, T-1, 4 Cc]) and zero before the first window.
+__global__ __launch_bounds__(256) void ncde_dctl_fold(KArgs a, int n_st, const float* __restrict__ gdx, float* __restrict__ gc) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int C = a.C, Cc = a.Cc;
+    if (e >= (long long)a.B * Cc) return;
+    const int b = (int)(e / Cc), c = (int)(e - (long long)b * Cc);
+    const int S = n_stages(a.method);
+    const bool planned = a.plan != nullptr;
+    if (planned && !plan_header_ok(a, S)) return;
+    const int* pfwd = planned ? a.plan + plan_off_fwd() : nullptr;
+    const bool cubic = a.interp == NCDE_INTERP_CUBIC;
+    const long long row = cubic ? 4LL * Cc : Cc;
+    float* gb = gc + (long long)b * (cubic ? a.T - 1 : a.T) * row + c;
+    const float* gp = gdx + (long long)(b >> 4) * (16 * C) + (b & 15) * C + c;
+    const long long stage_stride = (long long)n_st * 16 * C;
+    int sc = 0;
+    for (int n = a.win_hi; n > a.win_lo; --n) {
+        for (int j = 0; j < S; ++j, ++sc) {      // the sweep's record order: forward stage S - 1 - j of forward step n - 1
+            const StageDesc sd = planned ? plan_stage(pfwd + (n - 1) * plan_step_words(S), S - 1 - j)
+                                         : default_stage(a.method, (float)(n - 1) + stage_offset(a.method, S - 1 - j), a.n_pieces);
+            const float g = gp[sc * stage_stride];
+            float* r = gb + (long long)sd.idx * row;
+            if (cubic) {
+                r[Cc] += g;
+                r[2 * Cc] += g * sd.frac;
+                r[3 * Cc] += (g * sd.frac) * sd.frac;
+            } else {
+                const float q = sd.kdt != 1.0f ? g / sd.kdt : g;
+                r[row] += q;
+                r[0] -= q;
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -3388,6 +3484,10 @@ const PassBFn kAdjPair[5][5] = {
     {nullptr, ncde_dwo_pair<2, 3, 1>, ncde_dwo_pair<4, 3, 1>, ncde_dwo_pair<8, 1, 1>},
     {nullptr, nullptr, nullptr, ncde_dwo_pair<8, 2, 1>}};
 
+// pass C (control-path gradients) over fp32 records
+using PassCFn = void (*)(KArgs, float*);
+const PassCFn kCtlStage[5] = {ncde_dctl_tiled<1>, ncde_dctl_tiled<2>, ncde_dctl_tiled<4>, ncde_dctl_tiled<8>, ncde_dctl_tiled<16>};
+
 // ---- forward plan: what ncde_tiled_forward launches, and its workspace [64 | packed output layer | split-bf16 copy | fault words | coop]
 constexpr int kFwdCoopLdsFloats = 2 * 2 * 2048 + 2 * 2 * 1280 + 2 * 2 * 64 + 2 * 8 * 64 + 8 * 16 + 64 + 320 + 4 * 4 * 256 + 8;      // = CBX .. CFL of ncde_fwd_tiled
 struct FwdPlan {
@@ -3530,7 +3630,10 @@ AdjSeq tiled_adj_seq(const NcdeProblem* p, const TiledAdjPlan& t, bool coop, boo
 // output-layer partials at gB.  The cooperative sequence takes one CHUNK of the batch at a time (all of it unless there are more sample
 // tiles than CUs), each chunk through all its windows, and ncde_dwo_h2 keeps adding to gB; the per-workgroup sequence takes the whole
 // batch as one chunk.
-int tiled_adj_run(const NcdeProblem* p, const TiledAdjPlan& t, const AdjSeq& s, const KArgs& a, int n_rsteps, float* gB, hipStream_t st) {
+// gdx / grad_coeffs (ncde_backward_control, per-workgroup sequence only): pass C behind pass B of every window -- ncde_dctl_tiled fills the
+// window buffer gdx from the records, ncde_dctl_fold adds it onto grad_coeffs.
+int tiled_adj_run(const NcdeProblem* p, const TiledAdjPlan& t, const AdjSeq& s, const KArgs& a, int n_rsteps, float* gB, hipStream_t st,
+                  float* gdx = nullptr, float* grad_coeffs = nullptr) {
     if (s.ldsB && ncde_lds_optin((const void*)s.fb, s.ldsB) != hipSuccess) return NCDE_ERR_HIP;
     if (ncde_lds_optin((const void*)s.fa, s.lds) != hipSuccess) return NCDE_ERR_HIP;
     const int chunk = s.coop ? t.coop.chunk : t.n_st;
@@ -3547,6 +3650,10 @@ int tiled_adj_run(const NcdeProblem* p, const TiledAdjPlan& t, const AdjSeq& s, 
             hipLaunchKernelGGL(s.fa, dim3(tiles), dim3(64 * s.nwv), s.lds, st, ac);
             hipLaunchKernelGGL(s.fb, s.gridB, dim3(s.threadsB), s.ldsB, st, ac, n_sc, tiles, gB);
             if (s.fb2) hipLaunchKernelGGL(s.fb2, s.gridB, dim3(s.threadsB), s.ldsB, st, ac, n_sc, tiles, gB + (long long)s.parts * t.theta_o);
+            if (grad_coeffs) {
+                hipLaunchKernelGGL(kCtlStage[tiled_pk_col(tiled_adj_pk(p))], dim3(n_sc * tiles), dim3(256), 0, st, ac, gdx);
+                hipLaunchKernelGGL(ncde_dctl_fold, dim3((int)(((long long)ac.B * ac.Cc + 255) / 256)), dim3(256), 0, st, ac, tiles, gdx, grad_coeffs);
+            }
             if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
         }
     }
@@ -3690,13 +3797,46 @@ int ncde_tiled_forward(const NcdeProblem* p, float* out, float* stages, void* ws
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
+// ---- control-path gradients: the exact discrete backward + pass C, on the per-workgroup kernels over fp32 records -----------------------
+// (p carries NCDE_FLAG_FP32_MFMA | NCDE_FLAG_NO_COOP: ncde_abi.hip sets them).  Workspace: the backward's own, then the window buffer
+// gdx [stages of a window][sample tiles][16][C].
+namespace {
+bool tiled_control_ok(const NcdeProblem* p) {
+    return ncde_tiled_supported(p, 2) && p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL &&
+           (p->interp == NCDE_INTERP_LINEAR || p->interp == NCDE_INTERP_CUBIC) && !tiled_adj_bf(p);
+}
+long long tiled_control_gdx_floats(const NcdeProblem* p, const TiledAdjPlan& t) { return (long long)t.n_sc * t.n_st * 16 * p->channels; }
+}  // namespace
+
+int64_t ncde_tiled_control_workspace_bytes(const NcdeProblem* p) {
+    if (!tiled_control_ok(p)) return NCDE_ERR_UNSUPPORTED;
+    const TiledAdjPlan t = tiled_adj_plan(p, make_layout(p));
+    if (t.coop.ok) return NCDE_ERR_UNSUPPORTED;
+    return (int64_t)sizeof(float) * (t.total + tiled_control_gdx_floats(p, t));
+}
+
+const char* ncde_tiled_control_kernel_name(const NcdeProblem* p) {
+    if (ncde_tiled_control_workspace_bytes(p) < 0) return nullptr;
+    return tiled_adj_bigh(p) ? "ncde_adj_tiled<wide,discrete>+ncde_dwo_tiled+ncde_dctl_tiled+ncde_dctl_fold"
+                             : "ncde_adj_tiled<discrete>+ncde_dwo_tiled+ncde_dctl_tiled+ncde_dctl_fold";
+}
+
 int ncde_tiled_adjoint(const NcdeProblem* p, const float* src, const float* grad_out, const NcdeGrads* g, void* ws, size_t ws_bytes,
-                       hipStream_t st, bool main_kernel_only, bool discrete) {
+                       hipStream_t st, bool main_kernel_only, bool discrete, float* grad_coeffs) {
     if (!ncde_tiled_supported(p, discrete ? 2 : 1)) return NCDE_ERR_UNSUPPORTED;
     const Layout y = make_layout(p);
     const TiledAdjPlan t = tiled_adj_plan(p, y);
     if (ws_bytes < sizeof(float) * (size_t)t.total) return NCDE_ERR_WORKSPACE;
     float* w = (float*)ws;
+    float* gdx = nullptr;
+    if (grad_coeffs) {      // ncde_backward_control
+        if (!discrete || main_kernel_only || !tiled_control_ok(p) || t.coop.ok) return NCDE_ERR_UNSUPPORTED;
+        if (ws_bytes < sizeof(float) * (size_t)(t.total + tiled_control_gdx_floats(p, t))) return NCDE_ERR_WORKSPACE;
+        gdx = w + t.total;
+        const size_t rows = p->interp == NCDE_INTERP_CUBIC ? 4 * (size_t)(p->n_knots - 1) : (size_t)p->n_knots;
+        const int Cc = p->reserved_ ? (p->reserved_ & 0xFFF) : p->channels;      // (zero-padded problems: the caller's channel count)
+        if (hipMemsetAsync(grad_coeffs, 0, sizeof(float) * (size_t)p->batch * rows * Cc, st) != hipSuccess) return NCDE_ERR_HIP;
+    }
     KArgs a;
     fill_kargs(p, y, &a);
     a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
@@ -3756,7 +3896,7 @@ int ncde_tiled_adjoint(const NcdeProblem* p, const float* src, const float* grad
             return tiled_adj_reduce(p, y, t, pw, g, a.gpart, gB, a.run_if, st);
         }
     }
-    const int rc = tiled_adj_run(p, t, pw, a, n_rsteps, gB, st);
+    const int rc = tiled_adj_run(p, t, pw, a, n_rsteps, gB, st, gdx, grad_coeffs);
     if (rc != NCDE_OK || main_kernel_only) return rc;
     return tiled_adj_reduce(p, y, t, pw, g, a.gpart, gB, nullptr, st);
 }

@@ -5,7 +5,7 @@ What the reference does per call -- wrap (X, func) in a vector field, hand it to
 time loop (solvers.py:94-119) and, for the backward pass, to OdeintAdjointMethod (adjoint.py:37-145)
 -- happens here in ONE kernel launch per direction.  There is no CPU fallback.  What the fused kernels do
 not cover but the reference accepts (an arbitrary ``func``, decreasing output times, gradients of the control
-path or of ``t``, non-fp32 tensors, shapes no fused kernel exists for -- hidden widths beyond 256 in training)
+path under the continuous adjoint or of ``t``, non-fp32 tensors, shapes no fused kernel exists for -- hidden widths beyond 256 in training)
 runs on the package's own UNFUSED torch-op solver on the GPU (unfused.py) behind a one-time UserWarning naming
 the reason; what neither path covers raises NotImplementedError.
 """
@@ -399,6 +399,140 @@ class _FusedCdeint(torch.autograd.Function):
         return (grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 
+class _FusedControl(torch.autograd.Function):
+    """adjoint=False with a coefficient tensor that requires grad (a stacked CDE: layer i's hidden sequence is layer i+1's linear
+    coefficients): forward = ncde_forward_record on its usual route, backward = ncde_backward_control -- ncde_backward on the
+    batch-tiled family plus dL/dcoeffs (pass C: ncde_dctl_tiled + ncde_dctl_fold).  `coeffs` is a differentiable input here."""
+
+    @staticmethod
+    def forward(ctx, z0, coeffs, cfg, *params):
+        spec = cfg["spec"]
+        z0c = z0.detach().contiguous()
+        coeffs = coeffs.detach()
+        p = build_problem(coeffs, cfg["interp"], z0c, spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
+        if cfg["plan"] is not None:
+            n_out = cfg["plan"][1][0]
+        else:
+            n_out = coeffs.shape[1] + (0 if cfg["interp"] == "linear" else 1) if cfg["output"] == _lib.OUT_KNOTS else 2
+        out = torch.empty(z0.shape[0], n_out, z0.shape[1], dtype=torch.float32, device=z0.device)
+        record = cfg["needs_grad"] and any(ctx.needs_input_grad)
+        lib = _lib.lib()
+        with torch.cuda.device(z0.device):
+            ws = _workspace(p, 0, z0.device)
+            if record:
+                nbytes = _lib.check(lib.ncde_stage_record_bytes(ctypes.byref(p)), "ncde_stage_record_bytes")
+                stages = torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=z0.device)
+                rc = lib.ncde_forward_record(ctypes.byref(p), out.data_ptr(), stages.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+            else:
+                rc = lib.ncde_forward(ctypes.byref(p), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+            if rc >= 0:
+                _coop_track(p, 0, ws, z0.device)
+        _lib.check(rc, "ncde_forward_record" if record else "ncde_forward")
+        ctx.cfg, ctx.z0_shape = cfg, z0.shape
+        if record:
+            ctx.save_for_backward(out, stages, coeffs, *params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        cfg = ctx.cfg
+        out, stages, coeffs, *params = ctx.saved_tensors
+        spec, dev = cfg["spec"], out.device
+        grad_out = grad_out.contiguous().float()
+        p = build_problem(coeffs, cfg["interp"], out[:, 0], spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
+        gbuf = {id(q): torch.empty_like(q, memory_format=torch.contiguous_format) for q in spec.unique_params()}
+        g = _lib.NcdeGrads()
+        grad_z0 = torch.empty(ctx.z0_shape, dtype=torch.float32, device=dev)
+        g.grad_z0 = grad_z0.data_ptr()
+        for i, (w, b) in enumerate(spec.layers):
+            g.grad_layer_W[i], g.grad_layer_b[i] = gbuf[id(w)].data_ptr(), gbuf[id(b)].data_ptr()
+        g.grad_Wo, g.grad_bo = gbuf[id(spec.Wo)].data_ptr(), gbuf[id(spec.bo)].data_ptr()
+        grad_coeffs = torch.empty(coeffs.shape, dtype=torch.float32, device=dev)
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            ws = _workspace_bytes(_lib.check(lib.ncde_control_workspace_bytes(ctypes.byref(p)), "ncde_control_workspace_bytes"), dev)
+            rc = lib.ncde_backward_control(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(g), grad_coeffs.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream_ptr())
+        _lib.check(rc, "ncde_backward_control")
+        grads = [gbuf[id(q)] if needs else None for q, needs in zip(params, ctx.needs_input_grad[3:])]
+        return (grad_z0 if ctx.needs_input_grad[0] else None, grad_coeffs if ctx.needs_input_grad[1] else None, None, *grads)
+
+
+_CONTROL_REASON = "the control path requires gradients"
+
+
+def _control_route(reason, adjoint, method, plain_control, cuda_fp32, coeffs_grad, other_grad, t_grad):
+    """The routing decision on plain values: a call that `_unfused_reason` sends away for `reason` may take the fused
+    control-gradient route iff adjoint=False, a fixed-step method, a plain LinearInterpolation / NaturalCubicSpline (`plain_control`),
+    z0 and the coefficients CUDA fp32 (`cuda_fp32`), the coefficient tensor requires grad and is the control's only buffer that does
+    (knots that require grad stay unfused), and `t` does not."""
+    return bool(reason == _CONTROL_REASON and not adjoint and method in _FIXED_METHODS and plain_control and cuda_fp32 and
+                coeffs_grad and not other_grad and not t_grad)
+
+
+def _control_route_ok(reason, X, z0, t, adjoint, method):
+    """`_control_route` of a call's arguments (looks at the arguments only: type, device, dtype, requires_grad)."""
+    if type(X) not in (LinearInterpolation, NaturalCubicSpline) or not torch.is_tensor(z0):
+        return False
+    coeffs = X._coeffs
+    cuda_fp32 = z0.is_cuda and coeffs.is_cuda and z0.dtype == torch.float32 and coeffs.dtype == torch.float32
+    other_grad = any(b.requires_grad for b in X.buffers() if b is not coeffs)
+    return _control_route(reason, adjoint, method, True, cuda_fp32, coeffs.requires_grad, other_grad, torch.is_tensor(t) and t.requires_grad)
+
+
+def _fused_control(X, func, z0, t, vector_field_type, method, options, flags):
+    """The fused control-gradient route of a call `_control_route_ok` accepted, or None when anything about it is outside what
+    ncde_backward_control covers (options beyond a positive step_size, a gated field or direct input, parameters that are not
+    contiguous CUDA fp32, a shape beyond the batch-tiled backward): the caller then runs the unfused solver as before."""
+    if set(options) - {"step_size", "perturb"} or options.get("perturb") or options.get("step_size") is None:
+        return None
+    step = options["step_size"]
+    step = step.item() if torch.is_tensor(step) else step
+    if not float(step) > 0.0 or z0.dim() < 1:
+        return None
+    coeffs = X._coeffs
+    batch_shape = z0.shape[:-1]
+    if coeffs.dim() < 2 or tuple(coeffs.shape[:-2]) != tuple(batch_shape):
+        return None
+    spec = func.fused_spec()
+    uniq = spec.unique_params()
+    if spec.kind != "original" or spec.mode != "matmul" or vector_field_type != "matmul" or not spec.layers:
+        return None
+    if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() for q in uniq):
+        return None
+    if len(batch_shape) != 1:
+        z0 = z0.reshape(-1, z0.shape[-1])
+        coeffs = coeffs.reshape(-1, coeffs.shape[-2], coeffs.shape[-1])
+    if coeffs.stride(2) != 1:
+        coeffs = coeffs.contiguous()
+    flags = _coop_flags(flags, z0.device)
+    output = _time_mode(X, t) if float(step) == 1.0 else None
+    stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
+    plan = None
+    if output is None:
+        tq = torch.as_tensor(t)
+        if tq.dim() != 1:
+            return None
+        plan = _time_plan(X, tq, method, step, z0.device)
+        output = _lib.OUT_TIMES
+        nfe = stages * plan[1][1]
+    else:
+        nfe = stages * (X.n_knots - 1)
+    p = build_problem(coeffs.detach(), X.interp_name, z0.detach(), spec, method, output, flags, plan)
+    lib = _lib.lib()
+    if lib.ncde_control_workspace_bytes(ctypes.byref(p)) < 0 or lib.ncde_workspace_bytes(ctypes.byref(p), 0) < 0:
+        return None
+    cfg = {"spec": spec, "interp": X.interp_name, "method": method, "output": output, "flags": flags, "plan": plan,
+           "needs_grad": torch.is_grad_enabled()}
+    out = _FusedControl.apply(z0, coeffs, cfg, *uniq)
+    if hasattr(func, "nfe"):
+        func.nfe += nfe
+    if len(batch_shape) != 1:
+        out = out.reshape(*batch_shape, out.shape[-2], out.shape[-1])
+    return out
+
+
 class _AdaptiveSpec:
     """Host description of one dopri5 call: output times / knots as host doubles + NcdeAdaptiveOptions."""
 
@@ -689,6 +823,10 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
 
     reason = _unfused_reason(X, func, z0, t, adjoint, adjoint_params, method)
     if reason is not None:
+        if _control_route_ok(reason, X, z0, t, adjoint, method):      # adjoint=False, coefficients that require grad: ncde_backward_control
+            out = _fused_control(X, func, z0, t, vector_field_type, method, options_in, flags)
+            if out is not None:
+                return out
         return unfused_(reason)
     adaptive = method == "dopri5"
     if adaptive:
