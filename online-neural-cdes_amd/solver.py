@@ -313,150 +313,132 @@ def _check_tensor(x, name):
         raise NotImplementedError("cdeint fused path needs fp32 tensors on the GPU; %s is %s on %s" % (name, x.dtype, x.device))
 
 
+class BoundGrads:
+    """What `bind_grads` returns: `g` (the NcdeGrads), `grad_z0` and `bufs` ({id(parameter): its gradient buffer}; `of(q)` looks one up)."""
+
+    def __init__(self, g, grad_z0, bufs):
+        self.g, self.grad_z0, self.bufs = g, grad_z0, bufs
+
+    def of(self, q):
+        return self.bufs[id(q)]
+
+
+def bind_grads(spec, z0_shape, device, live=None, fill=None):
+    """Allocate the destinations of one backward call and fill its NcdeGrads: one contiguous buffer per UNIQUE parameter (a shared
+    layer is bound to the same buffer at every layer index), the sigmoid head for the gated fields, the reset net for the GRU one.
+    live: ids of the parameters that get a destination -- the others keep NULL, which for the dopri5 adjoint means "not part of the
+    augmented state", hence not of the mixed error norm (adjoint.py:176-189); None binds every parameter.
+    fill: a value to initialise every buffer with (tests: NaN proves that a call wrote every element)."""
+    new = (lambda x: x) if fill is None else (lambda x: x.fill_(fill))
+    bufs = {id(q): new(torch.empty_like(q, memory_format=torch.contiguous_format)) for q in spec.unique_params()}
+    grad_z0 = new(torch.empty(z0_shape, dtype=torch.float32, device=device))
+    ptr = lambda q: bufs[id(q)].data_ptr() if live is None or id(q) in live else None      # noqa: E731
+    g = _lib.NcdeGrads()
+    g.grad_z0 = grad_z0.data_ptr()
+    for i, (w, b) in enumerate(spec.layers):
+        g.grad_layer_W[i], g.grad_layer_b[i] = ptr(w), ptr(b)
+    g.grad_Wo, g.grad_bo = ptr(spec.Wo), ptr(spec.bo)
+    if spec.kind != "original":
+        g.grad_Wg, g.grad_bg = ptr(spec.Wg), ptr(spec.bg)
+    if spec.kind == "gru":
+        g.grad_Wr, g.grad_br = ptr(spec.Wr), ptr(spec.br)
+    return BoundGrads(g, grad_z0, bufs)
+
+
+def _num_outputs(coeffs, interp, output, plan):
+    """Rows of the solution: the plan's output times, every knot of the control, or the two ends of the interval."""
+    if plan is not None:
+        return plan[1][0]
+    return coeffs.shape[1] + (0 if interp == "linear" else 1) if output == _lib.OUT_KNOTS else 2
+
+
+def _alloc_out(z0, n_out):
+    return torch.empty(z0.shape[0], n_out, z0.shape[1], dtype=torch.float32, device=z0.device)
+
+
+def _launch_forward(p, out, record, dev):
+    """ncde_forward, or with `record` ncde_forward_record (-> the stage record, else None), of `p` into `out`; the cooperative
+    status word is tracked and rc checked under the name of the entry point that was called."""
+    lib = _lib.lib()
+    stages = None
+    with torch.cuda.device(dev):   # the C-ABI launches on the calling thread's current device / stream
+        ws = _workspace(p, 0, dev)
+        if record:
+            nbytes = _lib.check(lib.ncde_stage_record_bytes(ctypes.byref(p)), "ncde_stage_record_bytes")
+            stages = torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=dev)
+            rc = lib.ncde_forward_record(ctypes.byref(p), out.data_ptr(), stages.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+        else:
+            rc = lib.ncde_forward(ctypes.byref(p), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+        if rc >= 0:
+            _coop_track(p, 0, ws, dev)
+    _lib.check(rc, "ncde_forward_record" if record else "ncde_forward")
+    return stages
+
+
 class _FusedCdeint(torch.autograd.Function):
     """adjoint=True : forward = ncde_forward, backward = ncde_adjoint (continuous adjoint, adjoint.py:37-145).
     adjoint=False: forward = ncde_forward_record (solution + every stage input), backward = ncde_backward, the exact
     transpose of the discretised solve -- the gradients autograd produces in the reference when ``odeint`` is
-    taped (solver.py:224), without a tape."""
+    taped (solver.py:224), without a tape.
+    cfg["control"] (adjoint=False with a coefficient tensor that requires grad; a stacked CDE: layer i's hidden sequence is layer
+    i+1's linear coefficients): `coeffs` is a differentiable input, the forward keeps its usual route and the backward is
+    ncde_backward_control -- ncde_backward on the batch-tiled family plus dL/dcoeffs (pass C: ncde_dctl_tiled + ncde_dctl_fold)."""
 
     @staticmethod
     def forward(ctx, z0, coeffs, cfg, *params):
-        spec = cfg["spec"]
+        control = bool(cfg.get("control"))
+        if control:
+            coeffs = coeffs.detach()
         z0c = z0.detach().contiguous()
-        p = build_problem(coeffs, cfg["interp"], z0c, spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
-        if cfg["plan"] is not None:
-            n_out = cfg["plan"][1][0]
-        else:
-            n_out = coeffs.shape[1] + (0 if cfg["interp"] == "linear" else 1) if cfg["output"] == _lib.OUT_KNOTS else 2
-        out = torch.empty(z0.shape[0], n_out, z0.shape[1], dtype=torch.float32, device=z0.device)
+        p = build_problem(coeffs, cfg["interp"], z0c, cfg["spec"], cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
+        out = _alloc_out(z0, _num_outputs(coeffs, cfg["interp"], cfg["output"], cfg["plan"]))
         record = (not cfg["adjoint"]) and cfg.get("needs_grad", True) and any(ctx.needs_input_grad)
-        stages = None
-        with torch.cuda.device(z0.device):   # the C-ABI launches on the calling thread's current device / stream
-            ws = _workspace(p, 0, z0.device)
-            if record:
-                nbytes = _lib.check(_lib.lib().ncde_stage_record_bytes(ctypes.byref(p)), "ncde_stage_record_bytes")
-                stages = torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=z0.device)
-                rc = _lib.lib().ncde_forward_record(ctypes.byref(p), out.data_ptr(), stages.data_ptr(), ws.data_ptr(),
-                                                    ws.numel(), _stream_ptr())
-            else:
-                rc = _lib.lib().ncde_forward(ctypes.byref(p), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
-            if rc >= 0:
-                _coop_track(p, 0, ws, z0.device)
-        _lib.check(rc, "ncde_forward_record" if record else "ncde_forward")
-        ctx.cfg = cfg
-        ctx.coeffs = coeffs
-        ctx.recorded = record
-        if record:
-            ctx.save_for_backward(out, stages, *params)
-        else:
-            ctx.save_for_backward(out, *params)
-        ctx.z0_shape = z0.shape
+        stages = _launch_forward(p, out, record, z0.device)
+        ctx.cfg, ctx.z0_shape, ctx.recorded = cfg, z0.shape, record
+        ctx.coeffs = None if control else coeffs
+        ctx.save_for_backward(out, *([stages] if record else []), *([coeffs] if control else []), *params)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable     # the kernels are not themselves differentiable: no create_graph
     def backward(ctx, grad_out):
         cfg = ctx.cfg
-        if ctx.recorded:
-            out, stages, *params = ctx.saved_tensors
-        else:
-            out, *params = ctx.saved_tensors
-        spec, coeffs = cfg["spec"], ctx.coeffs
-        dev = out.device
+        control = bool(cfg.get("control"))
+        params = list(ctx.saved_tensors)
+        out = params.pop(0)
+        stages = params.pop(0) if ctx.recorded else None
+        coeffs = params.pop(0) if control else ctx.coeffs
+        spec, dev = cfg["spec"], out.device
         grad_out = grad_out.contiguous().float()
         z0 = out[:, 0]     # only its shape matters here: the backward kernels never read z0 (row 0 of `out` is a valid pointer)
         p = build_problem(coeffs, cfg["interp"], z0, spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
-        uniq = spec.unique_params()
-        gbuf = {id(q): torch.empty_like(q, memory_format=torch.contiguous_format) for q in uniq}
-        g = _lib.NcdeGrads()
-        grad_z0 = torch.empty(ctx.z0_shape, dtype=torch.float32, device=dev)
-        g.grad_z0 = grad_z0.data_ptr()
-        for i, (w, b) in enumerate(spec.layers):
-            g.grad_layer_W[i], g.grad_layer_b[i] = gbuf[id(w)].data_ptr(), gbuf[id(b)].data_ptr()
-        g.grad_Wo, g.grad_bo = gbuf[id(spec.Wo)].data_ptr(), gbuf[id(spec.bo)].data_ptr()
-        if spec.kind != "original":
-            g.grad_Wg, g.grad_bg = gbuf[id(spec.Wg)].data_ptr(), gbuf[id(spec.bg)].data_ptr()
-        if spec.kind == "gru":
-            g.grad_Wr, g.grad_br = gbuf[id(spec.Wr)].data_ptr(), gbuf[id(spec.br)].data_ptr()
+        bound = bind_grads(spec, ctx.z0_shape, dev)
+        grad_coeffs = torch.empty(coeffs.shape, dtype=torch.float32, device=dev) if control else None
+        lib = _lib.lib()
         with torch.cuda.device(dev):
-            if ctx.recorded:
+            if control:
+                name = "ncde_backward_control"
+                ws = _workspace_bytes(_lib.check(lib.ncde_control_workspace_bytes(ctypes.byref(p)), "ncde_control_workspace_bytes"), dev)
+                rc = lib.ncde_backward_control(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(bound.g),
+                                               grad_coeffs.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+            elif ctx.recorded:
+                name = "ncde_backward"
                 ws = _workspace(p, 2, dev)
-                rc = _lib.lib().ncde_backward(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(g),
-                                              ws.data_ptr(), ws.numel(), _stream_ptr())
+                rc = lib.ncde_backward(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(bound.g),
+                                       ws.data_ptr(), ws.numel(), _stream_ptr())
             else:
+                name = "ncde_adjoint"
                 ws = _workspace(p, 1, dev)
-                rc = _lib.lib().ncde_adjoint(ctypes.byref(p), out.data_ptr(), grad_out.data_ptr(), ctypes.byref(g),
-                                             ws.data_ptr(), ws.numel(), _stream_ptr())
-            if rc >= 0:
+                rc = lib.ncde_adjoint(ctypes.byref(p), out.data_ptr(), grad_out.data_ptr(), ctypes.byref(bound.g),
+                                      ws.data_ptr(), ws.numel(), _stream_ptr())
+            if rc >= 0 and not control:      # (the control route pins NCDE_FLAG_NO_COOP: nothing cooperative to track)
                 _coop_track(p, 2 if ctx.recorded else 1, ws, dev)
-        _lib.check(rc, "ncde_backward" if ctx.recorded else "ncde_adjoint")
+        _lib.check(rc, name)
         if not ctx.recorded and cfg["func"] is not None and hasattr(cfg["func"], "nfe"):
             cfg["func"].nfe += cfg["nfe_adjoint"]   # the adjoint sweep re-evaluates f (base.py:90); autograd does not
-        grads = []
-        keep = cfg["adjoint_param_ids"]     # adjoint_params of odeint_adjoint (adjoint.py:176-183): others get no gradient
-        for q, needs in zip(params, ctx.needs_input_grad[3:]):
-            grads.append(gbuf[id(q)] if needs and (keep is None or id(q) in keep) else None)
-        return (grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
-
-
-class _FusedControl(torch.autograd.Function):
-    """adjoint=False with a coefficient tensor that requires grad (a stacked CDE: layer i's hidden sequence is layer i+1's linear
-    coefficients): forward = ncde_forward_record on its usual route, backward = ncde_backward_control -- ncde_backward on the
-    batch-tiled family plus dL/dcoeffs (pass C: ncde_dctl_tiled + ncde_dctl_fold).  `coeffs` is a differentiable input here."""
-
-    @staticmethod
-    def forward(ctx, z0, coeffs, cfg, *params):
-        spec = cfg["spec"]
-        z0c = z0.detach().contiguous()
-        coeffs = coeffs.detach()
-        p = build_problem(coeffs, cfg["interp"], z0c, spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
-        if cfg["plan"] is not None:
-            n_out = cfg["plan"][1][0]
-        else:
-            n_out = coeffs.shape[1] + (0 if cfg["interp"] == "linear" else 1) if cfg["output"] == _lib.OUT_KNOTS else 2
-        out = torch.empty(z0.shape[0], n_out, z0.shape[1], dtype=torch.float32, device=z0.device)
-        record = cfg["needs_grad"] and any(ctx.needs_input_grad)
-        lib = _lib.lib()
-        with torch.cuda.device(z0.device):
-            ws = _workspace(p, 0, z0.device)
-            if record:
-                nbytes = _lib.check(lib.ncde_stage_record_bytes(ctypes.byref(p)), "ncde_stage_record_bytes")
-                stages = torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=z0.device)
-                rc = lib.ncde_forward_record(ctypes.byref(p), out.data_ptr(), stages.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
-            else:
-                rc = lib.ncde_forward(ctypes.byref(p), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
-            if rc >= 0:
-                _coop_track(p, 0, ws, z0.device)
-        _lib.check(rc, "ncde_forward_record" if record else "ncde_forward")
-        ctx.cfg, ctx.z0_shape = cfg, z0.shape
-        if record:
-            ctx.save_for_backward(out, stages, coeffs, *params)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        cfg = ctx.cfg
-        out, stages, coeffs, *params = ctx.saved_tensors
-        spec, dev = cfg["spec"], out.device
-        grad_out = grad_out.contiguous().float()
-        p = build_problem(coeffs, cfg["interp"], out[:, 0], spec, cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
-        gbuf = {id(q): torch.empty_like(q, memory_format=torch.contiguous_format) for q in spec.unique_params()}
-        g = _lib.NcdeGrads()
-        grad_z0 = torch.empty(ctx.z0_shape, dtype=torch.float32, device=dev)
-        g.grad_z0 = grad_z0.data_ptr()
-        for i, (w, b) in enumerate(spec.layers):
-            g.grad_layer_W[i], g.grad_layer_b[i] = gbuf[id(w)].data_ptr(), gbuf[id(b)].data_ptr()
-        g.grad_Wo, g.grad_bo = gbuf[id(spec.Wo)].data_ptr(), gbuf[id(spec.bo)].data_ptr()
-        grad_coeffs = torch.empty(coeffs.shape, dtype=torch.float32, device=dev)
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            ws = _workspace_bytes(_lib.check(lib.ncde_control_workspace_bytes(ctypes.byref(p)), "ncde_control_workspace_bytes"), dev)
-            rc = lib.ncde_backward_control(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(g), grad_coeffs.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), _stream_ptr())
-        _lib.check(rc, "ncde_backward_control")
-        grads = [gbuf[id(q)] if needs else None for q, needs in zip(params, ctx.needs_input_grad[3:])]
-        return (grad_z0 if ctx.needs_input_grad[0] else None, grad_coeffs if ctx.needs_input_grad[1] else None, None, *grads)
+        keep = cfg.get("adjoint_param_ids")     # adjoint_params of odeint_adjoint (adjoint.py:176-183): others get no gradient
+        grads = [bound.of(q) if needs and (keep is None or id(q) in keep) else None for q, needs in zip(params, ctx.needs_input_grad[3:])]
+        return (bound.grad_z0 if ctx.needs_input_grad[0] else None, grad_coeffs if ctx.needs_input_grad[1] else None, None, *grads)
 
 
 _CONTROL_REASON = "the control path requires gradients"
@@ -481,6 +463,38 @@ def _control_route_ok(reason, X, z0, t, adjoint, method):
     return _control_route(reason, adjoint, method, True, cuda_fp32, coeffs.requires_grad, other_grad, torch.is_tensor(t) and t.requires_grad)
 
 
+_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+def _fixed_axis(X, t, method, step, device):
+    """-> (output, plan, nfe, nfe_adjoint) of a fixed-step solve: the default axis when `_time_mode` recognises X's own interval /
+    knots under step 1, else the time plan.  None for a `t` the plan cannot take (not one-dimensional): the caller reports it."""
+    output = _time_mode(X, t) if float(step) == 1.0 else None
+    if output is not None:
+        nfe = _STAGES[method] * (X.n_knots - 1)
+        return output, None, nfe, nfe
+    tq = torch.as_tensor(t)
+    if tq.dim() != 1:
+        return None
+    plan = _time_plan(X, tq, method, step, device)
+    return _lib.OUT_TIMES, plan, _STAGES[method] * plan[1][1], _STAGES[method] * plan[1][2]
+
+
+def _flatten_batch(z0, coeffs):
+    """Any number of batch dimensions, as the reference allows, flattened for the kernels: z0 [B, H], coeffs [B, T, K] with unit
+    stride in K.  `_restore_batch` undoes it on the solution."""
+    if z0.dim() != 2:
+        z0 = z0.reshape(-1, z0.shape[-1])
+        coeffs = coeffs.reshape(-1, coeffs.shape[-2], coeffs.shape[-1])
+    if coeffs.stride(2) != 1:
+        coeffs = coeffs.contiguous()
+    return z0, coeffs
+
+
+def _restore_batch(out, batch_shape):
+    return out if len(batch_shape) == 1 else out.reshape(*batch_shape, out.shape[-2], out.shape[-1])
+
+
 def _fused_control(X, func, z0, t, vector_field_type, method, options, flags):
     """The fused control-gradient route of a call `_control_route_ok` accepted, or None when anything about it is outside what
     ncde_backward_control covers (options beyond a positive step_size, a gated field or direct input, parameters that are not
@@ -501,36 +515,22 @@ def _fused_control(X, func, z0, t, vector_field_type, method, options, flags):
         return None
     if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() for q in uniq):
         return None
-    if len(batch_shape) != 1:
-        z0 = z0.reshape(-1, z0.shape[-1])
-        coeffs = coeffs.reshape(-1, coeffs.shape[-2], coeffs.shape[-1])
-    if coeffs.stride(2) != 1:
-        coeffs = coeffs.contiguous()
+    z0, coeffs = _flatten_batch(z0, coeffs)
     flags = _coop_flags(flags, z0.device)
-    output = _time_mode(X, t) if float(step) == 1.0 else None
-    stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-    plan = None
-    if output is None:
-        tq = torch.as_tensor(t)
-        if tq.dim() != 1:
-            return None
-        plan = _time_plan(X, tq, method, step, z0.device)
-        output = _lib.OUT_TIMES
-        nfe = stages * plan[1][1]
-    else:
-        nfe = stages * (X.n_knots - 1)
+    axis = _fixed_axis(X, t, method, step, z0.device)
+    if axis is None:
+        return None
+    output, plan, nfe, _ = axis
     p = build_problem(coeffs.detach(), X.interp_name, z0.detach(), spec, method, output, flags, plan)
     lib = _lib.lib()
     if lib.ncde_control_workspace_bytes(ctypes.byref(p)) < 0 or lib.ncde_workspace_bytes(ctypes.byref(p), 0) < 0:
         return None
     cfg = {"spec": spec, "interp": X.interp_name, "method": method, "output": output, "flags": flags, "plan": plan,
-           "needs_grad": torch.is_grad_enabled()}
-    out = _FusedControl.apply(z0, coeffs, cfg, *uniq)
+           "needs_grad": torch.is_grad_enabled(), "adjoint": False, "control": True}
+    out = _FusedCdeint.apply(z0, coeffs, cfg, *uniq)
     if hasattr(func, "nfe"):
         func.nfe += nfe
-    if len(batch_shape) != 1:
-        out = out.reshape(*batch_shape, out.shape[-2], out.shape[-1])
-    return out
+    return _restore_batch(out, batch_shape)
 
 
 class _AdaptiveSpec:
@@ -567,31 +567,73 @@ class _AdaptiveSpec:
         self.opt = o
 
 
+def _dopri5_call(name, cfg, ad, coeffs, z0, pass_, launch, book=None):
+    """One adaptive C-ABI call `name` of pass `pass_` (0 forward, 1 adjoint, 2 taped backward) under the time / option structs `ad`:
+    builds the problem ("rk4" and OUT_INTERVAL only fill the fields; `ad.ts` carries the output times), sizes the workspace and
+    runs `launch(entry point, leading arguments (problem, times, options), trailing arguments (workspace, its size, stream[,
+    stats])) -> rc` on z0's device.  book = "forward" / "backward" for the solves that step adaptively: an rc of -1 is the
+    reference's assertion (rk_common.py:232-233, 195), and their statistics go to cfg["stats_<book>"], `func.nfe` and, when a trace was
+    asked for (diagnostics, tests), `func.dopri5_trace[_backward]`."""
+    lib = _lib.lib()
+    p = build_problem(coeffs, cfg["interp"], z0, cfg["spec"], "rk4", _lib.OUT_INTERVAL, cfg["flags"])
+    stats = _lib.NcdeAdaptiveStats()
+    with torch.cuda.device(z0.device):
+        need = _lib.check(lib.ncde_dopri5_workspace_bytes(ctypes.byref(p), ctypes.byref(ad.ts), pass_), "ncde_dopri5_workspace_bytes")
+        ws = _workspace_bytes(int(need), z0.device)
+        tail = (ws.data_ptr(), ws.numel(), _stream_ptr()) + ((ctypes.byref(stats),) if book else ())
+        rc = launch(getattr(lib, name), (ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt)), tail)
+    if book and rc == -1:
+        raise AssertionError(lib.ncde_last_error_string().decode())
+    _lib.check(rc, name)
+    if not book:
+        return
+    cfg["stats_" + book] = (stats.nfe, stats.n_accepted, stats.n_rejected)
+    func = cfg["func"]
+    if func is not None and ad.trace is not None:
+        setattr(func, "dopri5_trace" if book == "forward" else "dopri5_trace_backward", ad.trace[:stats.n_accepted + stats.n_rejected].copy())
+    if func is not None and hasattr(func, "nfe"):
+        func.nfe += stats.nfe
+
+
+def _dopri5_forward(z0, coeffs, cfg, taped=False):
+    """The adaptive forward solve -> (solution, the contiguous z0 it started from, step record or None).  taped: ncde_dopri5_forward_record
+    keeps a record of the accepted steps for ncde_dopri5_backward."""
+    ad = cfg["adaptive"]
+    z0c = z0.detach().contiguous()
+    out = _alloc_out(z0, len(ad.tv))
+    rec = None
+
+    def launch_record(fn, head, tail):
+        # The record holds one start state per ACCEPTED step; its default size is a guess when the options give no min_step
+        # (ncde_dopri5_record_bytes).  A solve that outgrows it reports NCDE_ERR_WORKSPACE: repeat it with twice the record
+        # -- the forward is deterministic -- where the reference's autograd tape would simply have grown (ADVICE round 3).
+        nonlocal rec
+        lib = _lib.lib()
+        rbytes = int(_lib.check(lib.ncde_dopri5_record_bytes(*head), "ncde_dopri5_record_bytes"))
+        rbytes = int(cfg.get("record_bytes") or rbytes)
+        for _ in range(8):
+            rec = torch.empty(rbytes, dtype=torch.uint8, device=z0.device)
+            rc = fn(*head, out.data_ptr(), rec.data_ptr(), rec.numel(), *tail)
+            if rc != -3 or b"record" not in (lib.ncde_last_error_string() or b""):
+                break
+            rec = None
+            rbytes *= 2
+        return rc
+
+    if taped:
+        _dopri5_call("ncde_dopri5_forward_record", cfg, ad, coeffs, z0c, 0, launch_record, "forward")
+    else:
+        _dopri5_call("ncde_dopri5_forward", cfg, ad, coeffs, z0c, 0, lambda fn, head, tail: fn(*head, out.data_ptr(), *tail), "forward")
+    return out, z0c, rec
+
+
 class _FusedDopri5(torch.autograd.Function):
     """method='dopri5': forward = ncde_dopri5_forward; backward = ncde_dopri5_adjoint (one adaptive reverse solve per output
     interval, adjoint.py:37-145).  Both calls synchronise: the number of attempts depends on the data."""
 
     @staticmethod
     def forward(ctx, z0, coeffs, cfg, *params):
-        spec, ad = cfg["spec"], cfg["adaptive"]
-        z0c = z0.detach().contiguous()
-        p = build_problem(coeffs, cfg["interp"], z0c, spec, "rk4", _lib.OUT_INTERVAL, cfg["flags"])
-        out = torch.empty(z0.shape[0], len(ad.tv), z0.shape[1], dtype=torch.float32, device=z0.device)
-        lib = _lib.lib()
-        stats = _lib.NcdeAdaptiveStats()
-        with torch.cuda.device(z0.device):
-            need = _lib.check(lib.ncde_dopri5_workspace_bytes(ctypes.byref(p), ctypes.byref(ad.ts), 0), "ncde_dopri5_workspace_bytes")
-            ws = _workspace_bytes(int(need), z0.device)
-            rc = lib.ncde_dopri5_forward(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt), out.data_ptr(), ws.data_ptr(),
-                                         ws.numel(), _stream_ptr(), ctypes.byref(stats))
-        if rc == -1:
-            raise AssertionError(lib.ncde_last_error_string().decode())      # the reference asserts (rk_common.py:232-233, 195)
-        _lib.check(rc, "ncde_dopri5_forward")
-        cfg["stats_forward"] = (stats.nfe, stats.n_accepted, stats.n_rejected)
-        if ad.trace is not None and cfg["func"] is not None:
-            cfg["func"].dopri5_trace = ad.trace[:stats.n_accepted + stats.n_rejected].copy()
-        if cfg["func"] is not None and hasattr(cfg["func"], "nfe"):
-            cfg["func"].nfe += stats.nfe
+        out = _dopri5_forward(z0, coeffs, cfg)[0]
         ctx.cfg, ctx.coeffs, ctx.z0_shape = cfg, coeffs, z0.shape
         ctx.save_for_backward(out, *params)
         return out
@@ -601,40 +643,16 @@ class _FusedDopri5(torch.autograd.Function):
     def backward(ctx, grad_out):
         cfg = ctx.cfg
         out, *params = ctx.saved_tensors
-        spec, ad = cfg["spec"], cfg["adaptive_backward"]
-        dev = out.device
         grad_out = grad_out.contiguous().float()
-        p = build_problem(ctx.coeffs, cfg["interp"], out[:, 0], spec, "rk4", _lib.OUT_INTERVAL, cfg["flags"])
-        uniq = spec.unique_params()
-        gbuf = {id(q): torch.empty_like(q, memory_format=torch.contiguous_format) for q in uniq}
-        g = _lib.NcdeGrads()
-        grad_z0 = torch.empty(ctx.z0_shape, dtype=torch.float32, device=dev)
-        g.grad_z0 = grad_z0.data_ptr()
         # the adjoint's parameters (adjoint.py:176-189): those that require a gradient and, if given, are listed in adjoint_params; the
         # others get a NULL destination = they are not part of the augmented state, hence not of the mixed error norm
         keep = cfg["adjoint_param_ids"]
         live = {id(q) for q, needs in zip(params, ctx.needs_input_grad[3:]) if needs and (keep is None or id(q) in keep)}
-        ptr = lambda q: gbuf[id(q)].data_ptr() if id(q) in live else None      # noqa: E731
-        for i, (w, b) in enumerate(spec.layers):
-            g.grad_layer_W[i], g.grad_layer_b[i] = ptr(w), ptr(b)
-        g.grad_Wo, g.grad_bo = ptr(spec.Wo), ptr(spec.bo)
-        lib = _lib.lib()
-        stats = _lib.NcdeAdaptiveStats()
-        with torch.cuda.device(dev):
-            need = _lib.check(lib.ncde_dopri5_workspace_bytes(ctypes.byref(p), ctypes.byref(ad.ts), 1), "ncde_dopri5_workspace_bytes")
-            ws = _workspace_bytes(int(need), dev)
-            rc = lib.ncde_dopri5_adjoint(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt), out.data_ptr(), grad_out.data_ptr(),
-                                         ctypes.byref(g), ws.data_ptr(), ws.numel(), _stream_ptr(), ctypes.byref(stats))
-        if rc == -1:
-            raise AssertionError(lib.ncde_last_error_string().decode())
-        _lib.check(rc, "ncde_dopri5_adjoint")
-        cfg["stats_backward"] = (stats.nfe, stats.n_accepted, stats.n_rejected)
-        if cfg["func"] is not None and hasattr(cfg["func"], "nfe"):
-            cfg["func"].nfe += stats.nfe
-        if ad.trace is not None and cfg["func"] is not None:      # diagnostics (tests): the reverse solve's own step sequence
-            cfg["func"].dopri5_trace_backward = ad.trace[:stats.n_accepted + stats.n_rejected].copy()
-        grads = [gbuf[id(q)] if id(q) in live else None for q in params]
-        return (grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
+        bound = bind_grads(cfg["spec"], ctx.z0_shape, out.device, live)
+        _dopri5_call("ncde_dopri5_adjoint", cfg, cfg["adaptive_backward"], ctx.coeffs, out[:, 0], 1,
+                     lambda fn, head, tail: fn(*head, out.data_ptr(), grad_out.data_ptr(), ctypes.byref(bound.g), *tail), "backward")
+        grads = [bound.of(q) if id(q) in live else None for q in params]
+        return (bound.grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 
 class _FusedDopri5Taped(torch.autograd.Function):
@@ -645,43 +663,9 @@ class _FusedDopri5Taped(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z0, coeffs, cfg, *params):
-        spec, ad = cfg["spec"], cfg["adaptive"]
-        z0c = z0.detach().contiguous()
-        p = build_problem(coeffs, cfg["interp"], z0c, spec, "rk4", _lib.OUT_INTERVAL, cfg["flags"])
-        out = torch.empty(z0.shape[0], len(ad.tv), z0.shape[1], dtype=torch.float32, device=z0.device)
-        lib = _lib.lib()
-        stats = _lib.NcdeAdaptiveStats()
         # nothing to differentiate (torch.no_grad(), frozen inputs): the plain solve, no step record at all
         taped = cfg.get("needs_grad", True) and any(ctx.needs_input_grad)
-        rec = None
-        with torch.cuda.device(z0.device):
-            need = _lib.check(lib.ncde_dopri5_workspace_bytes(ctypes.byref(p), ctypes.byref(ad.ts), 0), "ncde_dopri5_workspace_bytes")
-            ws = _workspace_bytes(int(need), z0.device)
-            if not taped:
-                rc = lib.ncde_dopri5_forward(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt), out.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), _stream_ptr(), ctypes.byref(stats))
-            else:
-                # The record holds one start state per ACCEPTED step; its default size is a guess when the options give no min_step
-                # (ncde_dopri5_record_bytes).  A solve that outgrows it reports NCDE_ERR_WORKSPACE: repeat it with twice the record
-                # -- the forward is deterministic -- where the reference's autograd tape would simply have grown.
-                rbytes = int(_lib.check(lib.ncde_dopri5_record_bytes(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt)), "ncde_dopri5_record_bytes"))
-                rbytes = int(cfg.get("record_bytes") or rbytes)
-                for _ in range(8):
-                    rec = torch.empty(rbytes, dtype=torch.uint8, device=z0.device)
-                    rc = lib.ncde_dopri5_forward_record(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt), out.data_ptr(), rec.data_ptr(),
-                                                        rec.numel(), ws.data_ptr(), ws.numel(), _stream_ptr(), ctypes.byref(stats))
-                    if rc != -3 or b"record" not in (lib.ncde_last_error_string() or b""):
-                        break
-                    rec = None
-                    rbytes *= 2
-        if rc == -1:
-            raise AssertionError(lib.ncde_last_error_string().decode())      # the reference asserts (rk_common.py:232-233, 195)
-        _lib.check(rc, "ncde_dopri5_forward_record" if taped else "ncde_dopri5_forward")
-        cfg["stats_forward"] = (stats.nfe, stats.n_accepted, stats.n_rejected)
-        if ad.trace is not None and cfg["func"] is not None:
-            cfg["func"].dopri5_trace = ad.trace[:stats.n_accepted + stats.n_rejected].copy()
-        if cfg["func"] is not None and hasattr(cfg["func"], "nfe"):
-            cfg["func"].nfe += stats.nfe
+        out, z0c, rec = _dopri5_forward(z0, coeffs, cfg, taped)
         ctx.cfg, ctx.coeffs, ctx.z0_shape = cfg, coeffs, z0.shape
         if taped:
             ctx.save_for_backward(z0c, rec, *params)
@@ -692,27 +676,12 @@ class _FusedDopri5Taped(torch.autograd.Function):
     def backward(ctx, grad_out):
         cfg = ctx.cfg
         z0c, rec, *params = ctx.saved_tensors
-        spec, ad = cfg["spec"], cfg["adaptive"]
-        dev = z0c.device
         grad_out = grad_out.contiguous().float()
-        p = build_problem(ctx.coeffs, cfg["interp"], z0c, spec, "rk4", _lib.OUT_INTERVAL, cfg["flags"])
-        uniq = spec.unique_params()
-        gbuf = {id(q): torch.empty_like(q, memory_format=torch.contiguous_format) for q in uniq}
-        g = _lib.NcdeGrads()
-        grad_z0 = torch.empty(ctx.z0_shape, dtype=torch.float32, device=dev)
-        g.grad_z0 = grad_z0.data_ptr()
-        for i, (w, b) in enumerate(spec.layers):
-            g.grad_layer_W[i], g.grad_layer_b[i] = gbuf[id(w)].data_ptr(), gbuf[id(b)].data_ptr()
-        g.grad_Wo, g.grad_bo = gbuf[id(spec.Wo)].data_ptr(), gbuf[id(spec.bo)].data_ptr()
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            need = _lib.check(lib.ncde_dopri5_workspace_bytes(ctypes.byref(p), ctypes.byref(ad.ts), 2), "ncde_dopri5_workspace_bytes")
-            ws = _workspace_bytes(int(need), dev)
-            rc = lib.ncde_dopri5_backward(ctypes.byref(p), ctypes.byref(ad.ts), ctypes.byref(ad.opt), rec.data_ptr(), rec.numel(),
-                                          grad_out.data_ptr(), ctypes.byref(g), ws.data_ptr(), ws.numel(), _stream_ptr())
-        _lib.check(rc, "ncde_dopri5_backward")
-        grads = [gbuf[id(q)] if needs else None for q, needs in zip(params, ctx.needs_input_grad[3:])]
-        return (grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
+        bound = bind_grads(cfg["spec"], ctx.z0_shape, z0c.device)
+        _dopri5_call("ncde_dopri5_backward", cfg, cfg["adaptive"], ctx.coeffs, z0c, 2,
+                     lambda fn, head, tail: fn(*head, rec.data_ptr(), rec.numel(), grad_out.data_ptr(), ctypes.byref(bound.g), *tail))
+        grads = [bound.of(q) if needs else None for q, needs in zip(params, ctx.needs_input_grad[3:])]
+        return (bound.grad_z0 if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 
 _DOPRI5_OPTIONS = ("min_step", "max_step", "first_step", "safety", "ifactor", "dfactor", "max_num_steps", "_trace", "_replay",
@@ -873,11 +842,7 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
         raise ValueError("batch dimensions of X %s != batch dimensions of z0 %s" % (tuple(coeffs.shape[:-2]), tuple(batch_shape)))
     _check_tensor(z0, "z0")
     _check_tensor(coeffs, "coeffs")
-    if len(batch_shape) != 1:
-        z0 = z0.reshape(-1, z0.shape[-1])
-        coeffs = coeffs.reshape(-1, coeffs.shape[-2], coeffs.shape[-1])
-    if coeffs.stride(2) != 1:
-        coeffs = coeffs.contiguous()
+    z0, coeffs = _flatten_batch(z0, coeffs)
     if coeffs.shape[0] != z0.shape[0]:
         raise ValueError("batch of X (%d) != batch of z0 (%d)" % (coeffs.shape[0], z0.shape[0]))
     spec = _field_spec(func)
@@ -910,22 +875,11 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
         why = _no_kernel_reason(build_problem(coeffs, X.interp_name, z0.detach(), spec, "rk4", _lib.OUT_INTERVAL, flags), passes, cfg["adaptive"].ts)
         if why is not None:
             return unfused_(why, warned=True)
-        out = (_FusedDopri5 if adjoint else _FusedDopri5Taped).apply(z0, coeffs.detach(), cfg, *uniq)
-        if len(batch_shape) != 1:
-            out = out.reshape(*batch_shape, out.shape[-2], out.shape[-1])
-        return out
+        return _restore_batch((_FusedDopri5 if adjoint else _FusedDopri5Taped).apply(z0, coeffs.detach(), cfg, *uniq), batch_shape)
     flags = _coop_flags(flags, z0.device)
-    output = _time_mode(X, t) if float(step) == 1.0 else None
-    stages = {"euler": 1, "midpoint": 2, "rk4": 4}[method]
-    plan = None
-    if output is None:
-        tq = torch.as_tensor(t)
-        assert tq.dim() == 1, "t must be one dimensional"
-        plan = _time_plan(X, tq, method, step, z0.device)
-        output = _lib.OUT_TIMES
-        nfe, nfe_adj = stages * plan[1][1], stages * plan[1][2]
-    else:
-        nfe = nfe_adj = stages * (X.n_knots - 1)
+    axis = _fixed_axis(X, t, method, step, z0.device)
+    assert axis is not None, "t must be one dimensional"
+    output, plan, nfe, nfe_adj = axis
     why = _no_kernel_reason(build_problem(coeffs, X.interp_name, z0.detach(), spec, method, output, flags, plan), passes)
     if why is not None:
         return unfused_(why, warned=True)
@@ -934,6 +888,4 @@ def cdeint(X, func, z0, t, adjoint=True, vector_field_type="matmul", **kwargs):
     out = _FusedCdeint.apply(z0, coeffs.detach(), cfg, *uniq)
     if hasattr(func, "nfe"):
         func.nfe += nfe
-    if len(batch_shape) != 1:
-        out = out.reshape(*batch_shape, out.shape[-2], out.shape[-1])
-    return out
+    return _restore_batch(out, batch_shape)

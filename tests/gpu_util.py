@@ -28,11 +28,29 @@ def case_field(case, device):
     return CaseField(case["params"], case["layers"], device, m.get("field_kind", "original"), m.get("field_mode", "matmul"))
 
 
+def case_control(case, device):
+    """The control path of a golden case (default integer grid)."""
+    coeffs = torch.from_numpy(case["coeffs"]).to(device)
+    return (ncde_amd.LinearInterpolation if case["meta"]["kind"] == "linear" else ncde_amd.NaturalCubicSpline)(coeffs)
+
+
+def case_problem(case, flags, device, z0=None):
+    """-> (the NcdeProblem of a golden case on its default axis, its field, the tensors the problem points into).  z0: start from
+    this state instead of the case's own."""
+    from ncde_amd import solver
+    m = case["meta"]
+    coeffs = torch.from_numpy(case["coeffs"]).to(device)
+    func = case_field(case, device)
+    z0 = torch.from_numpy(case["z0"]).to(device) if z0 is None else z0
+    p = solver.build_problem(coeffs, m["kind"], z0, func.fused_spec(), m["method"],
+                             _lib.OUT_KNOTS if m["sequence"] else _lib.OUT_INTERVAL, flags)
+    return p, func, (coeffs, z0)
+
+
 def run_case(case, flags=_lib.FLAG_AUTO, device="cuda", need_grads=True, adjoint=True):
     """-> dict(z_out, dz0, grads{name: array}) computed by the HIP path (adjoint=False: exact discrete backward)."""
     m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
-    X = (ncde_amd.LinearInterpolation if m["kind"] == "linear" else ncde_amd.NaturalCubicSpline)(coeffs)
+    X = case_control(case, device)
     func = case_field(case, device)
     z0 = torch.from_numpy(case["z0"]).to(device).requires_grad_(True)
     t = X.grid_points if m["sequence"] else X.interval
@@ -52,8 +70,7 @@ def run_case(case, flags=_lib.FLAG_AUTO, device="cuda", need_grads=True, adjoint
 def run_case_async(case, flags=_lib.FLAG_AUTO, device="cuda"):
     """The forward solve of `case` enqueued on the CURRENT stream; returns the device tensor without synchronising."""
     m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
-    X = (ncde_amd.LinearInterpolation if m["kind"] == "linear" else ncde_amd.NaturalCubicSpline)(coeffs)
+    X = case_control(case, device)
     func = case_field(case, device)
     z0 = torch.from_numpy(case["z0"]).to(device)
     with torch.no_grad():
@@ -71,30 +88,13 @@ def run_adjoint_direct(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=
 def prepare_adjoint(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None):
     """The device inputs and (NaN-filled) gradient buffers of one run_adjoint_direct call, uploaded on the current stream."""
     from ncde_amd import solver
-    m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
-    func = case_field(case, device)
-    spec = func.fused_spec()
     z_out = torch.from_numpy(np.ascontiguousarray(z_out)).to(device)
     gout = torch.from_numpy(case["expect"]["grad_out"]).to(device).contiguous()
-    z0 = z_out[:, 0].contiguous()
-    p = solver.build_problem(coeffs, m["kind"], z0, spec, m["method"],
-                             _lib.OUT_KNOTS if m["sequence"] else _lib.OUT_INTERVAL, flags)
-    uniq = spec.unique_params()
-    gbuf = {id(q): torch.full_like(q, float("nan")) for q in uniq}
-    g = _lib.NcdeGrads()
-    gz0 = torch.full_like(z0, float("nan"))
-    g.grad_z0 = gz0.data_ptr()
-    for i, (w, b) in enumerate(spec.layers):
-        g.grad_layer_W[i], g.grad_layer_b[i] = gbuf[id(w)].data_ptr(), gbuf[id(b)].data_ptr()
-    g.grad_Wo, g.grad_bo = gbuf[id(spec.Wo)].data_ptr(), gbuf[id(spec.bo)].data_ptr()
-    if spec.kind != "original":
-        g.grad_Wg, g.grad_bg = gbuf[id(spec.Wg)].data_ptr(), gbuf[id(spec.bg)].data_ptr()
-    if spec.kind == "gru":
-        g.grad_Wr, g.grad_br = gbuf[id(spec.Wr)].data_ptr(), gbuf[id(spec.br)].data_ptr()
+    p, func, keep = case_problem(case, flags, device, z0=z_out[:, 0].contiguous())
+    bound = solver.bind_grads(func.fused_spec(), keep[1].shape, device, fill=float("nan"))
     rec = None if stages is None else torch.from_numpy(np.ascontiguousarray(stages)).to(device)
-    return {"p": p, "g": g, "gz0": gz0, "gbuf": gbuf, "func": func, "z_out": z_out, "gout": gout, "rec": rec, "device": device,
-            "keep": (coeffs, z0)}
+    return {"p": p, "g": bound.g, "gz0": bound.grad_z0, "gbuf": bound.bufs, "func": func, "z_out": z_out, "gout": gout, "rec": rec,
+            "device": device, "keep": keep}
 
 
 def workspace(prep):
@@ -134,12 +134,7 @@ def coop_status_word(case, pass_, flags=_lib.FLAG_AUTO, device="cuda"):
     workspace arena of the current stream (no other call in between); None if the pass launches nothing cooperative."""
     import ctypes
     from ncde_amd import solver
-    m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
-    func = case_field(case, device)
-    z0 = torch.from_numpy(case["z0"]).to(device)
-    p = solver.build_problem(coeffs, m["kind"], z0, func.fused_spec(), m["method"],
-                             _lib.OUT_KNOTS if m["sequence"] else _lib.OUT_INTERVAL, flags)
+    p, _, _keep = case_problem(case, flags, device)
     off = _lib.lib().ncde_coop_status_offset(ctypes.byref(p), pass_)
     if off < 0:
         return None
@@ -151,13 +146,7 @@ def coop_status_word(case, pass_, flags=_lib.FLAG_AUTO, device="cuda"):
 def kernel_names(case, flags=_lib.FLAG_AUTO, device="cuda"):
     """(forward, adjoint, discrete backward) kernel family names the C-ABI would dispatch this case to."""
     import ctypes
-    from ncde_amd import solver
-    m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
-    func = case_field(case, device)
-    z0 = torch.from_numpy(case["z0"]).to(device)
-    p = solver.build_problem(coeffs, m["kind"], z0, func.fused_spec(), m["method"],
-                             _lib.OUT_KNOTS if m["sequence"] else _lib.OUT_INTERVAL, flags)
+    p, _, _keep = case_problem(case, flags, device)
     lib = _lib.lib()
     return tuple((lib.ncde_kernel_name(ctypes.byref(p), k) or b"?").decode() for k in (0, 1, 2))
 

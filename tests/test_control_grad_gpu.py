@@ -134,13 +134,10 @@ def _abi_backward(lib, f, m, control, flags=0):
     ws = ws_for(lib.ncde_workspace_bytes(ctypes.byref(p), 0))
     assert lib.ncde_forward_record(ctypes.byref(p), out.data_ptr(), stages.data_ptr(), ws.data_ptr(), ws.numel(), stream) == 0
     p = solver.build_problem(coeffs, m["interp"], z0, spec, m["method"], output, flags, plan)
-    bufs = {"z0": torch.full_like(z0, float("nan"))}
-    bufs.update({k: torch.full_like(v, float("nan")) for k, v in func.p.items()})
-    g = _lib.NcdeGrads()
-    g.grad_z0 = bufs["z0"].data_ptr()
-    for i, (w, b) in enumerate([("W0", "b0")] + [("W1", "b1")] * (m["dims"]["nl"] - 1)):
-        g.grad_layer_W[i], g.grad_layer_b[i] = bufs[w].data_ptr(), bufs[b].data_ptr()
-    g.grad_Wo, g.grad_bo = bufs["Wo"].data_ptr(), bufs["bo"].data_ptr()
+    bound = solver.bind_grads(spec, z0.shape, z0.device, fill=float("nan"))
+    g = bound.g
+    bufs = {"z0": bound.grad_z0}
+    bufs.update({k: bound.of(v) for k, v in func.p.items()})
     gout = torch.from_numpy(f["grad_out"]).cuda()
     gc = None
     if control:
@@ -170,6 +167,43 @@ def test_control_backward_is_ncde_backward_plus_grad_coeffs(name, window, gpu_li
         assert np.isfinite(base[k]).all() and np.array_equal(base[k], one[k]) and np.array_equal(one[k], two[k]), k
     assert np.isfinite(gc1).all() and np.array_equal(gc1, gc2)
     assert gu.relerr(gc1, f["dcoeffs"]) <= E2E_G
+
+
+def test_control_route_under_no_grad_keeps_no_stage_record(gpu_lib):
+    """Case a through cdeint under torch.no_grad(): the same bits as with grad enabled, on the fused route (no warning), and the
+    stage record is never sized -- ncde_stage_record_bytes is counted for the duration of the two calls: 0 queries, then 1."""
+    import gpu_util
+    import ncde_amd
+    from ncde_amd import unfused
+    f, m = _load("g16_a_rect_rk4_interval")
+    unfused._WARNED.clear()
+    coeffs = torch.from_numpy(f["coeffs"]).cuda().requires_grad_(True)
+    X = _control(f, m, coeffs)
+    func = gpu_util.CaseField({k[2:]: f[k] for k in f if k.startswith("p_")}, [("W0", "b0")] + [("W1", "b1")] * (m["dims"]["nl"] - 1), "cuda")
+    z0 = torch.from_numpy(f["z0"]).cuda().requires_grad_(True)
+    real, queries = gpu_lib.ncde_stage_record_bytes, []
+
+    def counted(p):
+        queries.append(1)
+        return real(p)
+
+    def solve():
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            return ncde_amd.cdeint(X, func, z0, _times(f, m, X), adjoint=False, method=m["method"], options={"step_size": m["step_size"]})
+    gpu_lib.ncde_stage_record_bytes = counted
+    try:
+        with torch.no_grad():
+            quiet = solve()
+        n_quiet = len(queries)
+        taped = solve()
+    finally:
+        gpu_lib.ncde_stage_record_bytes = real
+    assert n_quiet == 0 and len(queries) == 1, (n_quiet, len(queries))
+    assert not unfused._WARNED, unfused._WARNED
+    assert not quiet.requires_grad and taped.requires_grad
+    assert quiet.shape == f["z_out"].shape and torch.equal(quiet.view(torch.int32), taped.detach().view(torch.int32))
+    assert gu.relerr(quiet.cpu().numpy(), f["z_out"]) <= TIGHT_Z
 
 
 @pytest.mark.parametrize("seq", [True, False])

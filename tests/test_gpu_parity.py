@@ -1953,6 +1953,44 @@ def test_dopri5_max_num_steps_counts_per_output_and_frozen_parameters(gpu_lib):
     assert func.p["W0"].grad is None and func.p["W1"].grad is None and func.p["Wo"].grad is not None
 
 
+def test_dopri5_adjoint_params_subset_binds_null_for_the_rest(gpu_lib):
+    """adjoint_params = (Wo, bo), a strict subset of the field's parameters, on the smallest g10 case with the reference's step
+    sequences replayed: the NcdeGrads the library receives carries NULL for every excluded tensor (seen through bind_grads' `live`
+    argument and the struct it returns), the excluded parameters' .grad stays None, and -- the step sequence being forced, each
+    segment of the augmented state integrates on its own -- dL/dz0, dL/dWo and dL/dbo still meet the golden."""
+    import ncde_amd
+    from ncde_amd import _lib, solver
+    f, m, X, func, z0, t = _dopri5_golden_setup("g10_ncde_dopri5_cubic_final")
+    opts = dict(m["options"])
+    fwd = dict(opts, _replay=[[r[1], r[2]] for r in m["trace_fwd"]])
+    bwd = dict(opts, _replay=[[r[1], r[2]] for r in m["trace_bwd"]])
+    real, seen = solver.bind_grads, []
+
+    def spy(spec, z0_shape, device, live=None, fill=None):
+        bound = real(spec, z0_shape, device, live, fill)
+        seen.append((live, bound))
+        return bound
+    solver.bind_grads = spy
+    try:
+        out = ncde_amd.cdeint(X, func, z0, t, adjoint=True, method="dopri5", rtol=m["rtol"], atol=m["atol"], options=fwd, adjoint_options=bwd,
+                              adjoint_params=(func.p["Wo"], func.p["bo"]))
+        (out * torch.from_numpy(f["grad_out"]).cuda()).sum().backward()
+    finally:
+        solver.bind_grads = real
+    assert len(seen) == 1
+    live, bound = seen[0]
+    assert live == {id(func.p["Wo"]), id(func.p["bo"])}
+    g = bound.g
+    assert g.grad_z0 and g.grad_Wo == bound.of(func.p["Wo"]).data_ptr() and g.grad_bo == bound.of(func.p["bo"]).data_ptr()
+    assert all(g.grad_layer_W[i] is None and g.grad_layer_b[i] is None for i in range(_lib.NCDE_MAX_LAYERS))
+    assert g.grad_Wg is None and g.grad_bg is None and g.grad_Wr is None and g.grad_br is None
+    for k in ("W0", "b0", "W1", "b1"):
+        assert func.p[k].grad is None, k
+    assert gu.relerr(z0.grad.cpu().numpy(), f["dz0"]) <= E2E_G
+    for k in ("Wo", "bo"):
+        assert gu.relerr(func.p[k].grad.cpu().numpy(), f["d" + k]) <= E2E_G, k
+
+
 @pytest.mark.parametrize("interp,seq", [("linear", False), ("linear", True), ("cubic", False), ("cubic", True)])
 def test_dopri5_forced_step_sequence_vs_oracle(interp, seq, gpu_lib):
     """dopri5 with first_step = min_step = max_step = 0.5: every attempt has dt = 0.5 and is accepted (rk_common.py:262-266), so

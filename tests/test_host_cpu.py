@@ -530,3 +530,75 @@ def test_dispatch_table_matches_the_recorded_one():
     for row in fx["rows"]:
         case = dict(zip(fx["keys"], row[:nk]))
         assert dt.query(h, case) == row[nk:], case
+
+
+def _grad_slots(g, nl):
+    """Every destination of an NcdeGrads as {name: address or None}."""
+    d = {"z0": g.grad_z0}
+    for i in range(nl):
+        d["W%d" % i], d["b%d" % i] = g.grad_layer_W[i], g.grad_layer_b[i]
+    d.update({k: getattr(g, "grad_" + k) for k in ("Wo", "bo", "Wg", "bg", "Wr", "br")})
+    return d
+
+
+def _cpu_spec(kind="original", H=4, C=3, HH=6):
+    P = lambda *s: torch.nn.Parameter(torch.zeros(*s))      # noqa: E731
+    W0, b0, W1, b1, Wo, bo = P(HH, H), P(HH), P(HH, HH), P(HH), P(H * C, HH), P(H * C)
+    heads = {} if kind == "original" else {"Wg": P(H * C, HH), "bg": P(H * C)}
+    if kind == "gru":
+        heads.update(Wr=P(H, H), br=P(H))
+    return ncde_amd.FieldSpec([(W0, b0), (W1, b1), (W1, b1)], Wo, bo, kind=kind, **heads)
+
+
+def test_bind_grads_shares_one_buffer_per_unique_parameter():
+    """nl = 3 with layers 1 and 2 sharing one (W1, b1): both layer indices are bound to ONE buffer, every bound address is the
+    buffer bind_grads hands back for that parameter, and there are as many buffers as unique parameters."""
+    spec = _cpu_spec()
+    bound = solver.bind_grads(spec, (5, 4), "cpu")
+    g = bound.g
+    assert g.grad_layer_W[1] == g.grad_layer_W[2] and g.grad_layer_W[1] != g.grad_layer_W[0]
+    assert g.grad_layer_b[1] == g.grad_layer_b[2] and g.grad_layer_b[1] != g.grad_layer_b[0]
+    for i, (w, b) in enumerate(spec.layers):
+        assert g.grad_layer_W[i] == bound.of(w).data_ptr() and g.grad_layer_b[i] == bound.of(b).data_ptr()
+    assert g.grad_Wo == bound.of(spec.Wo).data_ptr() and g.grad_bo == bound.of(spec.bo).data_ptr()
+    assert g.grad_z0 == bound.grad_z0.data_ptr() and bound.grad_z0.shape == (5, 4) and bound.grad_z0.dtype == torch.float32
+    assert len(bound.bufs) == len(spec.unique_params()) == 6
+    assert len({buf.data_ptr() for buf in bound.bufs.values()}) == 6
+    assert all(g.grad_layer_W[i] is None and g.grad_layer_b[i] is None for i in range(3, _lib.NCDE_MAX_LAYERS))
+
+
+@pytest.mark.parametrize("kind,heads", [("original", ()), ("minimal", ("Wg", "bg")), ("gru", ("Wg", "bg", "Wr", "br"))])
+def test_bind_grads_binds_the_heads_of_the_field_kind(kind, heads):
+    spec = _cpu_spec(kind)
+    bound = solver.bind_grads(spec, (5, 4), "cpu")
+    for k in ("Wg", "bg", "Wr", "br"):
+        addr = getattr(bound.g, "grad_" + k)
+        if k in heads:
+            assert addr is not None and addr == bound.of(getattr(spec, k)).data_ptr(), k
+        else:
+            assert addr is None, k
+    assert len(bound.bufs) == 6 + len(heads)
+
+
+def test_bind_grads_restricted_live_set_leaves_the_rest_null():
+    """live = {Wo, b0}: exactly those two destinations and grad_z0 are bound (the dopri5 adjoint's "not in the augmented state")."""
+    spec = _cpu_spec("gru")
+    b0 = spec.layers[0][1]
+    bound = solver.bind_grads(spec, (5, 4), "cpu", live={id(spec.Wo), id(b0)})
+    slots = _grad_slots(bound.g, _lib.NCDE_MAX_LAYERS)
+    assert {k for k, v in slots.items() if v is not None} == {"z0", "Wo", "b0"}
+    assert slots["Wo"] == bound.of(spec.Wo).data_ptr() and slots["b0"] == bound.of(b0).data_ptr()
+
+
+def test_bind_grads_fill_and_non_contiguous_parameters():
+    """fill = NaN reaches every element of every buffer; the buffer of a parameter that is a transposed view is contiguous and has
+    the parameter's shape (the kernels write dense rows)."""
+    spec = _cpu_spec("gru")
+    spec.Wo = torch.nn.Parameter(torch.zeros(6, 12)).t()
+    assert not spec.Wo.is_contiguous()
+    bound = solver.bind_grads(spec, (5, 4), "cpu", fill=float("nan"))
+    assert len(bound.bufs) == 10
+    assert all(torch.isnan(buf).all() for buf in bound.bufs.values()) and torch.isnan(bound.grad_z0).all()
+    assert bound.of(spec.Wo).is_contiguous() and bound.of(spec.Wo).shape == spec.Wo.shape == (12, 6)
+    plain = solver.bind_grads(spec, (5, 4), "cpu")
+    assert plain.of(spec.Wo).is_contiguous() and plain.of(spec.Wo).shape == (12, 6)
