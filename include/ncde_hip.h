@@ -379,6 +379,17 @@ const char* ncde_prepare_kernel_name(int kind, int B, int L, int C, int has_grid
 int ncde_smooth_pieces(int T, double eps);
 int ncde_prepare_smooth(const float* x, int B, int T, int C, double eps, int order, float* out, void* stream);
 
+/* Transpose of ncde_prepare_smooth for cubic matching: what autograd hands back to the linear coefficients through
+ * _setup_cubic_matching_coefficients (src/ncde/interpolation.py:146-158) when a SmoothLinearInterpolation is built on a tensor that
+ * requires grad and the solve is taped (adjoint=False).  The builder is linear in x with weights that depend on eps only
+ * (2c = (4 / eps) jump, 3d = (-3 / eps^2) jump, jump = x[k+1] - 2 x[k] + x[k-1]; the linear rest starts at x[k] + eps (x[k+1] - x[k])).
+ *   grad_rows [B, P, 4C], P = ncde_smooth_pieces(T, eps): dL/d(a | b | 2c | 3d) of every piece (e.g. grad_coeffs of ncde_backward_control)
+ *   grad_x    [B, T, C], written completely
+ * One launch on `stream`, one thread per element of grad_x summing the at most 5 pieces that read that knot in a fixed order: no
+ * atomics, no workspace, bit-reproducible.  order 3 only: order 5 answers NCDE_ERR_UNSUPPORTED (ncde_last_error_string() says so);
+ * other bad arguments NCDE_ERR_INVALID, as for ncde_prepare_smooth. */
+int ncde_prepare_smooth_backward(const float* grad_rows, int B, int T, int C, double eps, int order, float* grad_x, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,7 +117,7 @@ EXPORTS = (
     "ncde_kernel_name", "ncde_forward", "ncde_adjoint", "ncde_time_kernel",
     "ncde_prepare_workspace_bytes", "ncde_prepare_linear", "ncde_prepare_cubic", "ncde_prepare_linear_grid", "ncde_prepare_cubic_grid",
     "ncde_prepare_kernel_name",
-    "ncde_smooth_pieces", "ncde_prepare_smooth",
+    "ncde_smooth_pieces", "ncde_prepare_smooth", "ncde_prepare_smooth_backward",
     "ncde_stage_record_bytes", "ncde_forward_record", "ncde_backward",
     "ncde_time_plan_build", "ncde_dopri5_workspace_bytes", "ncde_dopri5_forward", "ncde_dopri5_adjoint",
     "ncde_dopri5_record_bytes", "ncde_dopri5_forward_record", "ncde_dopri5_backward", "ncde_dopri5_kernel_name",
@@ -201,6 +201,8 @@ def lib():
     h.ncde_smooth_pieces.restype = ctypes.c_int
     h.ncde_prepare_smooth.argtypes = [vp, i32, i32, i32, ctypes.c_double, i32, vp, vp]
     h.ncde_prepare_smooth.restype = ctypes.c_int
+    h.ncde_prepare_smooth_backward.argtypes = [vp, i32, i32, i32, ctypes.c_double, i32, vp, vp]
+    h.ncde_prepare_smooth_backward.restype = ctypes.c_int
     h.ncde_prepare_linear_grid.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     h.ncde_prepare_linear_grid.restype = ctypes.c_int
     h.ncde_prepare_cubic_grid.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]

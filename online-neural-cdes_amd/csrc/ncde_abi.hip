@@ -538,6 +538,8 @@ int pass_in_range(int pass) { return pass < 0 || pass > 2 ? fail(NCDE_ERR_INVALI
 
 }  // namespace
 
+int ncde_fail_text(int code, const char* text) { return fail(code, "%s", text); }
+
 extern "C" {
 
 int ncde_version(void) { return NCDE_ABI_VERSION; }

@@ -21,6 +21,9 @@ extern "C" __global__ void ncde_reduce_partials(const float* gpart, int n_part, 
 
 constexpr int kLdsLimit = 160 * 1024;
 
+// ncde_abi.hip: `text` becomes the calling thread's ncde_last_error_string(); returns `code` (for entry points of other units)
+int ncde_fail_text(int code, const char* text);
+
 // Internal flag (not in include/ncde_hip.h): the development adjoint kernels of the (32, 32, 20) set (ncde_adj_fast / ncde_adj_fast2,
 // cubic + midpoint only) also write the per-stage chain values of workgroup 0 to the tail of the workspace, and every split-GEMM
 // choice of that set falls back to split-bf16.  A problem that carries it is never zero-padded onto a kernel set.

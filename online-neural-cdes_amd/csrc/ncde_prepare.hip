@@ -685,9 +685,60 @@ __global__ __launch_bounds__(256) void ncde_smooth_coeffs_kernel(const float* __
     }
 }
 
+// Transpose of the cubic builder above: dL/d(rows) [B, P, 4C] -> dL/dx [B, T, C].  In exact arithmetic the rows are linear in x with
+// weights that depend on eps only (jump_k = x[k+1] - 2 x[k] + x[k-1]):
+//   piece 0            a = x[0]                        b = x[1] - x[0]
+//   matching piece M(k) a = x[k]                        b = x[k] - x[k-1]      2c = (4 / eps) jump_k      3d = (-3 / eps^2) jump_k
+//   linear rest  R(k)  a = x[k] + eps (x[k+1] - x[k])  b = x[k+1] - x[k]      (eps < 1 only)
+// Gather form: one thread per (sample, knot t, channel) sums what the pieces that read x[t] hand back, in ascending piece order --
+// piece 0 (t <= 1), M(t-1), R(t-1), M(t), R(t), M(t+1): at most 5 pieces (3 for eps == 1).  Plain loads and one store per element,
+// no atomics, no workspace: bit-reproducible, and grad_x is written completely.
+struct SmoothBwdScal { float w2, w3, eps, one_m_eps; };
+__global__ __launch_bounds__(256) void ncde_smooth_coeffs_bwd_kernel(const float* __restrict__ g, int B, int T, int C, int P, bool split,
+                                                                     SmoothBwdScal k, float* __restrict__ gx) {
+    const long long total = (long long)B * T * C, row = 4LL * C;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int c = (int)(e % C), t = (int)((e / C) % T), b = (int)(e / ((long long)C * T));
+        const float* gs = g + (long long)b * P * row + c;
+        auto piece = [&](int kn) { return gs + (long long)(split ? 1 + 2 * (kn - 1) : kn) * row; };      // M(kn); R(kn) is the next row
+        auto interior = [&](int kn) { return kn >= 1 && kn <= T - 2; };
+        float acc = 0.0f;
+        if (t <= 1) acc = t == 0 ? gs[0] - gs[C] : gs[C];
+        if (interior(t - 1)) {                 // x[t] is the knot after: it enters the jump, and the rest piece's end
+            const float* r = piece(t - 1);
+            acc += k.w2 * r[2 * C] + k.w3 * r[3 * C];
+            if (split) acc += k.eps * r[row] + r[row + C];
+        }
+        if (interior(t)) {                     // x[t] is the knot itself
+            const float* r = piece(t);
+            const float s = k.w2 * r[2 * C] + k.w3 * r[3 * C];
+            acc += (r[0] + r[C]) - 2.0f * s;
+            if (split) acc += k.one_m_eps * r[row] - r[row + C];
+        }
+        if (interior(t + 1)) {                 // x[t] is the knot before: the incoming slope and the jump
+            const float* r = piece(t + 1);
+            acc += (k.w2 * r[2 * C] + k.w3 * r[3 * C]) - r[C];
+        }
+        gx[e] = acc;
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+int ncde_prepare_smooth_backward(const float* grad_rows, int B, int T, int C, double eps, int order, float* grad_x, void* stream) {
+    if (!grad_rows || !grad_x || B < 1 || T < 2 || C < 1 || (order != 3 && order != 5) || !(eps > 0.0) || eps > 1.0) return NCDE_ERR_INVALID;
+    if (order != 3)
+        return ncde_fail_text(NCDE_ERR_UNSUPPORTED, "ncde_prepare_smooth_backward: order 5 (quintic matching) has no transpose kernel; order 3 only");
+    const int P = ncde_smooth_pieces(T, eps);
+    SmoothBwdScal k;      // evaluated in double, rounded once
+    k.w2 = (float)(4.0 / eps); k.w3 = (float)(-3.0 / (eps * eps)); k.eps = (float)eps; k.one_m_eps = (float)(1.0 - eps);
+    const long long total = (long long)B * T * C;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(ncde_smooth_coeffs_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, grad_rows, B, T, C, P, eps < 1.0, k, grad_x);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+}
 
 int ncde_smooth_pieces(int T, double eps) {
     if (T < 2 || !(eps > 0.0) || eps > 1.0) return NCDE_ERR_INVALID;

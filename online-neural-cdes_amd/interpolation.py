@@ -178,6 +178,10 @@ class SmoothLinearInterpolation(_ControlBase):
     ``fused_coeffs`` (built once per object by ``ncde_prepare_smooth``) is an ordinary ``a | b | 2c | 3d`` tensor for cubic matching
     -- every fused kernel family runs it -- and ``a | b | 2c | 3d | 4e | 5f`` (``NCDE_INTERP_QUINTIC``) for quintic matching.
     ``n_knots`` stays T (it describes ``grid_points``); the refined grid reaches the kernels through ``_plan_grid`` only.
+
+    Coefficients that require grad (``adjoint=False``): with cubic matching the solve stays fused -- ``fused_coeffs`` is built from the
+    detached coefficients and ``cdeint`` folds dL/d(rows) back onto them with ``ncde_prepare_smooth_backward`` (solver.py); quintic
+    matching and ``gradient_matching_eps=None`` run on the unfused solver.
     """
 
     def __init__(self, coeffs, t=None, gradient_matching_eps=None, match_second_derivatives=False, **kwargs):

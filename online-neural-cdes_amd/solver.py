@@ -382,13 +382,17 @@ class _FusedCdeint(torch.autograd.Function):
     taped (solver.py:224), without a tape.
     cfg["control"] (adjoint=False with a coefficient tensor that requires grad; a stacked CDE: layer i's hidden sequence is layer
     i+1's linear coefficients): `coeffs` is a differentiable input, the forward keeps its usual route and the backward is
-    ncde_backward_control -- ncde_backward on the batch-tiled family plus dL/dcoeffs (pass C: ncde_dctl_tiled + ncde_dctl_fold)."""
+    ncde_backward_control -- ncde_backward on the batch-tiled family plus dL/dcoeffs (pass C: ncde_dctl_tiled + ncde_dctl_fold).
+    cfg["smooth"] = (rows, eps) on that route (a cubic-smoothed control): `coeffs` is still the differentiable input, the LINEAR
+    coefficients [B, T, C]; the kernels read `rows`, the a | b | 2c | 3d tensor ncde_prepare_smooth built from them, and the backward
+    folds ncde_backward_control's dL/d(rows) back onto the linear coefficients with ncde_prepare_smooth_backward."""
 
     @staticmethod
     def forward(ctx, z0, coeffs, cfg, *params):
         control = bool(cfg.get("control"))
         if control:
-            coeffs = coeffs.detach()
+            ctx.x_shape = coeffs.shape
+            coeffs = cfg["smooth"][0] if cfg.get("smooth") else coeffs.detach()
         z0c = z0.detach().contiguous()
         p = build_problem(coeffs, cfg["interp"], z0c, cfg["spec"], cfg["method"], cfg["output"], cfg["flags"], cfg["plan"])
         out = _alloc_out(z0, _num_outputs(coeffs, cfg["interp"], cfg["output"], cfg["plan"]))
@@ -421,6 +425,12 @@ class _FusedCdeint(torch.autograd.Function):
                 ws = _workspace_bytes(_lib.check(lib.ncde_control_workspace_bytes(ctypes.byref(p)), "ncde_control_workspace_bytes"), dev)
                 rc = lib.ncde_backward_control(ctypes.byref(p), stages.data_ptr(), grad_out.data_ptr(), ctypes.byref(bound.g),
                                                grad_coeffs.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr())
+                if rc >= 0 and cfg.get("smooth"):      # dL/d(rows) -> dL/d(linear coefficients), same stream
+                    name = "ncde_prepare_smooth_backward"
+                    B, T, C = ctx.x_shape
+                    grad_rows, grad_coeffs = grad_coeffs, torch.empty(ctx.x_shape, dtype=torch.float32, device=dev)
+                    rc = lib.ncde_prepare_smooth_backward(grad_rows.data_ptr(), B, T, C, float(cfg["smooth"][1]), 3, grad_coeffs.data_ptr(),
+                                                          _stream_ptr())
             elif ctx.recorded:
                 name = "ncde_backward"
                 ws = _workspace(p, 2, dev)
@@ -446,16 +456,23 @@ _CONTROL_REASON = "the control path requires gradients"
 
 def _control_route(reason, adjoint, method, plain_control, cuda_fp32, coeffs_grad, other_grad, t_grad):
     """The routing decision on plain values: a call that `_unfused_reason` sends away for `reason` may take the fused
-    control-gradient route iff adjoint=False, a fixed-step method, a plain LinearInterpolation / NaturalCubicSpline (`plain_control`),
-    z0 and the coefficients CUDA fp32 (`cuda_fp32`), the coefficient tensor requires grad and is the control's only buffer that does
-    (knots that require grad stay unfused), and `t` does not."""
+    control-gradient route iff adjoint=False, a fixed-step method, a plain LinearInterpolation / NaturalCubicSpline or a cubic-smoothed
+    SmoothLinearInterpolation (`plain_control`), z0 and the coefficients CUDA fp32 (`cuda_fp32`), the coefficient tensor requires grad
+    and is the control's only buffer that does (knots that require grad stay unfused), and `t` does not."""
     return bool(reason == _CONTROL_REASON and not adjoint and method in _FIXED_METHODS and plain_control and cuda_fp32 and
                 coeffs_grad and not other_grad and not t_grad)
 
 
+def _cubic_smoothed(X):
+    """A SmoothLinearInterpolation whose fused form is an a | b | 2c | 3d tensor with a transpose kernel (ncde_prepare_smooth_backward):
+    cubic matching on the integer grid.  Quintic matching, no smoothing at all and a user `t` are not."""
+    return (type(X) is SmoothLinearInterpolation and X.gradient_matching_eps is not None and not X.match_second_derivatives
+            and X._integer_grid)
+
+
 def _control_route_ok(reason, X, z0, t, adjoint, method):
     """`_control_route` of a call's arguments (looks at the arguments only: type, device, dtype, requires_grad)."""
-    if type(X) not in (LinearInterpolation, NaturalCubicSpline) or not torch.is_tensor(z0):
+    if not (type(X) in (LinearInterpolation, NaturalCubicSpline) or _cubic_smoothed(X)) or not torch.is_tensor(z0):
         return False
     coeffs = X._coeffs
     cuda_fp32 = z0.is_cuda and coeffs.is_cuda and z0.dtype == torch.float32 and coeffs.dtype == torch.float32
@@ -516,17 +533,21 @@ def _fused_control(X, func, z0, t, vector_field_type, method, options, flags):
     if not all(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() for q in uniq):
         return None
     z0, coeffs = _flatten_batch(z0, coeffs)
+    smooth = None
+    if _cubic_smoothed(X):      # the kernels read the refined rows (built from the detached coefficients, cached per tensor version)
+        rows = X.fused_coeffs
+        smooth = (rows.reshape(-1, rows.shape[-2], rows.shape[-1]), X.gradient_matching_eps)
     flags = _coop_flags(flags, z0.device)
     axis = _fixed_axis(X, t, method, step, z0.device)
     if axis is None:
         return None
     output, plan, nfe, _ = axis
-    p = build_problem(coeffs.detach(), X.interp_name, z0.detach(), spec, method, output, flags, plan)
+    p = build_problem(smooth[0] if smooth else coeffs.detach(), X.interp_name, z0.detach(), spec, method, output, flags, plan)
     lib = _lib.lib()
     if lib.ncde_control_workspace_bytes(ctypes.byref(p)) < 0 or lib.ncde_workspace_bytes(ctypes.byref(p), 0) < 0:
         return None
     cfg = {"spec": spec, "interp": X.interp_name, "method": method, "output": output, "flags": flags, "plan": plan,
-           "needs_grad": torch.is_grad_enabled(), "adjoint": False, "control": True}
+           "needs_grad": torch.is_grad_enabled(), "adjoint": False, "control": True, "smooth": smooth}
     out = _FusedCdeint.apply(z0, coeffs, cfg, *uniq)
     if hasattr(func, "nfe"):
         func.nfe += nfe

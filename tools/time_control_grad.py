@@ -6,6 +6,8 @@
   (ii)  coefficients with grad on the fused route (ncde_backward_control: (i) on fp32 records + pass C)
   (iii) the same request on the unfused torch-op solver (what it ran on before the route existed), FEWER timed steps (2) -- stated in the output
   (iv)  a two-layer StackedNeuralCDE step, hidden sizes 32 and 32, adjoint=False: fused, and (v) with the control route switched off
+  (vi)  coefficients with grad under interpolation="linear_cubic_smoothing", interpolation_eps 0.5, on the fused route (ncde_prepare_smooth,
+        the time plan of the refined grid, ncde_backward_control + ncde_prepare_smooth_backward), and (vii) with the route switched off
 The legs alternate: every round runs each leg once; the output holds every run, the median and the spread (max - min) / median."""
 import json, os, sys, time, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,9 +25,12 @@ lf = torch.nn.BCEWithLogitsLoss()
 route = solver._control_route_ok
 
 
-def make(stacked, flags=0):
+def make(stacked, flags=0, smooth=False):
     torch.manual_seed(0)
-    if stacked:
+    if smooth:
+        m = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation="linear_cubic_smoothing",
+                               interpolation_eps=0.5, adjoint=False, solver="rk4").cuda()
+    elif stacked:
         m = ncde_amd.StackedNeuralCDE(c["C"], [32, 32], 1, adjoint=False).cuda()
     else:
         m = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation="linear", adjoint=False,
@@ -37,7 +42,9 @@ LEGS = [("i: no control grad, FORCE_TILED", make(False, 0x8000), False, True, 8)
         ("ii: control grad, fused", make(False), True, True, 8),
         ("iii: control grad, unfused (2 timed steps)", make(False), True, False, 2),
         ("iv: stacked [32, 32], fused", make(True), False, True, 8),
-        ("v: stacked [32, 32], unfused (2 timed steps)", make(True), False, False, 2)]
+        ("v: stacked [32, 32], unfused (2 timed steps)", make(True), False, False, 2),
+        ("vi: cubic-smoothed eps 0.5, control grad, fused", make(False, smooth=True), True, True, 8),
+        ("vii: cubic-smoothed eps 0.5, control grad, unfused (2 timed steps)", make(False, smooth=True), True, False, 2)]
 runs = {k[0]: [] for k in LEGS}
 for rnd in range(int(arg("--rounds", 4))):
     for label, (m, opt), grad, fused, n in LEGS:
@@ -58,7 +65,8 @@ med = {k: sorted(v)[len(v) // 2] for k, v in runs.items()}
 k = [l[0] for l in LEGS]
 out = {"what": "tools/time_control_grad.py: adjoint=False training step at cfg2 dims (B %d, %d knots), ms; legs alternate within one session" % (B, coeffs.shape[1]),
        "runs_ms": runs, "median_ms": med, "spread": {q: round((max(v) - min(v)) / med[q], 3) for q, v in runs.items()},
-       "ii_over_i": round(med[k[1]] / med[k[0]], 3), "iii_over_ii": round(med[k[2]] / med[k[1]], 2), "v_over_iv": round(med[k[4]] / med[k[3]], 2)}
+       "ii_over_i": round(med[k[1]] / med[k[0]], 3), "iii_over_ii": round(med[k[2]] / med[k[1]], 2), "v_over_iv": round(med[k[4]] / med[k[3]], 2),
+       "vi_over_ii": round(med[k[5]] / med[k[1]], 3), "vii_over_vi": round(med[k[6]] / med[k[5]], 2)}
 print(json.dumps(out, indent=1))
 if arg("--out"):
     with open(arg("--out"), "w") as fh:
