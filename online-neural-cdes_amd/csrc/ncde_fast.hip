@@ -2134,13 +2134,17 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                             }
                         }
                 }
-                // From here on the activations are needed only as ReLU masks (x_L's B operand `xb` is already split): one bit each
-                // instead of 8 NL registers carried across the output tiles (round 4: the kernel's last 32 B / lane of scratch)
-                unsigned relu_mask = 0;
+                // From here on the activations are needed only as ReLU masks (x_L's B operand `xb` is already split): one wave lane
+                // mask each (a scalar register pair, ncde_fastdefs.h) instead of 8 NL registers carried across the output tiles
+                // (round 4 packed them into one bit each of a VGPR to shed the kernel's last 32 B / lane of scratch; the lane masks
+                // take no VGPR at all and cost one compare to build and one select to apply).  A lane mask is a WAVE-wide value:
+                // every branch between here and the gates below (wq, pw, j, the role split) is wave-uniform and all 64 lanes are
+                // active (invalid samples of a tail tile compute on zeros).  A lane-divergent branch around either end would break it.
+                LaneMask relu_on[NL][8];
 #pragma unroll
                 for (int l = 0; l < NL; ++l)
 #pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) relu_mask |= (x[l][jj] > 0.0f ? 1u : 0u) << (8 * l + jj);
+                    for (int jj = 0; jj < 8; ++jj) relu_on[l][jj] = lane_mask_gt0(x[l][jj]);
                 // ---- output tiles: P, r = 1/(exp(2P)+1), f, dP -> LDS tile + flag -----------------------------------
                 float kout[NB];
                 float sdx = 0.0f;
@@ -2198,7 +2202,7 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                     float v = red[(8 * g + jj) * 16 + s];
 #pragma unroll
                     for (int wv = 1; wv < NW; ++wv) v += red[wv * HH * 16 + (8 * g + jj) * 16 + s];
-                    gpre[jj] = ((relu_mask >> (8 * (NL - 1) + jj)) & 1u) ? v : 0.0f;
+                    gpre[jj] = lane_mask_gate(relu_on[NL - 1][jj], v);
                 }
                 // ---- hidden layers backward (split-bf16) -----------------------------------------------------------------
 #pragma unroll
@@ -2218,7 +2222,7 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                     for (int tt = 0; tt < HT; ++tt) {
                         const f32x4 gq = SO::finish(acc[tt]);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) gpre[4 * tt + r] = ((relu_mask >> (8 * (l - 1) + 4 * tt + r)) & 1u) ? gq[r] : 0.0f;
+                        for (int r = 0; r < 4; ++r) gpre[4 * tt + r] = lane_mask_gate(relu_on[l - 1][4 * tt + r], gq[r]);
                     }
                 }
                 if (wq != 0.0f && pw == 0) {

@@ -40,4 +40,11 @@ __device__ __forceinline__ float relu_bits(float x) {
     return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
 
+// ReLU gates of a backward pass as WAVE LANE MASKS: `x > 0` of all 64 lanes is one v_cmp result in a scalar register pair (no VGPR,
+// no bit twiddling), and gating a cotangent with it is one v_cndmask_b32 that takes the pair as its condition.  Strict: an
+// activation of exactly 0 (and a NaN) blocks the gradient.  Every lane of the wave must be active at both ends.
+typedef unsigned long long LaneMask;
+__device__ __forceinline__ LaneMask lane_mask_gt0(float x) { return __builtin_amdgcn_ballot_w64(x > 0.0f); }
+__device__ __forceinline__ float lane_mask_gate(LaneMask m, float v) { return __builtin_amdgcn_inverse_ballot_w64(m) ? v : 0.0f; }
+
 }  // namespace

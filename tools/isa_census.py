@@ -6,6 +6,7 @@ for this instruction stream (`valu_ceiling_ms`, `mfma_ceiling_ms` of bench.py's 
 
     python tools/isa_census.py            # -> profiles/r06_isa_census.json (+ a table on stdout)
     python tools/isa_census.py --list ncde_fast      # kernel symbols of one object
+    python tools/isa_census.py --per-role profiles/r07_isa_roles.json   # opcode histogram of each role's stage loop (cfg2), per stage
 
 How a count becomes a time: natural loops of the kernel's control-flow graph (dominator analysis on the disassembly); every
 instruction is weighted by the product of the trip counts of the loops around it; trip counts come from the workload (`table()` below,
@@ -268,11 +269,12 @@ def table():
     return {
         # cfg2: B = 4096 -> 256 workgroups of 16 samples.  Forward: ONE loop = the 398 steps, its body = the 4 stages unrolled.
         "cfg2.forward": dict(obj="ncde_fast_fwd3", frag="ncde_fwd_fast_bf3ILi32ELi32ELi20ELi4ELi0ELi2ELi0ELi3ELi1ELi0E", waves_per_simd=1, n_wg=256, wg_per_cu=1,
-                             trips=[T2 - 1]),
+                             trips=[T2 - 1], stages=4, role_names=["all"]),
         # adjoint: loop 0 prologue fill; loops 1-2 = the gradient waves' step / stage loops; 3-8 their flag polls; 9-10 = the chain
         # waves' step / stage loops.  One wave of each role per SIMD.
         "cfg2.backward": dict(obj="ncde_fast", frag="ncde_adj_fast3ILi3ELi20ELi0ELi2ELi0ELi0ELi2ELi0E", waves_per_simd=2, n_wg=256, wg_per_cu=1,
-                              trips=[1, T2 - 1, 4, 1, 1, 1, 1, 1, 1, T2 - 1, 4], roles=[[1, 2, 3, 4, 5, 6, 7, 8], [9, 10]]),
+                              trips=[1, T2 - 1, 4, 1, 1, 1, 1, 1, 1, T2 - 1, 4], roles=[[1, 2, 3, 4, 5, 6, 7, 8], [9, 10]],
+                              stages=4, role_names=["gradient", "chain"]),
         # cfg4: B = 8192 -> 512 workgroups; forward 2 per CU (4 waves each), backward 1 per CU (two rounds); midpoint: 2 stages
         "cfg4.forward": dict(obj="ncde_fast_fwd3", frag="ncde_fwd_fast_bf3ILi64ELi64ELi4ELi4ELi1ELi1ELi0ELi3ELi1ELi0E", waves_per_simd=1, n_wg=512, wg_per_cu=2,
                              trips=[T4 - 1]),
@@ -323,11 +325,65 @@ def census_for(keys=None):
     return {k: run(e) for k, e in table().items() if keys is None or k in keys}
 
 
+def per_role(entry):
+    """Opcode histogram of each role's stage loop, PER STAGE: the role's step loop (the first loop of its group in table(), the one
+    with the workload's step count) with every instruction weighted by the trip counts of the loops nested inside it, divided by the
+    stages of a step.  Nothing is looked for: every mnemonic that is there is counted and put into its issue class."""
+    dis = disassemble(os.path.join(ROOT, "online-neural-cdes_amd", "csrc", entry["obj"] + ".o"))
+    sym = find_symbol(dis, entry["frag"])
+    ins = dis[sym]
+    lp = loops_of(ins)
+    if len(lp) != len(entry["trips"]):
+        raise RuntimeError("%s: %d natural loops, the table lists %d trip counts -- the kernel changed, update table()" % (sym, len(lp), len(entry["trips"])))
+    groups = entry.get("roles") or [list(range(len(lp)))]
+    out = {"symbol": sym, "stages_per_step": entry["stages"], "roles": {}}
+    for name, grp in zip(entry["role_names"], groups):
+        step = grp[0]
+        body = set(lp[step][1])
+        weight = dict.fromkeys(body, 1.0 / entry["stages"])
+        inner = []
+        for k in grp[1:]:
+            if set(lp[k][1]) <= body:
+                inner.append({"head": "%x" % ins[lp[k][0]][0], "instructions": len(lp[k][1]), "trip": entry["trips"][k]})
+                for i in lp[k][1]:
+                    weight[i] *= entry["trips"][k]
+        ops, classes = Counter(), Counter()
+        for i, w in weight.items():
+            ops[ins[i][1]] += w
+            classes[classify(ins[i][1])[0]] += w
+        out["roles"][name] = {"step_loop": {"head": "%x" % ins[lp[step][0]][0], "instructions": len(body), "trip": entry["trips"][step]},
+                              "inner_loops": inner,
+                              "per_stage": {"instructions": round(sum(weight.values()), 2),
+                                            "by_class": {k: round(v, 2) for k, v in sorted(classes.items())},
+                                            "by_opcode": {k: round(v, 2) for k, v in sorted(ops.items(), key=lambda kv: (-kv[1], kv[0]))}}}
+    return out
+
+
+def main_per_role(path):
+    from ncde_amd import _lib
+    out = {}
+    for key in ("cfg2.backward", "cfg2.forward"):
+        out[key] = per_role(table()[key])
+        for name, r in out[key]["roles"].items():
+            ps = r["per_stage"]
+            print("%s  %s wave: %.1f instructions per stage (%s); step loop %d static" % (
+                key, name, ps["instructions"], ", ".join("%s %.1f" % kv for kv in ps["by_class"].items()), r["step_loop"]["instructions"]))
+            for mn, n in list(ps["by_opcode"].items())[:16]:
+                print("    %-34s %8.2f" % (mn, n))
+    json.dump(out, open(path, "w"), indent=1)
+    meta = {"source_fingerprint": _lib.source_fingerprint(), "tool": "tools/isa_census.py --per-role",
+            "note": "static opcode histogram per stage of each role's step loop, from the built gfx950 code objects"}
+    json.dump(meta, open(os.path.splitext(path)[0] + ".meta.json", "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--per-role", default=None, metavar="JSON", help="write the per-stage opcode histogram of each role's stage loop (cfg2) there")
     ap.add_argument("--list", default=None, help="object name (e.g. ncde_fast): print its kernel symbols and loop structure")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r06_isa_census.json"))
     a = ap.parse_args()
+    if a.per_role:
+        return main_per_role(a.per_role)
     if a.list:
         dis = disassemble(os.path.join(ROOT, "online-neural-cdes_amd", "csrc", a.list + ".o"))
         for s, ins in dis.items():
