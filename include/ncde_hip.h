@@ -123,7 +123,12 @@ typedef struct NcdeProblem {
      *   linear/rectilinear: coeffs[b][t][c], t < T           (linear_interpolation_coeffs output)
      *   cubic:              coeffs[b][p][4C] = a|b|2c|3d, p < T-1 (natural_cubic_coeffs output)
      *   quintic:            coeffs[b][p][6C] = a|b|2c|3d|4e|5f, p < T-1; with f = t - knot[p]:
-     *                       dX/dt = b + f(2c + f(3d + f(4e + f 5f))),  X = a + f(b + f(2c/2 + f(3d/3 + f(4e/4 + f 5f/5))))    */
+     *                       dX/dt = b + f(2c + f(3d + f(4e + f 5f))),  X = a + f(b + f(2c/2 + f(3d/3 + f(4e/4 + f 5f/5))))
+     * Stride contract (tests/test_strided_coeffs_gpu.py runs every kernel family on it): both strides count ELEMENTS (floats), the
+     * channel stride is 1.  coeffs_stride_b is any value >= 0 -- 0 (one path shared by the batch) and values smaller than one sample
+     * (overlapping samples) included; coeffs_stride_t is at least the row width (C, 4C, 6C), anything smaller is NCDE_ERR_INVALID.
+     * The pointer needs the alignment of a float (4 bytes) only, rows need not be 16-byte aligned, and b * coeffs_stride_b +
+     * t * coeffs_stride_t is formed in 64 bits: offsets up to 2^63 bytes.  Only rows t < T (p < T-1) of a sample are read.      */
     const float* coeffs;
     int64_t coeffs_stride_b;
     int64_t coeffs_stride_t;

@@ -499,11 +499,13 @@ def _fixed_axis(X, t, method, step, device):
 
 def _flatten_batch(z0, coeffs):
     """Any number of batch dimensions, as the reference allows, flattened for the kernels: z0 [B, H], coeffs [B, T, K] with unit
-    stride in K.  `_restore_batch` undoes it on the solution."""
+    stride in K and rows that do not overlap.  `_restore_batch` undoes it on the solution.  The batch and time strides are handed to
+    the kernels as they are (include/ncde_hip.h: any batch stride >= 0, a time stride of at least one row); a time stride smaller than
+    the row -- a constant path expanded over time has 0 -- is copied, as a non-unit channel stride is."""
     if z0.dim() != 2:
         z0 = z0.reshape(-1, z0.shape[-1])
         coeffs = coeffs.reshape(-1, coeffs.shape[-2], coeffs.shape[-1])
-    if coeffs.stride(2) != 1:
+    if coeffs.stride(2) != 1 or coeffs.stride(1) < coeffs.shape[2]:
         coeffs = coeffs.contiguous()
     return z0, coeffs
 

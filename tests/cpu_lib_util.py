@@ -54,6 +54,15 @@ class CpuCase:
         self.p, self.layers = p, layers
         self.n_out = p.n_knots if sequence else 2
 
+    def point_at(self, view):
+        """Read the coefficients through `view` instead: a float32 numpy view [B, R, K] of any batch / time strides (unit stride in
+        K) holding the same values; the problem takes its pointer and element strides as they are."""
+        assert view.dtype == np.float32 and view.shape == self.keep[0].shape and view.strides[2] == 4
+        assert view.strides[0] % 4 == 0 and view.strides[1] % 4 == 0
+        self.keep.append(view)
+        self.p.coeffs, self.p.coeffs_stride_b, self.p.coeffs_stride_t = ptr(view), view.strides[0] // 4, view.strides[1] // 4
+        return self
+
     def forward(self, record=False):
         out = np.empty((self.p.batch, self.n_out, self.p.hidden), np.float32)
         lib = cpu_lib()

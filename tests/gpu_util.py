@@ -28,18 +28,27 @@ def case_field(case, device):
     return CaseField(case["params"], case["layers"], device, m.get("field_kind", "original"), m.get("field_mode", "matmul"))
 
 
-def case_control(case, device):
-    """The control path of a golden case (default integer grid)."""
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
+def _case_coeffs(case, device, coeffs):
+    """The coefficient tensor of a case on the device: `coeffs` (a device tensor of any batch / time strides holding the case's
+    values, tests/strided_views.py), else a fresh contiguous upload."""
+    if coeffs is None:
+        return torch.from_numpy(case["coeffs"]).to(device)
+    assert tuple(coeffs.shape) == case["coeffs"].shape and coeffs.device.type == torch.device(device).type
+    return coeffs
+
+
+def case_control(case, device, coeffs=None):
+    """The control path of a golden case (default integer grid).  coeffs: this device tensor instead of a contiguous upload."""
+    coeffs = _case_coeffs(case, device, coeffs)
     return (ncde_amd.LinearInterpolation if case["meta"]["kind"] == "linear" else ncde_amd.NaturalCubicSpline)(coeffs)
 
 
-def case_problem(case, flags, device, z0=None):
+def case_problem(case, flags, device, z0=None, coeffs=None):
     """-> (the NcdeProblem of a golden case on its default axis, its field, the tensors the problem points into).  z0: start from
-    this state instead of the case's own."""
+    this state instead of the case's own.  coeffs: this device tensor (any batch / time strides) instead of a contiguous upload."""
     from ncde_amd import solver
     m = case["meta"]
-    coeffs = torch.from_numpy(case["coeffs"]).to(device)
+    coeffs = _case_coeffs(case, device, coeffs)
     func = case_field(case, device)
     z0 = torch.from_numpy(case["z0"]).to(device) if z0 is None else z0
     p = solver.build_problem(coeffs, m["kind"], z0, func.fused_spec(), m["method"],
@@ -47,16 +56,16 @@ def case_problem(case, flags, device, z0=None):
     return p, func, (coeffs, z0)
 
 
-def run_case(case, flags=_lib.FLAG_AUTO, device="cuda", need_grads=True, adjoint=True):
+def run_case(case, flags=_lib.FLAG_AUTO, device="cuda", need_grads=True, adjoint=True, coeffs=None):
     """-> dict(z_out, dz0, grads{name: array}) computed by the HIP path (adjoint=False: exact discrete backward)."""
     m = case["meta"]
-    X = case_control(case, device)
+    X = case_control(case, device, coeffs)
     func = case_field(case, device)
     z0 = torch.from_numpy(case["z0"]).to(device).requires_grad_(True)
     t = X.grid_points if m["sequence"] else X.interval
     out = ncde_amd.cdeint(X, func, z0, t, adjoint=adjoint, vector_field_type=func.mode, method=m["method"],
                           options={"step_size": 1}, kernel_flags=flags)
-    res = {"z_out": out.detach().cpu().numpy(), "nfe_fwd": func.nfe, "kernels": kernel_names(case, flags, device)}
+    res = {"z_out": out.detach().cpu().numpy(), "nfe_fwd": func.nfe, "kernels": kernel_names(case, flags, device, coeffs)}
     if need_grads:
         gout = torch.from_numpy(case["expect"]["grad_out"]).to(device)
         (out * gout).sum().backward()
@@ -78,19 +87,19 @@ def run_case_async(case, flags=_lib.FLAG_AUTO, device="cuda"):
                                method=m["method"], options={"step_size": 1}, kernel_flags=flags)
 
 
-def run_adjoint_direct(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None):
+def run_adjoint_direct(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None, coeffs=None):
     """Call ncde_adjoint through the C-ABI on a GIVEN forward solution (e.g. the reference's own z_out):
     isolates the adjoint kernel from forward round-off (a last-bit change of z can flip a ReLU mask).
     With `stages` (a stage record [(T-1)*S, B, H]) it calls ncde_backward (exact discrete backward) instead."""
-    return collect_adjoint(enqueue_adjoint(prepare_adjoint(case, z_out, flags, device, stages)))
+    return collect_adjoint(enqueue_adjoint(prepare_adjoint(case, z_out, flags, device, stages, coeffs)))
 
 
-def prepare_adjoint(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None):
+def prepare_adjoint(case, z_out, flags=_lib.FLAG_AUTO, device="cuda", stages=None, coeffs=None):
     """The device inputs and (NaN-filled) gradient buffers of one run_adjoint_direct call, uploaded on the current stream."""
     from ncde_amd import solver
     z_out = torch.from_numpy(np.ascontiguousarray(z_out)).to(device)
     gout = torch.from_numpy(case["expect"]["grad_out"]).to(device).contiguous()
-    p, func, keep = case_problem(case, flags, device, z0=z_out[:, 0].contiguous())
+    p, func, keep = case_problem(case, flags, device, z0=z_out[:, 0].contiguous(), coeffs=coeffs)
     bound = solver.bind_grads(func.fused_spec(), keep[1].shape, device, fill=float("nan"))
     rec = None if stages is None else torch.from_numpy(np.ascontiguousarray(stages)).to(device)
     return {"p": p, "g": bound.g, "gz0": bound.grad_z0, "gbuf": bound.bufs, "func": func, "z_out": z_out, "gout": gout, "rec": rec,
@@ -143,18 +152,19 @@ def coop_status_word(case, pass_, flags=_lib.FLAG_AUTO, device="cuda"):
     return int(ws[off:off + 4].view(torch.int32).cpu()[0])
 
 
-def kernel_names(case, flags=_lib.FLAG_AUTO, device="cuda"):
+def kernel_names(case, flags=_lib.FLAG_AUTO, device="cuda", coeffs=None):
     """(forward, adjoint, discrete backward) kernel family names the C-ABI would dispatch this case to."""
     import ctypes
-    p, _, _keep = case_problem(case, flags, device)
+    p, _, _keep = case_problem(case, flags, device, coeffs=coeffs)
     lib = _lib.lib()
     return tuple((lib.ncde_kernel_name(ctypes.byref(p), k) or b"?").decode() for k in (0, 1, 2))
 
 
 def run_times_case(f, meta, adjoint=True, flags=_lib.FLAG_AUTO, device="cuda", kind="original", mode="matmul", params=None,
-                   tagged=None):
-    """A general-time-axis case (golden g11 layout: coeffs, [knots], t_out, z0, p_*, grad_out) through cdeint."""
-    coeffs = torch.from_numpy(f["coeffs"]).to(device)
+                   tagged=None, coeffs=None):
+    """A general-time-axis case (golden g11 layout: coeffs, [knots], t_out, z0, p_*, grad_out) through cdeint.  coeffs: this device
+    tensor (any batch / time strides, the values of f["coeffs"]) instead of a contiguous upload."""
+    coeffs = torch.from_numpy(f["coeffs"]).to(device) if coeffs is None else coeffs
     kn = torch.from_numpy(f["knots"]).to(device) if "knots" in f else None
     X = (ncde_amd.LinearInterpolation if meta["kind"] == "linear" else ncde_amd.NaturalCubicSpline)(coeffs, t=kn)
     params = params if params is not None else {k[2:]: f[k] for k in f if k.startswith("p_")}
