@@ -178,22 +178,23 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
         // (any batch-tiled knob is a request for that family; the non-default adjoint variants exist for the exact shapes only)
         if (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | NCDE_FLAG_FORCE_TILED |
                         NCDE_FLAG_TILED_NS1 | NCDE_FLAG_TILED_NS2 | NCDE_FLAG_TILED_NS4 | NCDE_FLAG_TILED_WINDOW_STEPS(0xFF) | kFlagChainDump)) return P;
-        for (int l = 0; l < p->n_layers; ++l) {
+        for (int l = 0; l < p->n_layers; ++l)
             if (p->layer_out[l] > t->HH) return P;
-            if (l >= 1 && (p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1])) return P;
-        }
-        if (p->n_layers > 1 && (p->layer_W[1] == p->layer_W[0] || p->layer_b[1] == p->layer_b[0])) return P;
+        if (!ncde_one_shared_inner_layer(p)) return P;
     }
     NcdeProblem& q = P.q;
     q = *p;
     q.hidden = t ? t->H : hru16(p->hidden);
     q.channels = t ? t->C : hru4(p->channels);
     q.reserved_ = (p->hidden << 12) | p->channels;
+    constexpr int kMaxSeg = (int)(sizeof(P.real) / sizeof(P.real[0]));
     int n = 0;
+    bool full = false;      // a stack with more distinct parameters than the plan has segments: refused BEFORE the write past the arrays
     long long off = 0;
     auto add = [&](const float* src, int n0, int n1, int n2, int p0, int p1, int p2) {
         for (int k = 0; k < n; ++k)
             if (P.real[k] == src) return k;      // a shared layer: one padded copy
+        if (n >= kMaxSeg) { full = true; return 0; }
         const int k = n++;
         P.real[k] = src;
         P.dims[k][0] = n0; P.dims[k][1] = n1; P.dims[k][2] = n2; P.dims[k][3] = p0; P.dims[k][4] = p1; P.dims[k][5] = p2;
@@ -207,6 +208,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
         q.layer_in[l] = din; q.layer_out[l] = dout;
         P.slot_W[l] = add(p->layer_W[l], 1, p->layer_out[l], p->layer_in[l], 1, dout, din);
         P.slot_b[l] = add(p->layer_b[l], 1, 1, p->layer_out[l], 1, 1, dout);
+        if (full) return P;
         // the same real matrix must get the same padded shape in every slot it is used in
         if (P.dims[P.slot_W[l]][4] != dout || P.dims[P.slot_W[l]][5] != din || P.dims[P.slot_b[l]][5] != dout) return P;
         din = dout;
@@ -218,7 +220,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
         P.slot_Wg = add(p->Wg, p->hidden, p->channels, dl, q.hidden, q.channels, din);
         P.slot_bg = add(p->bg, 1, p->hidden, p->channels, 1, q.hidden, q.channels);
     }
-    if (n > 12) return P;
+    if (full) return P;
     P.n_seg = n;
     P.param_floats = (off + 63) & ~63LL;
     // bind to a fake base so that the support checks see aligned, distinct pointers (offset + 64 floats: never NULL)

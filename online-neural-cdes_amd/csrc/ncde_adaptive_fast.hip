@@ -21,6 +21,7 @@
 #include "ncde_bf3.h"
 #include "ncde_dp_defs.h"
 #include "ncde_fastdefs.h"
+#include "ncde_host.h"
 
 #ifdef NCDE_DPF_PROF      // development build (tools/build_dpfprof.sh): wall-clock stamps (10 ns) of workgroup 0 -> row 0 of sample 0 of `out`
 #define DPF_STAMP(k) if (blockIdx.x == 0 && threadIdx.x == 0) stamps_[k] = wall_clock64();
@@ -1739,11 +1740,11 @@ typedef void (*DpfKernel)(DpArgs);
 
 int dpf_shape(const NcdeProblem* p) {      // 0: none, 1: <32, 32, 20>, 2: <64, 64, 4>
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL) return 0;
-    if (p->n_layers < 1) return 0;
+    if (p->n_layers < 1 || !ncde_one_shared_inner_layer(p)) return 0;
     const int HH = p->layer_out[0];
     if (p->layer_in[0] != p->hidden) return 0;
     for (int l = 1; l < p->n_layers; ++l)
-        if (p->layer_out[l] != HH || p->layer_in[l] != HH || p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return 0;
+        if (p->layer_out[l] != HH || p->layer_in[l] != HH) return 0;
     if (p->hidden <= 32 && HH <= 32 && p->channels <= 20) return 1;
     if (p->hidden <= 64 && HH <= 64 && p->channels <= 4) return 2;
     return 0;

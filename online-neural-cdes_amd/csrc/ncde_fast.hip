@@ -2862,10 +2862,10 @@ constexpr int kAdjLayers = 3;
 
 const FastEntry* find_entry(const NcdeProblem* p) {
     // structure the fast family understands: layer 0 is H->HH, every further layer is ONE shared HH->HH
-    if (p->n_layers < 1) return nullptr;
+    if (p->n_layers < 1 || !ncde_one_shared_inner_layer(p)) return nullptr;
     const int HH = p->layer_out[0];
     for (int l = 1; l < p->n_layers; ++l)
-        if (p->layer_out[l] != HH || p->layer_in[l] != HH || p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return nullptr;
+        if (p->layer_out[l] != HH || p->layer_in[l] != HH) return nullptr;
     for (const FastEntry& e : kFast)
         if (e.H == p->hidden && e.HH == HH && e.C == p->channels) return &e;
     return nullptr;
@@ -2878,8 +2878,8 @@ int c_set(const NcdeProblem* p) {
     if (p->channels != 4 && p->channels != 8 && p->channels != 12) return 0;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL || p->output == NCDE_OUT_TIMES) return 0;
     for (int l = 1; l < p->n_layers; ++l)
-        if (p->layer_out[l] != 32 || p->layer_in[l] != 32 || p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return 0;
-    if (p->n_layers > 1 && (p->layer_W[1] == p->layer_W[0] || p->layer_b[1] == p->layer_b[0])) return 0;
+        if (p->layer_out[l] != 32 || p->layer_in[l] != 32) return 0;
+    if (!ncde_one_shared_inner_layer(p)) return 0;
     if (p->flags & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_ADJOINT_SPLIT_FP16 |
                     NCDE_FLAG_DEBUG_PROFILE | kFlagChainDump)) return 0;
     return p->channels;

@@ -55,6 +55,16 @@ inline hipError_t ncde_lds_optin(const void* fn, size_t bytes) {
     if (e == hipSuccess) have = bytes;
     return e;
 }
+// The one layer structure the shape-specialised kernel sets (register-resident, H = 64 in-sweep adjoint, fused dopri5, and the
+// zero-padding onto them) understand -- the reference's: layer 0, then ONE other layer shared by every further position, and no
+// aliasing between the two (neither the matrices nor the biases).  Their adjoints keep one gradient accumulator for layer 0 and
+// one for the shared layer and STORE each to its offset of the partial: with layer 1 tied back to layer 0 (make_layout gives the two
+// one offset) the second store would overwrite the first.  Widths are each caller's own check.
+inline bool ncde_one_shared_inner_layer(const NcdeProblem* p) {
+    for (int l = 2; l < p->n_layers; ++l)
+        if (p->layer_W[l] != p->layer_W[1] || p->layer_b[l] != p->layer_b[1]) return false;
+    return p->n_layers < 2 || (p->layer_W[1] != p->layer_W[0] && p->layer_b[1] != p->layer_b[0]);
+}
 inline int hru4(int x) { return (x + 3) & ~3; }
 inline int hru16(int x) { return (x + 15) & ~15; }
 

@@ -3502,6 +3502,18 @@ struct FwdPlan {
     size_t lds_coop;
     const char* name;
 };
+// The resident-fragment forward (RESH) holds TWO (matrix, bias) pairs per wave -- layer 0's and the first layer's that differs from
+// it -- and picks between them by comparing a layer's matrix with layer 0's: every layer must use one of those two pairs, as a pair.
+bool tiled_fwd_two_pairs(const NcdeProblem* p) {
+    int l1 = -1;
+    for (int l = 1; l < p->n_layers; ++l) {
+        if ((p->layer_W[l] == p->layer_W[0]) != (p->layer_b[l] == p->layer_b[0])) return false;
+        if (p->layer_W[l] == p->layer_W[0]) continue;
+        if (l1 < 0) l1 = l;
+        else if (p->layer_W[l] != p->layer_W[l1] || p->layer_b[l] != p->layer_b[l1]) return false;
+    }
+    return true;
+}
 FwdPlan tiled_fwd_plan(const NcdeProblem* p) {      // (p: ncde_tiled_supported for pass 0)
     FwdPlan f{};
     const bool g = p->field_kind == NCDE_FIELD_MINIMAL;
@@ -3517,7 +3529,7 @@ FwdPlan tiled_fwd_plan(const NcdeProblem* p) {      // (p: ncde_tiled_supported 
         f.name = g ? "ncde_fwd_tiled<NS1,gated,direct>" : "ncde_fwd_tiled<NS1,direct>";
     } else if (f.split) {
         // small square hidden stack (H = every width = 32 or 64): hidden fragments resident
-        bool sq = (p->hidden == 32 || p->hidden == 64) && ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr;
+        bool sq = (p->hidden == 32 || p->hidden == 64) && ncde_dev_env("NCDE_TILED_NO_RES2") == nullptr && tiled_fwd_two_pairs(p);
         for (int l = 0; l < p->n_layers; ++l) sq = sq && p->layer_out[l] == p->hidden && p->layer_in[l] == p->hidden;
         const int resh = !sq ? 0 : (p->hidden == 32 ? 2 : 4);
         f.fn = f.split == 2 ? tiled_fwd_split_fn<2>(g, small, resh) : tiled_fwd_split_fn<1>(g, small, resh);

@@ -845,7 +845,7 @@ VrRes vr_residency(const NcdeProblem* p, const Layout& y, size_t& bytes) {
     for (int l = 0; l < p->n_layers; ++l) {
         int shared = -1;
         for (int q = 0; q < l; ++q)
-            if (p->layer_W[q] == p->layer_W[l]) shared = q;
+            if (p->layer_W[q] == p->layer_W[l] && p->layer_b[q] == p->layer_b[l]) shared = q;      // (the image carries the bias in its last column)
         r.w[l] = shared >= 0 ? r.w[shared] : take(p->layer_out[l], p->layer_in[l]);
     }
     r.o = take(rows, y.dlast);

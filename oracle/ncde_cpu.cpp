@@ -38,8 +38,10 @@ int fail(int code, const char* fmt, ...) {
 struct Dims {
     int B, T, C, H, L, S, n_out, n_pieces;
     int din[NCDE_MAX_LAYERS], dout[NCDE_MAX_LAYERS];
-    int slot[NCDE_MAX_LAYERS];       // unique-parameter slot of each layer (shared layers share a slot)
+    // unique-parameter slot of each layer's matrix and of its bias (repeated pointers share a slot; W and b may be shared independently)
+    int slot[NCDE_MAX_LAYERS], bslot[NCDE_MAX_LAYERS];
     int n_slots, slot_layer[NCDE_MAX_LAYERS];
+    int n_bslots, bslot_layer[NCDE_MAX_LAYERS];
     int dlast;
 };
 
@@ -56,16 +58,22 @@ int setup(const NcdeProblem* p, Dims* d) {
     d->S = p->method == NCDE_RK4_38 ? 4 : (p->method == NCDE_MIDPOINT ? 2 : 1);
     d->n_out = p->output == NCDE_OUT_KNOTS ? p->n_knots : 2;
     d->n_pieces = p->n_knots - 1;
-    d->n_slots = 0;
+    d->n_slots = d->n_bslots = 0;
     int in = p->hidden;
     for (int l = 0; l < p->n_layers; ++l) {
         if (p->layer_in[l] != in) return fail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], in);
         d->din[l] = p->layer_in[l]; d->dout[l] = p->layer_out[l];
         in = p->layer_out[l];
-        d->slot[l] = -1;
-        for (int q = 0; q < l; ++q)
+        d->slot[l] = d->bslot[l] = -1;
+        for (int q = 0; q < l; ++q) {
             if (p->layer_W[q] == p->layer_W[l]) d->slot[l] = d->slot[q];
+            if (p->layer_b[q] == p->layer_b[l]) d->bslot[l] = d->bslot[q];
+        }
+        if (d->slot[l] >= 0 && (d->dout[d->slot_layer[d->slot[l]]] != d->dout[l] || d->din[d->slot_layer[d->slot[l]]] != d->din[l]))
+            return fail(NCDE_ERR_INVALID, "layer %d: shared matrix used with two shapes", l);
+        if (d->bslot[l] >= 0 && d->dout[d->bslot_layer[d->bslot[l]]] != d->dout[l]) return fail(NCDE_ERR_INVALID, "layer %d: shared bias used with two widths", l);
         if (d->slot[l] < 0) { d->slot[l] = d->n_slots; d->slot_layer[d->n_slots++] = l; }
+        if (d->bslot[l] < 0) { d->bslot[l] = d->n_bslots; d->bslot_layer[d->n_bslots++] = l; }
     }
     d->dlast = in;
     return NCDE_OK;
@@ -176,7 +184,7 @@ void stage_vjp(const NcdeProblem* p, const Dims& d, const float* dx, const float
         for (int n = 0; n < N; ++n) gin[n] = sc.x[l + 1][n] > 0.0f ? gin[n] : 0.0f;      // dL/dpre_l
         if (w != 0.0f) {
             float* gw = gW[d.slot[l]];
-            float* gbv = gb[d.slot[l]];
+            float* gbv = gb[d.bslot[l]];
             for (int n = 0; n < N; ++n) {
                 gbv[n] += w * gin[n];
                 for (int q = 0; q < K; ++q) gw[(long long)n * K + q] += (w * gin[n]) * sc.x[l][q];
@@ -221,8 +229,11 @@ struct GradBufs {        // per-thread parameter-gradient accumulators
         for (int s = 0; s < d.n_slots; ++s) {
             const int l = d.slot_layer[s];
             W[s].assign((size_t)d.dout[l] * d.din[l], 0.0f);
-            b[s].assign(d.dout[l], 0.0f);
-            pW[s] = W[s].data(); pb[s] = b[s].data();
+            pW[s] = W[s].data();
+        }
+        for (int s = 0; s < d.n_bslots; ++s) {
+            b[s].assign(d.dout[d.bslot_layer[s]], 0.0f);
+            pb[s] = b[s].data();
         }
         Wo.assign((size_t)d.H * d.C * d.dlast, 0.0f);
         bo.assign((size_t)d.H * d.C, 0.0f);
@@ -269,7 +280,9 @@ int backward_impl(const NcdeProblem* p, const float* src, const float* grad_out,
     if (rc != NCDE_OK) return rc;
     if (!src || !grad_out || !g || !g->grad_z0 || !g->grad_Wo || !g->grad_bo) return fail(NCDE_ERR_INVALID, "NULL pointer");
     for (int s = 0; s < d.n_slots; ++s)
-        if (!g->grad_layer_W[d.slot_layer[s]] || !g->grad_layer_b[d.slot_layer[s]]) return fail(NCDE_ERR_INVALID, "NcdeGrads: NULL destination");
+        if (!g->grad_layer_W[d.slot_layer[s]]) return fail(NCDE_ERR_INVALID, "NcdeGrads: NULL destination");
+    for (int s = 0; s < d.n_bslots; ++s)
+        if (!g->grad_layer_b[d.bslot_layer[s]]) return fail(NCDE_ERR_INVALID, "NcdeGrads: NULL destination");
     GradBufs total;
     total.init(d);
 #pragma omp parallel
@@ -343,19 +356,16 @@ int backward_impl(const NcdeProblem* p, const float* src, const float* grad_out,
         }
 #pragma omp critical
         {
-            for (int s = 0; s < d.n_slots; ++s) {
+            for (int s = 0; s < d.n_slots; ++s)
                 for (size_t i = 0; i < gb.W[s].size(); ++i) total.W[s][i] += gb.W[s][i];
+            for (int s = 0; s < d.n_bslots; ++s)
                 for (size_t i = 0; i < gb.b[s].size(); ++i) total.b[s][i] += gb.b[s][i];
-            }
             for (size_t i = 0; i < gb.Wo.size(); ++i) total.Wo[i] += gb.Wo[i];
             for (size_t i = 0; i < gb.bo.size(); ++i) total.bo[i] += gb.bo[i];
         }
     }
-    for (int s = 0; s < d.n_slots; ++s) {
-        const int l = d.slot_layer[s];
-        memcpy(g->grad_layer_W[l], total.W[s].data(), sizeof(float) * total.W[s].size());
-        memcpy(g->grad_layer_b[l], total.b[s].data(), sizeof(float) * total.b[s].size());
-    }
+    for (int s = 0; s < d.n_slots; ++s) memcpy(g->grad_layer_W[d.slot_layer[s]], total.W[s].data(), sizeof(float) * total.W[s].size());
+    for (int s = 0; s < d.n_bslots; ++s) memcpy(g->grad_layer_b[d.bslot_layer[s]], total.b[s].data(), sizeof(float) * total.b[s].size());
     memcpy(g->grad_Wo, total.Wo.data(), sizeof(float) * total.Wo.size());
     memcpy(g->grad_bo, total.bo.data(), sizeof(float) * total.bo.size());
     return NCDE_OK;

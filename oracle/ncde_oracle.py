@@ -90,11 +90,16 @@ class Field:
         out += [self.Wo, self.bo]
         return out
 
+    on_pre = None      # optional observer fn(layer index, pre-activation tensor) of every inner-net evaluation (tests/layer_topologies.py)
+
     def _net(self, u):
         acts = [u]
         x = u
-        for w, b in self.layers:
-            x = torch.relu(torch.addmm(b, x, w.t()))
+        for li, (w, b) in enumerate(self.layers):
+            pre = torch.addmm(b, x, w.t())
+            if self.on_pre is not None:
+                self.on_pre(li, pre)
+            x = torch.relu(pre)
             acts.append(x)
         return acts
 
