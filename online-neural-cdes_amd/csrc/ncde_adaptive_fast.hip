@@ -1,5 +1,5 @@
 // Adaptive dopri5, FUSED attempt kernels (round 4): one launch = one whole attempt of the step [t0, t0 + dt] -- the six stage
-// evaluations on the register-resident field evaluation of the specialised family (ncde_fast.hip: weights held as split-bf16 MFMA
+// evaluations on the register-resident field evaluation of the specialised family (ncde_fast_kernels.h: weights held as split-bf16 MFMA
 // operands, hidden layers register-to-register, output tiles + tanh + channel contraction per wave), the embedded error estimate, the
 // tentative dense output -- and the CONTROLLER (batch-wide norm, accept / reject, next dt, stage descriptors of the next attempt;
 // ncde_dp_defs.h) in the last workgroup to finish.  The per-launch kernels of ncde_adaptive.hip (six stage launches, a controller
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_fwd(DpArgs d) {
 // ------------------------------------------------------------------------------------------------------------------
 // adjoint attempt: the augmented state (vjp_t, y, a, g_theta) of adjoint.py:37-145 in negated time
 // ------------------------------------------------------------------------------------------------------------------
-// One workgroup = one 16-sample tile, 4 waves (the structure of ncde_adj_fast, ncde_fast.hip: forward recompute register-to-register in
+// One workgroup = one 16-sample tile, 4 waves (the structure of ncde_adj_fast, ncde_fast_kernels.h: forward recompute register-to-register in
 // fp32 MFMA, output tiles P -> tanh -> f, dP; Wo^T dP from an LDS image; hidden backward; weight gradients from wave-private
 // [unit][sample] images with the samples as the K dimension).  What an ATTEMPT adds:
 //   * seven stage evaluations -- stage 1 is re-evaluated from (y0, a0) at the descriptor the controller kept (ctrl->st_k1) instead of

@@ -1,4 +1,4 @@
-// Split-bf16 arithmetic shared by the register-resident (ncde_fast.hip) and batch-tiled (ncde_tiled.hip) families.
+// Split-bf16 arithmetic shared by the register-resident (ncde_fast_kernels.h) and batch-tiled (ncde_tiled.hip) families.
 #pragma once
 #include "ncde_common.h"
 

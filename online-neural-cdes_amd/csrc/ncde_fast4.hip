@@ -25,9 +25,7 @@
 
 #include <type_traits>
 
-#include "ncde_common.h"
-#include "ncde_bf3.h"
-#include "ncde_fastdefs.h"
+#include "ncde_fast_kernels.h"   // NCDE_TICK, pick_pair (with ncde_common.h, ncde_bf3.h, ncde_fastdefs.h)
 
 namespace {
 
@@ -67,12 +65,6 @@ __attribute__((amdgpu_num_vgpr(F4_NV)))
 #endif
 __global__ __launch_bounds__(512, F4_LB) void ncde_adj_fast4(KArgs a) {
     unsigned long long prof[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
-#define NCDE_TICK(k)                                                \
-    if constexpr (PROF != 0) {                                      \
-        const unsigned long long now_ = __builtin_readcyclecounter(); \
-        prof[k] += now_ - tlast;                                    \
-        tlast = now_;                                               \
-    }
     using L = F4Lds<NL, C, INTERP>;
     constexpr int H = 32, HH = 32, NW = 4, HT = 2;
     constexpr int CP = L::CP, CQ = L::CQ, NB = 2, NTILE = L::NTILE, DXW = L::DXW, XROWS = L::XROWS;
@@ -770,7 +762,6 @@ __global__ __launch_bounds__(512, F4_LB) void ncde_adj_fast4(KArgs a) {
             }
         }
     }
-#undef NCDE_TICK
 }
 
 template <int NL, int C>
@@ -779,16 +770,7 @@ NcdeKernel pick4(int interp, int method, bool disc, bool prof) {
         if (interp == NCDE_INTERP_LINEAR && method == NCDE_RK4_38 && !disc) return ncde_adj_fast4<NL, C, NCDE_INTERP_LINEAR, NCDE_RK4_38, 1, 0>;
         return nullptr;
     }
-#define NCDE_PICK(I, M)                                                                                  \
-    if (interp == I && method == M) return disc ? ncde_adj_fast4<NL, C, I, M, 0, 1> : ncde_adj_fast4<NL, C, I, M, 0, 0>;
-    NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_RK4_38)
-    NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_MIDPOINT)
-    NCDE_PICK(NCDE_INTERP_LINEAR, NCDE_EULER)
-    NCDE_PICK(NCDE_INTERP_CUBIC, NCDE_RK4_38)
-    NCDE_PICK(NCDE_INTERP_CUBIC, NCDE_MIDPOINT)
-    NCDE_PICK(NCDE_INTERP_CUBIC, NCDE_EULER)
-#undef NCDE_PICK
-    return nullptr;
+    return pick_pair(interp, method, [disc](auto I, auto M) -> NcdeKernel { return disc ? ncde_adj_fast4<NL, C, I, M, 0, 1> : ncde_adj_fast4<NL, C, I, M, 0, 0>; });
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// (H, HH) = (32, 32) with C = 4 / 8 / 12 on the register-resident kernel templates of ncde_fast.hip: one translation unit per channel
+// (H, HH) = (32, 32) with C = 4 / 8 / 12 on the register-resident kernel templates of ncde_fast_kernels.h: one translation unit per channel
 // count (ncde_fast_c.hip compiled with -DNCDE_FAST_C=...), so that the instantiations build in parallel with the rest.
 #pragma once
 #include "ncde_common.h"

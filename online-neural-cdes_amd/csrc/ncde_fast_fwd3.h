@@ -1,4 +1,4 @@
-// The three-layer (unrolled) instantiations of the register-resident forward kernel ncde_fwd_fast_bf3 (ncde_fast.hip) -- the ones the
+// The three-layer (unrolled) instantiations of the register-resident forward kernel ncde_fwd_fast_bf3 (ncde_fast_kernels.h) -- the ones the
 // BASELINE configs 2 - 4 run -- in their own translation unit (ncde_fast_fwd3.hip), because that unit alone is compiled with
 // `-mllvm -amdgpu-mfma-vgpr-form` (MFMA results in VGPRs; csrc/Makefile): the option takes a sixth of the instructions
 // out of these kernels, and it MISCOMPILES the runtime-layer-count instantiation at H = 64 in this toolchain (z wrong by 4e-2:

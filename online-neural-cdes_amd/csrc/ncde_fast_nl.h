@@ -1,4 +1,4 @@
-// Further layer counts of the chain + gradient-wave adjoint of the (32, 32, 20) shape (ncde_adj_fast3, ncde_fast.hip): its own
+// Further layer counts of the chain + gradient-wave adjoint of the (32, 32, 20) shape (ncde_adj_fast3, ncde_fast_kernels.h): its own
 // translation unit (ncde_fast_nl.hip) so that the instantiations build in parallel with the rest.
 #pragma once
 #include "ncde_common.h"

@@ -1,4 +1,4 @@
-// Device-side pieces shared by the register-resident kernels (ncde_fast.hip, ncde_fast4.hip).
+// Device-side pieces shared by the register-resident kernels (ncde_fast_kernels.h, ncde_fast4.hip).
 #pragma once
 #include "ncde_common.h"
 #include "ncde_bf3.h"

@@ -7,7 +7,7 @@
 // global/L2 (weights).  The whole time loop runs inside the kernel: the state never leaves the CU.
 //
 // This family covers ANY (H, layer widths, C, T, B); shape-specialised register-resident kernels
-// live in ncde_fast.hip.  Reference semantics restated (relative to /root/reference):
+// live in ncde_fast_kernels.h.  Reference semantics restated (paths relative to the reference project):
 //   stage loop          modules/torchdiffeq/torchdiffeq/_impl/solvers.py:103-117, fixed_grid.py:6-29,
 //                       rk_common.py:106-114
 //   f_theta(z).dX/dt    src/ncde/vector_fields/base.py:83-104, modules/torchcde/torchcde/solver.py:112-137

@@ -1,7 +1,7 @@
 // Batch-tiled Neural-CDE kernels for gfx950: the LARGE-HIDDEN regime (BASELINE config 5: H = HH = 128, C = 80,
 // |theta| = 5.4 MB >> LDS), SURVEY.md §7 step 7.
 //
-// The register-resident family (ncde_fast.hip) needs every weight on chip; the generic family (ncde_generic.hip)
+// The register-resident family (ncde_fast_kernels.h) needs every weight on chip; the generic family (ncde_generic.hip)
 // re-reads every weight once per 16 samples, 4 bytes per lane-load, and is bound by that stream.  Here one workgroup
 // (8 waves) owns NS x 16 samples:
 //   * every weight fragment is fetched ONCE per stage per workgroup as a 16-byte load per lane (64 contiguous bytes
