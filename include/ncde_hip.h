@@ -94,6 +94,8 @@ typedef enum NcdeOutput { NCDE_OUT_INTERVAL = 0, NCDE_OUT_KNOTS = 1, NCDE_OUT_TI
 #define NCDE_FLAG_TILED_WINDOW_STEPS(n) (((uint32_t)(n) & 0xFFu) << 16) /* batch-tiled backward: n (1..255) solver steps per time window
                                           instead of what the record budget allows (0 = budget).  The library reads no environment
                                           variable on any call path; development switches exist only in builds with -DNCDE_DEV_KNOBS */
+#define NCDE_FLAG_FIELD_RANK(r) (((uint32_t)(r) & 0xFFu) << 24) /* NCDE_FIELD_LOWRANK: the rank R (1..channels) of the field, carried in the
+                                          top byte of `flags`; ignored for every other field kind (existing callers pass 0) */
 
 typedef struct NcdeProblem {
     int32_t abi_version;  /* = NCDE_ABI_VERSION */
@@ -140,11 +142,18 @@ typedef struct NcdeProblem {
      *   NCDE_FIELD_ORIGINAL  M = tanh(Wo hh + bo)
      *   NCDE_FIELD_MINIMAL   M = sigmoid(Wg hh + bg) * tanh(Wo hh + bo)
      *   NCDE_FIELD_GRU       M = sigmoid(Wg net(u) + bg) * tanh(Wo net(sigmoid(Wr u + br) * u) + bo)
+     *   NCDE_FIELD_LOWRANK   M = tanh(P Q),  P = (Wo hh + bo) viewed [H, R],  Q = (Wg hh + bg) viewed [R, C]
+     *                        (src/ncde/vector_fields/sparsity.py:33-55: Wo, bo = M_h, [H*R, last width] with row index h*R + r;
+     *                        Wg, bg = M_o, [R*C, last width] with row index r*C + c; Wr, br unused).  The rank R travels in
+     *                        flags (NCDE_FLAG_FIELD_RANK(R), 1 <= R <= channels); matmul input only.  Fixed-step solves only:
+     *                        ncde_dopri5_* and ncde_backward_control answer NCDE_ERR_UNSUPPORTED, as do NCDE_FLAG_FORCE_FAST
+     *                        and NCDE_FLAG_FORCE_TILED (the field has its own kernels, ncde_fwd_lowrank / ncde_adj_lowrank).
      * field_input (vector_field_type of cdeint, modules/torchcde/torchcde/solver.py:112-137)
      *   NCDE_INPUT_MATMUL      u = z;             heads have H*C rows, dz/dt = M[H,C] . dX/dt
      *   NCDE_INPUT_EVALUATE    u = [z, X(t)];     heads have H rows,   dz/dt = M        (layer_in[0] = H + C)
      *   NCDE_INPUT_DERIVATIVE  u = [z, dX/dt(t)]; heads have H rows,   dz/dt = M
-     * Wg, bg: the sigmoid head (same shape as Wo, bo); Wr [d0, d0], br [d0]: the GRU reset net, d0 = layer_in[0]. */
+     * Wg, bg: the sigmoid head (same shape as Wo, bo; low-rank: M_o, see above); Wr [d0, d0], br [d0]: the GRU reset net,
+     * d0 = layer_in[0]. */
     int32_t field_kind;
     int32_t field_input;
     const float* Wg;
@@ -162,7 +171,7 @@ typedef struct NcdeProblem {
     int32_t reserved_;      /* padding; NOT an input -- the library ignores whatever the caller leaves here (it is zeroed on entry) */
 } NcdeProblem;
 
-typedef enum NcdeFieldKind { NCDE_FIELD_ORIGINAL = 0, NCDE_FIELD_MINIMAL = 1, NCDE_FIELD_GRU = 2 } NcdeFieldKind;
+typedef enum NcdeFieldKind { NCDE_FIELD_ORIGINAL = 0, NCDE_FIELD_MINIMAL = 1, NCDE_FIELD_GRU = 2, NCDE_FIELD_LOWRANK = 3 } NcdeFieldKind;
 typedef enum NcdeFieldInput { NCDE_INPUT_MATMUL = 0, NCDE_INPUT_EVALUATE = 1, NCDE_INPUT_DERIVATIVE = 2 } NcdeFieldInput;
 
 /* gradient outputs of the adjoint sweep; aliasing must mirror NcdeProblem.layer_W/layer_b

@@ -8,7 +8,8 @@ from . import data  # noqa: F401
 from ._lib import NcdeError, lib  # noqa: F401
 from .interpolation import LinearInterpolation, NaturalCubicSpline, SmoothLinearInterpolation  # noqa: F401
 from .solver import FieldSpec, cdeint, coop_status  # noqa: F401
-from .vector_fields import GRUGatedVectorField, MinimalGatedVectorField, MLPField, OriginalVectorField  # noqa: F401
+from .vector_fields import (GRUGatedVectorField, LowRankVectorField, MinimalGatedVectorField, MLPField,  # noqa: F401
+                            OriginalVectorField)
 from .ncde import NeuralCDE  # noqa: F401
 from .stacked import StackedNeuralCDE  # noqa: F401
 from .coefficients import linear_interpolation_coeffs, natural_cubic_coeffs, natural_cubic_spline_coeffs  # noqa: F401

@@ -13,7 +13,7 @@ INTERP = {"linear": 0, "cubic": 1, "quintic": 2}
 INTERP_PARTS = {"linear": 1, "cubic": 4, "quintic": 6}      # floats per channel of one coefficient row
 METHOD = {"euler": 0, "midpoint": 1, "rk4": 2}
 OUT_INTERVAL, OUT_KNOTS, OUT_TIMES = 0, 1, 2
-FIELD_KIND = {"original": 0, "minimal": 1, "gru": 2}
+FIELD_KIND = {"original": 0, "minimal": 1, "gru": 2, "lowrank": 3}
 FIELD_INPUT = {"matmul": 0, "evaluate": 1, "derivative": 2}
 FLAG_AUTO, FLAG_FORCE_GENERIC, FLAG_FORCE_FAST, FLAG_FP32_MFMA, FLAG_ADJOINT_V1, FLAG_ADJOINT_V2 = 0, 1, 2, 4, 8, 16
 FLAG_ADJOINT_V4 = 32
@@ -25,6 +25,8 @@ FLAG_ADJOINT_SPLIT_FP16 = 128   # development builds of the library only (ignore
 
 def FLAG_TILED_WINDOW_STEPS(n):
     return (int(n) & 0xFF) << 16
+def FLAG_FIELD_RANK(r):      # rank of the low-rank field, in the top byte of flags (include/ncde_hip.h)
+    return (int(r) & 0xFF) << 24
 FLAG_TILED_NS1, FLAG_TILED_NS2, FLAG_TILED_NS4, FLAG_FORCE_TILED = 0x1000, 0x2000, 0x4000, 0x8000
 
 _c_float_p = ctypes.c_void_p  # device pointers are passed as integers

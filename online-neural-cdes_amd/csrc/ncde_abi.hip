@@ -13,6 +13,7 @@
 #include "ncde_common.h"
 #include "ncde_fast.h"
 #include "ncde_host.h"
+#include "ncde_lowrank.h"
 #include "ncde_tiled.h"
 #include "ncde_timeplan.h"
 #include "ncde_variant.h"
@@ -70,11 +71,16 @@ int validate(const NcdeProblem* p) {
         return fail(NCDE_ERR_INVALID, "a time plan is only read with output = NCDE_OUT_TIMES");
     }
     if (p->n_layers < 0 || p->n_layers > NCDE_MAX_LAYERS) return fail(NCDE_ERR_INVALID, "n_layers %d outside [0, %d]", p->n_layers, NCDE_MAX_LAYERS);
-    if (p->field_kind < NCDE_FIELD_ORIGINAL || p->field_kind > NCDE_FIELD_GRU) return fail(NCDE_ERR_INVALID, "unknown field_kind %d", p->field_kind);
+    if (p->field_kind < NCDE_FIELD_ORIGINAL || p->field_kind > NCDE_FIELD_LOWRANK) return fail(NCDE_ERR_INVALID, "unknown field_kind %d", p->field_kind);
     if (p->field_input < NCDE_INPUT_MATMUL || p->field_input > NCDE_INPUT_DERIVATIVE)
         return fail(NCDE_ERR_INVALID, "vector_field_type string not recognised (field_input %d)", p->field_input);
     if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return fail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
     if (p->field_kind == NCDE_FIELD_GRU && (!p->Wr || !p->br)) return fail(NCDE_ERR_INVALID, "GRU field: NULL Wr/br");
+    if (p->field_kind == NCDE_FIELD_LOWRANK) {      // (the rank byte of flags is read for this kind only)
+        const int rank = ncde_field_rank(p);
+        if (p->field_input != NCDE_INPUT_MATMUL) return fail(NCDE_ERR_INVALID, "Sparse method only work for the matmul vector field type (field_input %d)", p->field_input);
+        if (rank < 1 || rank > p->channels) return fail(NCDE_ERR_INVALID, "low-rank field: rank %d (NCDE_FLAG_FIELD_RANK) outside [1, channels = %d]", rank, p->channels);
+    }
     int d = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;
     for (int l = 0; l < p->n_layers; ++l) {
         if (p->layer_in[l] != d) return fail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
@@ -152,7 +158,7 @@ const PadTarget kPadTargets[] = {
     {32, 32, 40, {true, false, false}, false},      // round 5: a forward-only kernel set
 };
 
-enum class Family { Generic, Fast, Tiled, Variant, Padded };
+enum class Family { Generic, Fast, Tiled, Variant, Padded, LowRank };
 
 struct PadPlan {
     bool ok;
@@ -170,7 +176,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
     PadPlan P{};
     P.ok = false;
     P.inner = t ? Family::Fast : Family::Tiled;
-    if (p->n_layers < 1 || p->field_input != NCDE_INPUT_MATMUL || p->field_kind == NCDE_FIELD_GRU) return P;
+    if (p->n_layers < 1 || p->field_input != NCDE_INPUT_MATMUL || p->field_kind == NCDE_FIELD_GRU || p->field_kind == NCDE_FIELD_LOWRANK) return P;
     if (p->hidden > 2048 || p->channels > 4095) return P;
     if (t) {
         if (pass < 0 || pass > 2 || !t->passes[pass] || (p->output == NCDE_OUT_TIMES && !t->time_plan)) return P;
@@ -280,6 +286,14 @@ struct Call {
 // the family of the problem as it is (no padding): NCDE_OK and *fam, or an error
 int select_family_unpadded(const NcdeProblem* p, const Layout& y, int pass, Family* fam);
 int select_route(const NcdeProblem* p, const Layout& y, int pass, Route* r) {
+    if (p->field_kind == NCDE_FIELD_LOWRANK) {      // its own family on either time axis: never zero-padded onto another, nothing cooperative
+        r->family = Family::LowRank;
+        if (p->flags & (NCDE_FLAG_FORCE_FAST | NCDE_FLAG_FORCE_TILED))
+            return fail(NCDE_ERR_UNSUPPORTED, "the low-rank field runs on ncde_fwd_lowrank / ncde_adj_lowrank only (no shape-specialised or batch-tiled kernel)");
+        char why[200] = "";
+        if (!ncde_lowrank_supported(p, pass, why, sizeof(why))) return fail(NCDE_ERR_UNSUPPORTED, "%s", why);
+        return NCDE_OK;
+    }
     const int rc = select_family_unpadded(p, y, pass, &r->family);
     if (p->flags & (NCDE_FLAG_FORCE_GENERIC | NCDE_FLAG_FORCE_FAST)) return rc;
     // no specialised kernel of its own: a zero-padded run on a specialised kernel set (also instead of the batch-tiled family, which
@@ -347,6 +361,7 @@ int64_t route_workspace_bytes(const Call& c, int pass) {
         case Family::Fast: return ncde_fast_workspace_bytes(p, pass);
         case Family::Tiled: return ncde_tiled_workspace_bytes(p, pass);
         case Family::Variant: return ncde_variant_workspace_bytes(p, pass);
+        case Family::LowRank: return ncde_lowrank_workspace_bytes(p, pass);
         case Family::Padded: {
             const PadPlan& P = c.route.pad;
             const int64_t inner = P.inner == Family::Fast ? ncde_fast_workspace_bytes(&P.q, pass) : ncde_tiled_workspace_bytes(&P.q, pass);
@@ -363,6 +378,7 @@ const char* route_kernel_name(const Call& c, int pass) {
         case Family::Fast: return ncde_fast_kernel_name(p, pass);
         case Family::Tiled: return ncde_tiled_kernel_name(p, pass);
         case Family::Variant: return pass == 0 ? "ncde_fwd_variant" : (pass == 1 ? "ncde_adj_variant" : "ncde_adj_variant<discrete>");
+        case Family::LowRank: return pass == 0 ? "ncde_fwd_lowrank" : (pass == 1 ? "ncde_adj_lowrank" : "ncde_adj_lowrank<discrete>");
         case Family::Padded:      // (on the zero-padded problem)
             return c.route.pad.inner == Family::Fast ? ncde_fast_kernel_name(&c.route.pad.q, pass) : ncde_tiled_kernel_name(&c.route.pad.q, pass);
         case Family::Generic: break;
@@ -407,6 +423,10 @@ int launch_forward(Call& c, float* out, float* stages, void* ws, size_t ws_bytes
         case Family::Variant: {
             const int rc = ncde_variant_forward(p, out, stages, st);
             return rc == NCDE_OK ? NCDE_OK : fail(rc, "variant forward launch failed");
+        }
+        case Family::LowRank: {
+            const int rc = ncde_lowrank_forward(p, out, stages, st);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "low-rank forward launch failed");
         }
         case Family::Tiled: {
             const int rc = ncde_tiled_forward(p, out, stages, ws, ws_bytes, st);
@@ -471,6 +491,11 @@ int launch_adjoint(Call& c, const float* src, const float* grad_out, const NcdeG
             if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
             return rc == NCDE_OK ? NCDE_OK : fail(rc, "variant adjoint launch failed");
         }
+        case Family::LowRank: {
+            const int rc = ncde_lowrank_adjoint(p, src, grad_out, g, ws, st, main_kernel_only, discrete);
+            if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
+            return rc == NCDE_OK ? NCDE_OK : fail(rc, "low-rank adjoint launch failed");
+        }
         case Family::Tiled: {
             const int rc = ncde_tiled_adjoint(p, src, grad_out, g, ws, ws_bytes, st, main_kernel_only, discrete, grad_coeffs);
             if (rc == NCDE_ERR_INVALID) return fail(rc, "%s", null_grad);
@@ -523,7 +548,7 @@ int begin_control(const NcdeProblem* in, Call* c, ArgsOk&& args_ok) {
     if (q.field_kind != NCDE_FIELD_ORIGINAL || q.field_input != NCDE_INPUT_MATMUL)
         return fail(NCDE_ERR_UNSUPPORTED, "control-path gradients: the original vector field with the matmul input only (field_kind %d, field_input %d)", q.field_kind, q.field_input);
     if (q.interp == NCDE_INTERP_QUINTIC) return fail(NCDE_ERR_UNSUPPORTED, "control-path gradients: linear and cubic controls only (piecewise-quintic: not implemented)");
-    q.flags = (q.flags & NCDE_FLAG_TILED_WINDOW_STEPS(0xFF)) | kControlFlags;
+    q.flags = (q.flags & (NCDE_FLAG_TILED_WINDOW_STEPS(0xFF) | NCDE_FLAG_FIELD_RANK(0xFF))) | kControlFlags;
     c->y = make_layout(&q);
     c->route.family = Family::Tiled;
     if (ncde_tiled_control_workspace_bytes(&q) >= 0) return NCDE_OK;

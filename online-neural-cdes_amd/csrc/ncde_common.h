@@ -111,6 +111,8 @@ struct KArgs {
     const unsigned* run_if;
     unsigned coop_spin;      // polls of a group counter before giving up
     int coop_inject;         // NCDE_FLAG_COOP_FAULT_INJECT: workgroup 1 skips its first arrival (tests the time-out path)
+    // low-rank field (ncde_lowrank.hip): M = tanh(P Q), P = Wo hh + bo viewed [H, R] (rows = H * R), Q = Wg hh + bg viewed [R, C]
+    int rank, rows_g;        // R and R * C
 };
 
 // every kernel of the library that takes its arguments as one KArgs

@@ -73,13 +73,17 @@ struct Layout {
     int theta_size;
     int gW_off[NCDE_MAX_LAYERS], gb_off[NCDE_MAX_LAYERS], gWo_off, gbo_off;
     int gWg_off, gbg_off, gWr_off, gbr_off;
-    int d0, rows;          // field input width, head rows
+    int d0, rows;          // field input width, head rows (low-rank field: rows of M_h = H * R)
+    int rank, rows_g;      // low-rank field: R and the rows of M_o = R * C; every other field: 0 and rows
     bool variant;          // gated field or evaluate / derivative input (generic family only)
     int dlast;
     int n_wg;
     size_t lds_fwd, lds_adj;
     int gacc_in_lds;
 };
+
+// rank R of the low-rank field (NCDE_FLAG_FIELD_RANK in the top byte of flags); 0 for every other kind, whatever that byte holds
+inline int ncde_field_rank(const NcdeProblem* p) { return p->field_kind == NCDE_FIELD_LOWRANK ? (int)(p->flags >> 24) : 0; }
 
 inline Layout make_layout(const NcdeProblem* p) {
     Layout y{};
@@ -89,6 +93,9 @@ inline Layout make_layout(const NcdeProblem* p) {
     y.variant = p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL;
     y.d0 = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;
     y.rows = p->field_input == NCDE_INPUT_MATMUL ? p->hidden * p->channels : p->hidden;
+    y.rank = ncde_field_rank(p);
+    y.rows_g = y.rows;
+    if (p->field_kind == NCDE_FIELD_LOWRANK) { y.rows = p->hidden * y.rank; y.rows_g = y.rank * p->channels; }
     y.Dp = std::max(y.Hp, hru16(y.d0));
     for (int l = 0; l < y.L; ++l) y.Dp = std::max(y.Dp, hru16(p->layer_out[l]));
     y.HS = y.Hp * 16;
@@ -110,8 +117,8 @@ inline Layout make_layout(const NcdeProblem* p) {
     y.gbo_off = off; off += y.rows;
     y.gWg_off = y.gbg_off = y.gWr_off = y.gbr_off = 0;
     if (p->field_kind != NCDE_FIELD_ORIGINAL) {
-        y.gWg_off = off; off += y.rows * y.dlast;
-        y.gbg_off = off; off += y.rows;
+        y.gWg_off = off; off += y.rows_g * y.dlast;
+        y.gbg_off = off; off += y.rows_g;
     }
     if (p->field_kind == NCDE_FIELD_GRU) {
         y.gWr_off = off; off += y.d0 * y.d0;
@@ -152,6 +159,7 @@ inline void fill_kargs(const NcdeProblem* p, const Layout& y, KArgs* a) {
     a->Wg = p->Wg; a->bg = p->bg; a->Wr = p->Wr; a->br = p->br;
     a->gWg_off = y.gWg_off; a->gbg_off = y.gbg_off; a->gWr_off = y.gWr_off; a->gbr_off = y.gbr_off;
     a->gacc_in_lds = y.gacc_in_lds;
+    a->rank = y.rank; a->rows_g = y.rows_g;
     // internal (zero-padded problems, see KArgs): reserved_ = (real hidden size << 12) | real channel count, 0 = not padded
     a->Hr = p->reserved_ ? (p->reserved_ >> 12) : p->hidden;
     a->Cc = p->reserved_ ? (p->reserved_ & 0xFFF) : p->channels;
@@ -174,8 +182,8 @@ inline int launch_reduce_partials(const NcdeProblem* p, const Layout& y, const N
     segs.off[n] = y.gWo_off; segs.len[n] = y.rows * y.dlast; segs.dst[n] = g->grad_Wo; ++n;
     segs.off[n] = y.gbo_off; segs.len[n] = y.rows; segs.dst[n] = g->grad_bo; ++n;
     if (p->field_kind != NCDE_FIELD_ORIGINAL) {
-        segs.off[n] = y.gWg_off; segs.len[n] = y.rows * y.dlast; segs.dst[n] = g->grad_Wg; ++n;
-        segs.off[n] = y.gbg_off; segs.len[n] = y.rows; segs.dst[n] = g->grad_bg; ++n;
+        segs.off[n] = y.gWg_off; segs.len[n] = y.rows_g * y.dlast; segs.dst[n] = g->grad_Wg; ++n;
+        segs.off[n] = y.gbg_off; segs.len[n] = y.rows_g; segs.dst[n] = g->grad_bg; ++n;
     }
     if (p->field_kind == NCDE_FIELD_GRU) {
         segs.off[n] = y.gWr_off; segs.len[n] = y.d0 * y.d0; segs.dst[n] = g->grad_Wr; ++n;

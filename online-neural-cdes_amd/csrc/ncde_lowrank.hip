@@ -1,0 +1,619 @@
+// The reference's LOW-RANK vector field (src/ncde/vector_fields/sparsity.py:33-55) on the generic 16-sample-tile structure:
+//   hh = net_to_hh(z);  P = M_h hh + b_h viewed [H, R];  Q = M_o hh + b_o viewed [R, C];  M = tanh(P Q);  dz/dt = M . dX/dt
+// Same design as ncde_generic.hip / ncde_variant.hip (activations in LDS as [unit][sample], fp32 MFMA 16x16x4, the whole time
+// loop inside the kernel, per-workgroup parameter-gradient partials; the control input and the inner layers are the generic
+// family's own load_dx / dense_relu).  What is new is the head: ONE GEMM over the stacked (H + C) R rows of M_h and M_o -- no
+// activation -- into LDS, then the rank-R contraction, tanh and the channel contraction on the VALU, one thread per (h, sample).
+// M is never stored.  The continuous adjoint and the exact discrete backward share one kernel, as in ncde_variant.hip.
+//
+// LDS layout of the two small matrices: PQ[n][s], n = the stacked row -- P[h][r] at row h R + r, Q[r][c] at row H R + r C + c.
+// In the contraction a wave's lanes differ in s (16) and h (4), never in c: the 16 words Q[r][c][0..15] are consecutive (one
+// bank each, the 4 h-groups read them as a broadcast).  P[h][r] of the first four ranks is held in registers over the c loop.
+#include "ncde_generic_stage.h"
+#include "ncde_host.h"
+#include "ncde_lowrank.h"
+
+#define LR_THREADS GEN_THREADS
+#define LR_NW GEN_NW
+#define LR_RREG 4   // ranks whose P / Q / gradient values a thread keeps in registers (the reference's grids use R = 1..3)
+
+namespace {
+
+struct LrDims {
+    int H, C, R, NH, NT, NTp, dlast;      // NH = H R rows of M_h, NT = NH + R C stacked rows, NTp = NT rounded up to 16
+    const float* wl;                      // LDS-resident copy of the stacked head matrix [NT][ld] (bias in column dlast), or NULL
+    int ld;
+};
+
+__device__ __forceinline__ const float* lr_wrow(const KArgs& a, const LrDims& d, int n) {
+    if (d.wl) return d.wl + n * d.ld;
+    return n < d.NH ? a.Wo + (long long)n * d.dlast : a.Wg + (long long)(n - d.NH) * d.dlast;
+}
+__device__ __forceinline__ float lr_bias(const KArgs& a, const LrDims& d, int n) {
+    if (d.wl) return d.wl[n * d.ld + d.dlast];
+    return n < d.NH ? a.bo[n] : a.bg[n - d.NH];
+}
+
+__device__ void lr_fill_resident(const KArgs& a, const LrDims& d, float* dst, int tid) {
+    for (int e = tid; e < d.NT * d.ld; e += LR_THREADS) {
+        const int n = e / d.ld, c = e - n * d.ld;
+        const float* w = n < d.NH ? a.Wo + (long long)n * d.dlast : a.Wg + (long long)(n - d.NH) * d.dlast;
+        float v = 0.0f;
+        if (c < d.dlast) v = w[c];
+        else if (c == d.dlast) v = n < d.NH ? a.bo[n] : a.bg[n - d.NH];
+        dst[e] = v;
+    }
+}
+
+// PQ[n][s] = sum_k Wst[n][k] xl[k][s] + bst[n] for the stacked rows n < NT (rows NT .. NTp-1 come out as 0); no activation
+__device__ void lr_heads(const KArgs& a, const LrDims& d, const float* xl, float* PQ, int wave, int lane) {
+    const int li = lane & 15, lk = lane >> 4;
+    const int ntiles = d.NTp >> 4, nks = (d.dlast + 3) >> 2;
+    for (int t = wave; t < ntiles; t += LR_NW) {
+        const int rowA = 16 * t + li;
+        const bool rv = rowA < d.NT;
+        const float* wrow = lr_wrow(a, d, rv ? rowA : 0);
+        f32x4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * t + 4 * lk + r;
+            acc[r] = row < d.NT ? lr_bias(a, d, row) : 0.0f;
+        }
+#pragma unroll 4
+        for (int ks = 0; ks < nks; ++ks) {
+            const int k = 4 * ks + lk;
+            const float av = (rv && k < d.dlast) ? wrow[k] : 0.0f;
+            acc = mfma16(av, xl[k * 16 + li], acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * t + 4 * lk + r;
+            PQ[row * 16 + li] = row < d.NT ? acc[r] : 0.0f;
+        }
+    }
+}
+
+// S[h][c] = sum_r P[h][r] Q[r][c] for one (h, s): Ph -> P[h][0][s], Qc -> Q[0][c][s], pr = P[h][0..3] (registers)
+__device__ __forceinline__ float lr_rank_sum(const LrDims& d, const float (&pr)[LR_RREG], const float* Ph, const float* Qc) {
+    const int qs = d.C * 16;
+    float S = 0.0f;
+#pragma unroll
+    for (int r = 0; r < LR_RREG; ++r)
+        if (r < d.R) S = fmaf(pr[r], Qc[r * qs], S);
+    for (int r = LR_RREG; r < d.R; ++r) S = fmaf(Ph[r * 16], Qc[r * qs], S);
+    return S;
+}
+
+// KO[h][s] = sum_c tanh(S[h][c]) dX[c][s]      (rows h >= H come out as 0)
+__device__ void lr_contract(const LrDims& d, const float* PQ, const float* CIN, float* KO, int HS, int tid) {
+    for (int e = tid; e < HS; e += LR_THREADS) {
+        const int h = e >> 4, s = e & 15;
+        float k = 0.0f;
+        if (h < d.H) {
+            const float* Ph = PQ + h * d.R * 16 + s;
+            const float* Qs = PQ + d.NH * 16 + s;
+            float pr[LR_RREG];
+#pragma unroll
+            for (int r = 0; r < LR_RREG; ++r) pr[r] = r < d.R ? Ph[r * 16] : 0.0f;
+            for (int c = 0; c < d.C; ++c) k = fmaf(tanh_dev(lr_rank_sum(d, pr, Ph, Qs + c * 16)), CIN[c * 16 + s], k);
+        }
+        KO[e] = k;
+    }
+}
+
+__device__ __forceinline__ LrDims lr_dims(const KArgs& a, const float* lds) {
+    LrDims d;
+    d.H = a.H; d.C = a.C; d.R = a.rank;
+    d.NH = a.rows; d.NT = a.rows + a.rows_g; d.NTp = ru16(d.NT);
+    d.dlast = a.dout[a.n_layers - 1];
+    d.ld = (d.dlast + 1) | 1;
+    d.wl = a.wres_o >= 0 ? lds + a.wres_o : nullptr;
+    return d;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_fwd_lowrank(KArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const int H = a.H, Hp = ru16(H), Cp = ru4(a.C), L = a.n_layers;
+    int Dp = Hp;
+    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
+    const int HS = Hp * 16, DS = Dp * 16;
+    const LrDims d = lr_dims(a, lds);
+    float* U = lds;              // stage state [Dp][16] (rows >= H stay 0)
+    float* XA = U + DS;          // ping-pong activations of the inner net (2 buffers)
+    float* Y0 = XA + 2 * DS;
+    float* K1 = Y0 + HS;
+    float* K2 = K1 + HS;
+    float* KO = K2 + HS;
+    float* CIN = KO + HS;        // dX/dt [Cp][16]
+    float* PQ = CIN + Cp * 16;   // [NTp][16]
+    const int total = 3 * DS + 4 * HS + Cp * 16 + d.NTp * 16;
+    for (int e = tid; e < total; e += LR_THREADS) lds[e] = 0.0f;
+    if (a.wres_o >= 0) lr_fill_resident(a, d, lds + a.wres_o, tid);
+    __syncthreads();
+    for (int e = tid; e < HS; e += LR_THREADS) {
+        const int h = e >> 4, s = e & 15, b = b0 + s;
+        if (h < H && b < a.B) {
+            const float v = a.z0[(long long)b * H + h];
+            Y0[e] = v;
+            U[e] = v;
+            a.out[((long long)b * a.n_out) * H + h] = v;
+        }
+    }
+    const int S = n_stages(a.method);
+    const bool planned = a.plan != nullptr;
+    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier of the loop)
+    const int n_steps = planned ? a.n_steps_fwd : a.T - 1;
+    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
+    for (int n = 0; n < n_steps; ++n) {
+        const int* pstep = planned ? a.plan + plan_off_fwd() + n * plan_step_words(S) : nullptr;
+        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
+        for (int j = 0; j < S; ++j) {
+            const StageDesc sd = planned ? plan_stage(pstep, j) : default_stage(a.method, (float)n + stage_offset(a.method, j), a.n_pieces);
+            __syncthreads();      // U of this stage is complete (first stage: the z0 load above)
+            load_dx(a, b0, sd, CIN, Cp, tid);
+            if (a.stages) {
+                float* rec = a.stages + ((long long)(n * S + j) * a.B + b0) * H;
+                for (int e = tid; e < 16 * H; e += LR_THREADS) {
+                    const int s = e / H, h = e - s * H;
+                    if (b0 + s < a.B) rec[e] = U[h * 16 + s];
+                }
+            }
+            const float* in = U;
+            for (int l = 0; l < L; ++l) {
+                float* outb = XA + (l & 1) * DS;
+                dense_relu(a.W[l], a.b[l], a.dout[l], a.din[l], in, outb, wave, lane);
+                __syncthreads();
+                in = outb;
+            }
+            lr_heads(a, d, in, PQ, wave, lane);
+            __syncthreads();
+            lr_contract(d, PQ, CIN, KO, HS, tid);
+            __syncthreads();
+            for (int e = tid; e < HS; e += LR_THREADS) {
+                float y0 = Y0[e], k1 = K1[e], k2 = K2[e];
+                const float yprev = y0;
+                bool last;
+                const float ys = StageCombine::apply(a.method, j, KO[e], dt, y0, k1, k2, last);
+                U[e] = ys;
+                K1[e] = k1;
+                K2[e] = k2;
+                if (last) {
+                    Y0[e] = y0;
+                    const int h = e >> 4, s = e & 15, b = b0 + s;
+                    if (h < H && b < a.B) {
+                        if (planned) {
+                            const int q0 = pstep[1], q1 = q0 + pstep[2];
+                            for (int q = q0; q < q1; ++q) {
+                                const int kind = pout[2 * q];
+                                const float slope = __int_as_float(pout[2 * q + 1]);
+                                a.out[((long long)b * a.n_out + q) * H + h] = kind == 1 ? y0 : (kind == 0 ? yprev : yprev + slope * (y0 - yprev));
+                            }
+                        } else if (a.output == NCDE_OUT_KNOTS) a.out[((long long)b * a.n_out + (n + 1)) * H + h] = y0;
+                        else if (n == a.T - 2) a.out[((long long)b * a.n_out + 1) * H + h] = y0;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// adjoint / exact discrete backward
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// *p += v on this workgroup's PRIVATE gradient partial: every address is only ever touched by one thread, in program order, so
+// the result is the same on every run (global memory: a float add without return, as in ncde_variant.hip)
+__device__ __forceinline__ void lr_accum(float* p, float v, int in_lds) {
+    if (in_lds) *p += v;
+    else unsafeAtomicAdd(p, v);
+}
+
+// gW[j][i] += w sum_s gpre[j][s] xin[i][s];  gb[j] += w sum_s gpre[j][s]   (samples are the K dim of the MFMA).  row_w(j) /
+// row_b(j): where row j of the weight gradient / its bias entry live in the partial (the stacked head rows sit in two segments)
+template <class RowW, class RowB>
+__device__ void lr_dw_acc(const float* gpre, const float* xin, int N, int K, float w, RowW row_w, RowB row_b, int tid, int wave, int lane, int in_lds) {
+    const int li = lane & 15, lk = lane >> 4;
+    for (int jj = tid; jj < N; jj += LR_THREADS) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) sum += gpre[jj * 16 + s];
+        lr_accum(row_b(jj), w * sum, in_lds);
+    }
+    const int njt = (N + 15) >> 4, nit = (K + 15) >> 4;
+    for (int tt = wave; tt < njt * nit; tt += LR_NW) {
+        const int jt = tt / nit, it = tt - jt * nit;
+        f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) g = mfma16(gpre[(16 * jt + li) * 16 + 4 * ks + lk], xin[(16 * it + li) * 16 + 4 * ks + lk], g);
+        const int col = 16 * it + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * jt + 4 * lk + r;
+            if (row < N && col < K) lr_accum(row_w(row) + col, w * g[r], in_lds);
+        }
+    }
+}
+
+// out[i][s] = sum_j W(j)[i] gpre[j][s], i < ru16(K); optionally x relu'(mask[i][s]).  wrow(j): row j of the [N][K] matrix
+template <class WRow>
+__device__ void lr_bwd_data(WRow wrow, int N, int K, const float* gpre, const float* mask, float* out, int wave, int lane) {
+    const int li = lane & 15, lk = lane >> 4;
+    const int nit = (K + 15) >> 4, nks = (N + 3) >> 2;
+    for (int it = wave; it < nit; it += LR_NW) {
+        const int col = 16 * it + li;
+        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int ks = 0; ks < nks; ++ks) {
+            const int k = 4 * ks + lk;
+            const float av = (k < N && col < K) ? wrow(k)[col] : 0.0f;
+            acc = mfma16(av, gpre[k * 16 + li], acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * it + 4 * lk + r;
+            float v = acc[r];
+            if (mask) v = mask[row * 16 + li] > 0.0f ? v : 0.0f;
+            out[row * 16 + li] = v;
+        }
+    }
+}
+
+// One stage's head backward on the VALU, cotangent AS[h][s]:  gS[h][c] = AS[h] dX[c] (1 - M^2), recomputed in both passes,
+//   pass 1, one thread per (h, s):  KOY[h] = sum_c M dX[c];  gP[h][r] = sum_c gS[h][c] Q[r][c]   -> G rows h R + r
+//   pass 2, one thread per (c, s):  gQ[r][c] = sum_h P[h][r] gS[h][c]                              -> G rows H R + r C + c
+// (ranks >= LR_RREG accumulate in the thread's own words of G)
+__device__ void lr_head_vjp(const LrDims& d, const float* PQ, const float* CIN, const float* AS, float* G, float* KOY, int HS, int tid) {
+    const int qs = d.C * 16;
+    const float* Qb = PQ + d.NH * 16;
+    float* GQ = G + d.NH * 16;
+    for (int e = tid; e < HS; e += LR_THREADS) {
+        const int h = e >> 4, s = e & 15;
+        float k = 0.0f;
+        if (h < d.H) {
+            const float* Ph = PQ + h * d.R * 16 + s;
+            float* Gh = G + h * d.R * 16 + s;
+            const float ah = AS[e];
+            float pr[LR_RREG], gp[LR_RREG];
+#pragma unroll
+            for (int r = 0; r < LR_RREG; ++r) { pr[r] = r < d.R ? Ph[r * 16] : 0.0f; gp[r] = 0.0f; }
+            for (int r = LR_RREG; r < d.R; ++r) Gh[r * 16] = 0.0f;
+            for (int c = 0; c < d.C; ++c) {
+                const float* Qc = Qb + c * 16 + s;
+                const float dx = CIN[c * 16 + s];
+                const float m = tanh_dev(lr_rank_sum(d, pr, Ph, Qc));
+                k = fmaf(m, dx, k);
+                const float gS = (ah * dx) * (1.0f - m * m);
+#pragma unroll
+                for (int r = 0; r < LR_RREG; ++r)
+                    if (r < d.R) gp[r] = fmaf(gS, Qc[r * qs], gp[r]);
+                for (int r = LR_RREG; r < d.R; ++r) Gh[r * 16] = fmaf(gS, Qc[r * qs], Gh[r * 16]);
+            }
+#pragma unroll
+            for (int r = 0; r < LR_RREG; ++r)
+                if (r < d.R) Gh[r * 16] = gp[r];
+        }
+        KOY[e] = k;
+    }
+    for (int e = tid; e < d.C * 16; e += LR_THREADS) {
+        const int s = e & 15;
+        const float* Qc = Qb + e;         // Q[0][c][s]
+        float* Gc = GQ + e;
+        const float dx = CIN[e];
+        float qr[LR_RREG], gq[LR_RREG];
+#pragma unroll
+        for (int r = 0; r < LR_RREG; ++r) { qr[r] = r < d.R ? Qc[r * qs] : 0.0f; gq[r] = 0.0f; }
+        for (int r = LR_RREG; r < d.R; ++r) Gc[r * qs] = 0.0f;
+        for (int h = 0; h < d.H; ++h) {
+            const float* Ph = PQ + h * d.R * 16 + s;
+            float S = 0.0f;
+#pragma unroll
+            for (int r = 0; r < LR_RREG; ++r)
+                if (r < d.R) S = fmaf(Ph[r * 16], qr[r], S);
+            for (int r = LR_RREG; r < d.R; ++r) S = fmaf(Ph[r * 16], Qc[r * qs], S);
+            const float m = tanh_dev(S);
+            const float gS = (AS[h * 16 + s] * dx) * (1.0f - m * m);
+#pragma unroll
+            for (int r = 0; r < LR_RREG; ++r)
+                if (r < d.R) gq[r] = fmaf(Ph[r * 16], gS, gq[r]);
+            for (int r = LR_RREG; r < d.R; ++r) Gc[r * qs] = fmaf(Ph[r * 16], gS, Gc[r * qs]);
+        }
+#pragma unroll
+        for (int r = 0; r < LR_RREG; ++r)
+            if (r < d.R) Gc[r * qs] = gq[r];
+    }
+}
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_adj_lowrank(KArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const int H = a.H, Hp = ru16(H), Cp = ru4(a.C), L = a.n_layers;
+    int Dp = Hp;
+    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
+    const int HS = Hp * 16, DS = Dp * 16;
+    const LrDims d = lr_dims(a, lds);
+    float* U = lds;                  // stage input (rows >= H stay 0)
+    float* XI = U + DS;              // [L] activations of the inner net
+    float* GA = XI + L * DS;         // dL/dpre ping
+    float* GB = GA + DS;             // pong
+    float* DU = GB + DS;             // cotangent of the stage input
+    float* AS = DU + DS;             // stage cotangent [Hp][16]
+    float* Y0 = AS + HS;
+    float* A0 = Y0 + HS;
+    float* KY1 = A0 + HS;
+    float* KY2 = KY1 + HS;
+    float* KA1 = KY2 + HS;
+    float* KA2 = KA1 + HS;
+    float* KOY = KA2 + HS;
+    float* CIN = KOY + HS;           // dX/dt [Cp][16]
+    float* PQ = CIN + Cp * 16;       // [NTp][16]
+    float* G = PQ + d.NTp * 16;      // gP | gQ, stacked like PQ, [NTp][16] (rows >= NT stay 0)
+    float* GL = G + d.NTp * 16;      // the gradient partial, when it fits
+    const int total = (4 + L) * DS + 8 * HS + Cp * 16 + 2 * d.NTp * 16 + (a.gacc_in_lds ? a.theta_size : 0);
+    for (int e = tid; e < total; e += LR_THREADS) lds[e] = 0.0f;
+    if (a.wres_o >= 0) lr_fill_resident(a, d, lds + a.wres_o, tid);
+    float* gacc = a.gacc_in_lds ? GL : a.gpart + (long long)blockIdx.x * a.theta_size;
+    if (!a.gacc_in_lds)
+        for (int e = tid; e < a.theta_size; e += LR_THREADS) gacc[e] = 0.0f;
+    __syncthreads();
+    const int last_row = a.n_out - 1;
+    const int S = n_stages(a.method);
+    const bool disc = a.discrete != 0;
+    const bool planned = a.plan != nullptr;
+    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier of the loop)
+    const int pw_ = plan_step_words(S);
+    const int* pfwd = planned ? a.plan + plan_off_fwd() : nullptr;
+    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
+    const int* padj = planned ? a.plan + plan_off_adj(S, a.n_steps_fwd, a.n_out) : nullptr;
+    const int n_rsteps = planned ? (disc ? a.n_steps_fwd : a.n_steps_adj) : a.T - 1;
+    for (int e = tid; e < HS; e += LR_THREADS) {
+        const int h = e >> 4, s = e & 15, b = b0 + s;
+        if (h < H && b < a.B) {
+            const long long o = ((long long)b * a.n_out + last_row) * H + h;
+            float g = a.grad_out[o];
+            if (planned && disc) g = plan_out_cotangent(a, pfwd + (a.n_steps_fwd - 1) * pw_, pout, 1, (long long)b * a.n_out, h);
+            A0[e] = g;
+            if (disc) {
+                const float dtl = planned ? __int_as_float(pfwd[(a.n_steps_fwd - 1) * pw_]) : 1.0f;
+                AS[e] = a.method == NCDE_RK4_38 ? (g * dtl) * 0.125f : dtl * g;
+            } else {
+                const float y = a.z_out[o];
+                Y0[e] = y; U[e] = y; AS[e] = g;
+            }
+        }
+    }
+    const float* xl = XI + (L - 1) * DS;
+    auto head_w = [&](int n) { return gacc + (n < d.NH ? a.gWo_off + (long long)n * d.dlast : a.gWg_off + (long long)(n - d.NH) * d.dlast); };
+    auto head_b = [&](int n) { return gacc + (n < d.NH ? a.gbo_off + n : a.gbg_off + (n - d.NH)); };
+    auto head_row = [&](int n) { return lr_wrow(a, d, n); };
+    for (int rstep = 0; rstep < n_rsteps; ++rstep) {
+        const int n = a.T - 1 - rstep, m = n_rsteps - 1 - rstep;   // default grid: reverse step n -> n-1; m = forward step transposed
+        const int* pstep = planned ? (disc ? pfwd + m * pw_ : padj + rstep * pw_) : nullptr;
+        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
+        for (int j = 0; j < S; ++j) {
+            StageDesc sd;
+            if (planned) sd = plan_stage(pstep, disc ? S - 1 - j : j);
+            else sd = default_stage(a.method, disc ? (float)(n - 1) + stage_offset(a.method, S - 1 - j) : -(-(float)n + stage_offset(a.method, j)), a.n_pieces);
+            const float w = disc ? 1.0f : stage_weight(a.method, j) * dt;
+            __syncthreads();      // U / AS of this stage are complete (first stage: the loads above)
+            load_dx(a, b0, sd, CIN, Cp, tid);
+            if (disc) {
+                const float* rec = a.stages + ((long long)(m * S + (S - 1 - j)) * a.B + b0) * H;
+                for (int e = tid; e < 16 * H; e += LR_THREADS) {
+                    const int s = e / H, h = e - s * H;
+                    U[h * 16 + s] = b0 + s < a.B ? rec[e] : 0.0f;
+                }
+            }
+            __syncthreads();
+            // ---- the stage forward, every layer kept ------------------------------------------------------------------------
+            const float* in = U;
+            for (int l = 0; l < L; ++l) {
+                dense_relu(a.W[l], a.b[l], a.dout[l], a.din[l], in, XI + l * DS, wave, lane);
+                __syncthreads();
+                in = XI + l * DS;
+            }
+            lr_heads(a, d, xl, PQ, wave, lane);
+            __syncthreads();
+            // ---- heads backwards: f, gP, gQ (VALU) -----------------------------------------------------------------------------
+            lr_head_vjp(d, PQ, CIN, AS, G, KOY, HS, tid);
+            __syncthreads();
+            // ---- dM_h | dM_o += w G (x) x_L, their biases;  dL/dpre_L = (M_h^T gP + M_o^T gQ) * relu'(x_L): one GEMM over the stacked rows
+            if (w != 0.0f) lr_dw_acc(G, xl, d.NT, d.dlast, w, head_w, head_b, tid, wave, lane, a.gacc_in_lds);
+            lr_bwd_data(head_row, d.NT, d.dlast, G, xl, GA, wave, lane);
+            __syncthreads();
+            // ---- the inner net backwards (the generic family's) ----------------------------------------------------------------
+            float* gpre = GA;
+            float* gx = GB;
+            for (int l = L - 1; l >= 0; --l) {
+                const int N = a.dout[l], K = a.din[l];
+                const float* xin = l == 0 ? U : XI + (l - 1) * DS;
+                const float* Wl = a.W[l];
+                if (w != 0.0f) {
+                    float* gW = gacc + a.gW_off[l];
+                    float* gb = gacc + a.gb_off[l];
+                    lr_dw_acc(gpre, xin, N, K, w, [&](int r) { return gW + (long long)r * K; }, [&](int r) { return gb + r; }, tid, wave, lane, a.gacc_in_lds);
+                }
+                lr_bwd_data([&](int r) { return Wl + (long long)r * K; }, N, K, gpre, l > 0 ? xin : nullptr, l == 0 ? DU : gx, wave, lane);
+                __syncthreads();
+                float* tmp = gpre; gpre = gx; gx = tmp;
+            }
+            // ---- Butcher bookkeeping (d = dL/dy of the stage) ---------------------------------------------------------------------
+            for (int e = tid; e < HS; e += LR_THREADS) {
+                const int h = e >> 4, s = e & 15, b = b0 + s;
+                const bool valid = h < H && b < a.B;
+                const float dd = h < H ? DU[e] : 0.0f;
+                if (disc) {
+                    float a0 = A0[e];
+                    bool last = false;
+                    float next = 0.0f;
+                    if (a.method == NCDE_RK4_38) {
+                        const float c4 = (a0 * dt) * 0.125f;
+                        const float dt3 = dt * 0.333333343267440796f;
+                        if (j == 0) { KA1[e] = dd; next = 3.0f * c4 + dt * dd; }
+                        else if (j == 1) { KA2[e] = dd; next = (3.0f * c4 - dt * KA1[e]) + dt * dd; }
+                        else if (j == 2) { KY1[e] = dd; next = ((c4 + dt * KA1[e]) - dt3 * KA2[e]) + dt3 * dd; }
+                        else { a0 = (((a0 + KA1[e]) + KA2[e]) + KY1[e]) + dd; last = true; }
+                    } else if (a.method == NCDE_MIDPOINT) {
+                        if (j == 0) { KA1[e] = dd; next = (0.5f * dt) * dd; }
+                        else { a0 = (a0 + KA1[e]) + dd; last = true; }
+                    } else {
+                        a0 = a0 + dd; last = true;
+                    }
+                    if (last) {
+                        float dtp = 1.0f;
+                        if (planned) {
+                            if (valid) {
+                                const long long brow = (long long)b * a.n_out;
+                                a0 = a0 + plan_out_cotangent(a, pstep, pout, 0, brow, h);
+                                if (m > 0) a0 = a0 + plan_out_cotangent(a, pstep - pw_, pout, 1, brow, h);
+                                else a0 = a0 + a.grad_out[brow * H + h];
+                            }
+                            if (m > 0) dtp = __int_as_float(pstep[-pw_]);
+                        } else if (a.output == NCDE_OUT_KNOTS || n == 1) {
+                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out + (a.output == NCDE_OUT_KNOTS ? n - 1 : 0)) * H + h] : 0.0f);
+                        }
+                        A0[e] = a0;
+                        next = a.method == NCDE_RK4_38 ? (a0 * dtp) * 0.125f : dtp * a0;
+                        if (m == 0 && valid) a.grad_z0[(long long)b * H + h] = a0;
+                    }
+                    AS[e] = next;
+                } else {
+                    float y0 = Y0[e], k1 = KY1[e], k2 = KY2[e];
+                    bool last;
+                    const float ys = StageCombine::apply(a.method, j, -KOY[e], dt, y0, k1, k2, last);
+                    U[e] = ys; KY1[e] = k1; KY2[e] = k2;
+                    float a0 = A0[e], q1 = KA1[e], q2 = KA2[e];
+                    const float as = StageCombine::apply(a.method, j, dd, dt, a0, q1, q2, last);
+                    KA1[e] = q1; KA2[e] = q2;
+                    if (!last) {
+                        AS[e] = as;
+                    } else {
+                        if (planned) {
+                            const int row = pstep[1];
+                            if (row >= 0) {
+                                const long long o = ((long long)b * a.n_out + row) * H + h;
+                                y0 = valid ? a.z_out[o] : 0.0f;
+                                a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
+                            }
+                        } else if (a.output == NCDE_OUT_KNOTS) {
+                            const long long o = ((long long)b * a.n_out + (n - 1)) * H + h;
+                            y0 = valid ? a.z_out[o] : 0.0f;
+                            a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
+                        } else if (n == 1) {
+                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out) * H + h] : 0.0f);
+                        }
+                        Y0[e] = y0; U[e] = y0; A0[e] = a0; AS[e] = a0;
+                        if (rstep == n_rsteps - 1 && valid) a.grad_z0[(long long)b * H + h] = a0;
+                    }
+                }
+            }
+        }
+    }
+    if (a.gacc_in_lds) {
+        __syncthreads();
+        float* dst = a.gpart + (long long)blockIdx.x * a.theta_size;
+        for (int e = tid; e < a.theta_size; e += LR_THREADS) dst[e] = GL[e];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct LrPlan {
+    bool ok;
+    size_t lds_fwd, lds_adj;        // bytes, the resident copy of the heads included
+    int res_fwd, res_adj;           // float offset of the LDS-resident stacked head matrix, -1 = streamed from L2
+    int gacc_in_lds;
+};
+
+LrPlan lr_plan(const NcdeProblem* p, const Layout& y) {
+    LrPlan v{};
+    v.res_fwd = v.res_adj = -1;
+    const size_t HS = (size_t)y.Hp * 16, DS = (size_t)y.Dp * 16, L = (size_t)p->n_layers;
+    const size_t NT = (size_t)y.rows + (size_t)y.rows_g, NTp = (NT + 15) & ~(size_t)15;
+    const size_t fwd = 3 * DS + 4 * HS + (size_t)y.Cp * 16 + NTp * 16;
+    size_t adj = (4 + L) * DS + 8 * HS + (size_t)y.Cp * 16 + 2 * NTp * 16;
+    const size_t limit = (size_t)kLdsLimit / sizeof(float);
+    v.gacc_in_lds = adj + (size_t)y.theta_size <= limit;
+    if (v.gacc_in_lds) adj += (size_t)y.theta_size;
+    const size_t res = NT * (size_t)((y.dlast + 1) | 1);
+    v.lds_fwd = fwd; v.lds_adj = adj;
+    if (fwd + res <= limit) { v.res_fwd = (int)fwd; v.lds_fwd = fwd + res; }
+    if (adj + res <= limit) { v.res_adj = (int)adj; v.lds_adj = adj + res; }
+    v.ok = fwd <= limit && adj <= limit;
+    v.lds_fwd *= sizeof(float); v.lds_adj *= sizeof(float);
+    return v;
+}
+
+bool lr_refuse(char* why, size_t n, const char* fmt, long long a0 = 0, long long a1 = 0) {
+    if (why && n) snprintf(why, n, fmt, a0, a1);
+    return false;
+}
+
+}  // namespace
+
+bool ncde_lowrank_supported(const NcdeProblem* p, int pass, char* why, size_t n) {
+    const Layout y = make_layout(p);
+    if (p->field_kind != NCDE_FIELD_LOWRANK || p->field_input != NCDE_INPUT_MATMUL) return lr_refuse(why, n, "not a low-rank field with the matmul input");
+    if (p->n_layers < 1) return lr_refuse(why, n, "the low-rank kernels need at least one inner layer");
+    if (p->hidden > 128 || p->channels > 128) return lr_refuse(why, n, "the low-rank kernels cover hidden <= 128 and channels <= 128 (got %lld, %lld)", p->hidden, p->channels);
+    for (int l = 0; l < p->n_layers; ++l)
+        if (p->layer_out[l] > 128) return lr_refuse(why, n, "the low-rank kernels cover layer widths <= 128 (layer %lld: %lld)", l, p->layer_out[l]);
+    const LrPlan v = lr_plan(p, y);
+    const size_t need = pass == 0 ? v.lds_fwd : v.lds_adj;
+    if (need > (size_t)kLdsLimit) return lr_refuse(why, n, "the low-rank kernel of pass %lld needs %lld B of LDS", pass, (long long)need);
+    return true;
+}
+
+int64_t ncde_lowrank_workspace_bytes(const NcdeProblem* p, int pass) {
+    if (!ncde_lowrank_supported(p, pass)) return NCDE_ERR_UNSUPPORTED;
+    if (pass == 0) return 256;
+    const Layout y = make_layout(p);
+    return (int64_t)sizeof(float) * (int64_t)y.n_wg * (int64_t)y.theta_size + 256;
+}
+
+int ncde_lowrank_forward(const NcdeProblem* p, float* out, float* stages, hipStream_t st) {
+    if (!ncde_lowrank_supported(p, 0)) return NCDE_ERR_UNSUPPORTED;
+    const Layout y = make_layout(p);
+    const LrPlan v = lr_plan(p, y);
+    KArgs a;
+    fill_kargs(p, y, &a);
+    a.out = out;
+    a.stages = stages;
+    a.wres_o = v.res_fwd;
+    if (ncde_lds_optin((const void*)ncde_fwd_lowrank, v.lds_fwd) != hipSuccess) return NCDE_ERR_HIP;
+    hipLaunchKernelGGL(ncde_fwd_lowrank, dim3(y.n_wg), dim3(LR_THREADS), v.lds_fwd, st, a);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+}
+
+int ncde_lowrank_adjoint(const NcdeProblem* p, const float* src, const float* grad_out, const NcdeGrads* g, void* ws, hipStream_t st,
+                         bool main_kernel_only, bool discrete) {
+    if (!ncde_lowrank_supported(p, discrete ? 2 : 1)) return NCDE_ERR_UNSUPPORTED;
+    const Layout y = make_layout(p);
+    const LrPlan v = lr_plan(p, y);
+    KArgs a;
+    fill_kargs(p, y, &a);
+    a.grad_out = grad_out; a.grad_z0 = g->grad_z0;
+    if (discrete) { a.stages = const_cast<float*>(src); a.discrete = 1; }
+    else a.z_out = src;
+    a.gpart = (float*)ws;
+    a.gacc_in_lds = v.gacc_in_lds;
+    a.wres_o = v.res_adj;
+    if (ncde_lds_optin((const void*)ncde_adj_lowrank, v.lds_adj) != hipSuccess) return NCDE_ERR_HIP;
+    hipLaunchKernelGGL(ncde_adj_lowrank, dim3(y.n_wg), dim3(LR_THREADS), v.lds_adj, st, a);
+    if (hipGetLastError() != hipSuccess) return NCDE_ERR_HIP;
+    if (main_kernel_only) return NCDE_OK;
+    return launch_reduce_partials(p, y, g, (const float*)ws, y.n_wg, st);
+}

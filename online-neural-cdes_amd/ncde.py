@@ -12,7 +12,7 @@ from torch import nn
 
 from .interpolation import LinearInterpolation, NaturalCubicSpline, SmoothLinearInterpolation
 from .solver import cdeint
-from .vector_fields import GRUGatedVectorField, MinimalGatedVectorField, OriginalVectorField
+from .vector_fields import GRUGatedVectorField, LowRankVectorField, MinimalGatedVectorField, OriginalVectorField
 
 SPLINES = {
     "cubic": NaturalCubicSpline,
@@ -20,7 +20,8 @@ SPLINES = {
     "rectilinear": LinearInterpolation,
 }
 SMOOTHED = {"linear_cubic_smoothing": False, "linear_quintic_smoothing": True}      # name -> match_second_derivatives
-VECTOR_FIELDS = {"original": OriginalVectorField, "minimal": MinimalGatedVectorField, "gru": GRUGatedVectorField}
+VECTOR_FIELDS = {"original": OriginalVectorField, "minimal": MinimalGatedVectorField, "gru": GRUGatedVectorField,
+                 "low-rank": LowRankVectorField}
 
 
 class NeuralCDE(nn.Module):
@@ -62,7 +63,7 @@ class NeuralCDE(nn.Module):
         self.atol, self.rtol = 1e-5, 1e-3
         self.cdeint_options = {"min_step": 0.5} if solver == "dopri5" else {"step_size": 1}      # ncde.py:130-134
         if vector_field not in VECTOR_FIELDS:
-            raise NotImplementedError("vector_field '%s' (sparse / low-rank) is outside the fused path" % vector_field)
+            raise NotImplementedError("vector_field '%s' is not implemented (the sparse field needs the third-party sparselinear package)" % vector_field)
         self.func = VECTOR_FIELDS[vector_field](input_dim=input_dim, hidden_dim=hidden_dim,
                                                 hidden_hidden_dim=hidden_hidden_dim, num_layers=num_layers,
                                                 sparsity=sparsity, vector_field_type=vector_field_type)

@@ -27,18 +27,20 @@ class FieldSpec:
     """What the fused kernels need to know about ``func``: the Linear+ReLU stack (entries may repeat
     the same Parameters = a shared layer) and the final Linear (+tanh, viewed [H, C])."""
 
-    def __init__(self, layers, Wo, bo, kind="original", mode="matmul", Wg=None, bg=None, Wr=None, br=None):
+    def __init__(self, layers, Wo, bo, kind="original", mode="matmul", Wg=None, bg=None, Wr=None, br=None, rank=0):
         self.layers = list(layers)
         self.Wo, self.bo = Wo, bo
         # variants (src/ncde/vector_fields/gating.py; vector_field_type of solver.py:112-137)
         self.kind, self.mode = kind, mode
         self.Wg, self.bg, self.Wr, self.br = Wg, bg, Wr, br
+        # kind "lowrank" (src/ncde/vector_fields/sparsity.py:33-55): Wo, bo = M_h [H * rank, .], Wg, bg = M_o [rank * C, .]
+        self.rank = int(rank)
 
     def extra_params(self):
         out = []
         if self.kind == "gru":
             out += [self.Wr, self.br]
-        if self.kind in ("minimal", "gru"):
+        if self.kind in ("minimal", "gru", "lowrank"):
             out += [self.Wg, self.bg]
         return out
 
@@ -72,7 +74,7 @@ def _unfused_reason(X, func, z0, t, adjoint, adjoint_params, method=None):
     if method == "dopri5":      # the adaptive kernels evaluate the original field with the matmul input only
         spec = func.fused_spec()
         if spec.kind != "original" or spec.mode != "matmul":
-            return "method='dopri5' with a gated vector field or the evaluate / derivative input"
+            return "method='dopri5' with a gated or low-rank vector field or the evaluate / derivative input"
     # decreasing output times?  X.interval / X.grid_points are tagged and known to increase: no device sync for them
     # (ADVICE round 4); any other tensor is copied to the host ONCE (_host_times, shared with _time_mode / _time_plan).
     if not _is_tagged_time(X, t):
@@ -191,12 +193,18 @@ def build_problem(coeffs, interp, z0, spec, method, output, flags=0, plan=None):
     p.Wo, p.bo = spec.Wo.data_ptr(), spec.bo.data_ptr()
     d_last = spec.layers[-1][0].shape[0] if spec.layers else H
     rows = H * p.channels if spec.mode == "matmul" else H
+    rows_g = rows
+    if spec.kind == "lowrank":      # M_h [H * R, .] and M_o [R * C, .]; the rank travels in the top byte of flags
+        if not 1 <= spec.rank <= 255:
+            raise ValueError("low-rank field: rank %d outside [1, 255]" % spec.rank)
+        rows, rows_g = H * spec.rank, spec.rank * p.channels
+        p.flags = flags | _lib.FLAG_FIELD_RANK(spec.rank)
     if tuple(spec.Wo.shape) != (rows, d_last):
         raise ValueError("final layer must be [%d, %d], got %s" % (rows, d_last, tuple(spec.Wo.shape)))
     p.field_kind, p.field_input = _lib.FIELD_KIND[spec.kind], _lib.FIELD_INPUT[spec.mode]
     if spec.kind != "original":
-        if tuple(spec.Wg.shape) != (rows, d_last):
-            raise ValueError("sigmoid head must be [%d, %d], got %s" % (rows, d_last, tuple(spec.Wg.shape)))
+        if tuple(spec.Wg.shape) != (rows_g, d_last):
+            raise ValueError("second head must be [%d, %d], got %s" % (rows_g, d_last, tuple(spec.Wg.shape)))
         p.Wg, p.bg = spec.Wg.data_ptr(), spec.bg.data_ptr()
     if spec.kind == "gru":
         d0 = H if spec.mode == "matmul" else H + p.channels

@@ -6,6 +6,7 @@
 ``nfe`` counter, and a plain-torch ``forward(t, h)`` for use outside ``cdeint``.
 ``MLPField`` is the un-shared general stack (the toy's CDEFunc, experiments/sim_bm_toy_example.py:10-30).
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -21,8 +22,6 @@ class BaseVectorField(nn.Module):
         super().__init__()
         if vector_field_type not in ("matmul", "evaluate", "derivative"):
             raise ValueError("vector_field_type string not recognised")
-        if sparsity is not None:
-            raise NotImplementedError("sparse / low-rank fields (third-party sparselinear) are outside the fused path")
         self.input_dim, self.hidden_dim = input_dim, hidden_dim
         self.hidden_hidden_dim, self.num_layers = hidden_hidden_dim, num_layers
         self.sparsity, self.vector_field_type = sparsity, vector_field_type
@@ -39,6 +38,11 @@ class BaseVectorField(nn.Module):
         self.net_to_hh = nn.Sequential(*mods)
         self.additional_network_initialisation()
 
+    def _refuse_sparsity(self):
+        """The dense fields take the reference's ``sparsity`` argument and, as before, accept None only."""
+        if self.sparsity is not None:
+            raise NotImplementedError("sparsity is read by LowRankVectorField only (the sparse field needs third-party sparselinear)")
+
     def _inner_layers(self):
         return [(m.weight, m.bias) for m in self.net_to_hh if isinstance(m, nn.Linear)]
 
@@ -52,6 +56,7 @@ class BaseVectorField(nn.Module):
 
 class OriginalVectorField(BaseVectorField):
     def additional_network_initialisation(self):
+        self._refuse_sparsity()
         self.tanh_output_layer = nn.Sequential(nn.Linear(self.hidden_hidden_dim, self.output_dim), nn.Tanh())
 
     def fused_spec(self):
@@ -66,6 +71,7 @@ class MinimalGatedVectorField(BaseVectorField):
     """sigmoid(Linear_z(hh)) * tanh(Linear_r(hh)) (gating.py:7-32); same ``state_dict`` keys as the reference."""
 
     def additional_network_initialisation(self):
+        self._refuse_sparsity()
         self.sigmoid_net = nn.Sequential(nn.Linear(self.hidden_hidden_dim, self.output_dim), nn.Sigmoid())
         self.tanh_net = nn.Sequential(nn.Linear(self.hidden_hidden_dim, self.output_dim), nn.Tanh())
 
@@ -82,6 +88,7 @@ class GRUGatedVectorField(BaseVectorField):
     """sigmoid_net(net(h)) * tanh_net(net(reset_net(h) * h)) (gating.py:35-61)."""
 
     def additional_network_initialisation(self):
+        self._refuse_sparsity()
         self.reset_net = nn.Sequential(nn.Linear(self.initial_dim, self.initial_dim), nn.Sigmoid())
         self.sigmoid_net = nn.Sequential(nn.Linear(self.hidden_hidden_dim, self.output_dim), nn.Sigmoid())
         self.tanh_net = nn.Sequential(nn.Linear(self.hidden_hidden_dim, self.output_dim), nn.Tanh())
@@ -95,6 +102,31 @@ class GRUGatedVectorField(BaseVectorField):
         inner = self.net_to_hh(h)
         reset = self.net_to_hh(self.reset_net(h) * h)
         return self.sigmoid_net(inner) * self.tanh_net(reset)
+
+
+class LowRankVectorField(BaseVectorField):
+    """tanh(P @ Q) with P = M_h(hh) viewed [H, R] and Q = M_o(hh) viewed [R, C] (sparsity.py:33-55): the output Linear HH -> H*C
+    of the original field replaced by two of HH -> H*R and HH -> R*C, R = ceil(C (1 - sparsity)).  Same constructor and
+    ``state_dict`` keys (``net_to_hh.*``, ``M_h.*``, ``M_o.*``) as the reference; fused on ncde_fwd_lowrank / ncde_adj_lowrank."""
+
+    def additional_network_initialisation(self):
+        assert self.sparsity is not None, "sparse methods must have a sparsity!"
+        assert self.vector_field_type == "matmul", "Sparse method only work for the matmul vector field type."
+        # the reference's expression, as written: checkpoint shapes depend on its floating-point result ((10, 0.7) -> 4)
+        self.rank = int(np.ceil(self.input_dim * (1 - self.sparsity)))
+        self.M_h = nn.Linear(self.hidden_hidden_dim, self.hidden_dim * self.rank)
+        self.M_o = nn.Linear(self.hidden_hidden_dim, self.input_dim * self.rank)
+        self.tanh = nn.Tanh()
+
+    def fused_spec(self):
+        return FieldSpec(self._inner_layers(), self.M_h.weight, self.M_h.bias, "lowrank", "matmul", self.M_o.weight, self.M_o.bias,
+                         rank=self.rank)
+
+    def _forward(self, h):
+        inner = self.net_to_hh(h)
+        M_h = self.M_h(inner).reshape(-1, self.hidden_dim, self.rank)
+        M_o = self.M_o(inner).reshape(-1, self.rank, self.input_dim)
+        return self.tanh(M_h @ M_o)
 
 
 class MLPField(nn.Module):
