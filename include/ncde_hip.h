@@ -404,6 +404,38 @@ int ncde_prepare_smooth(const float* x, int B, int T, int C, double eps, int ord
  * other bad arguments NCDE_ERR_INVALID, as for ncde_prepare_smooth. */
 int ncde_prepare_smooth_backward(const float* grad_rows, int B, int T, int C, double eps, int order, float* grad_x, void* stream);
 
+/* ---- causal (online) control paths: a prediction at t_k may only see observations up to t_k ---------------------------------
+ * ncde_prepare_fill: the two fill arguments of the reference's torchcde.linear_interpolation_coeffs (interpolation_linear.py:159-173)
+ * and misc.forward_fill (misc.py:103-126).  x, out: [B, L, C] fp32 device, contiguous, x != out; L >= 1.
+ *   has_initial != 0  NaNs of the first time row become (float)initial_value           (initial_value_if_nan)
+ *   forward_fill != 0 then every channel is filled forward along time; NaNs in front of a channel's first observation stay NaN
+ * Values are copied, never computed.  One workgroup per sample, one launch on `stream`, `out` written completely. */
+int ncde_prepare_fill(const float* x, int B, int L, int C, int has_initial, double initial_value, int forward_fill, float* out, void* stream);
+
+/* The linear / rectilinear hybrid scheme (src/ncde/interpolation.py:191-253; time is channel 0): linear channels move with time,
+ * rectilinear channels step, and a knot is added only where a rectilinear channel changes.  The full table of a sample has 2L-1
+ * rows,  row 2i = (t_i, lin_i, rect_i),  row 2i+1 = (t_{i+1}, lin_{i+1}, rect_i);  row 0 is kept, any other row iff its time or
+ * one of its rectilinear values differs (!=) from the row before it; kept rows are packed to the front; a sample shorter than T
+ * repeats its last kept row.
+ *   x_filled   [B, L, C]: time in channel 0 and the rectilinear channels after ncde_prepare_fill(has_initial, 0.0, forward_fill)
+ *              (no NaN left in them; the other channels are not read)
+ *   x_linear   [B, L, NL], NL = C - 1 - n_rect: the linear channels in ascending channel order, NaN filled (ncde_prepare_fill with
+ *              initial value 0.0, then ncde_prepare_linear on the gathered channels); not read (may be NULL) when NL == 0
+ *   rect_idx   DEVICE pointer to n_rect distinct int32 channel indices in [1, C) (NULL when n_rect == 0); the caller validates
+ *              them, an index outside [1, C) is ignored by the kernels
+ * ncde_prepare_hybrid_count (pass 1): keep flag of every row, exclusive prefix sum per sample (wave scan, carried across the waves
+ *   and across chunks of 256 rows) -> row positions in `workspace`, lengths[b] = kept rows of sample b (int32 device, [B]), and
+ *   *max_len = max_b lengths[b] (int32 device): the ONE value the host has to read to size the output (T = *max_len).
+ * ncde_prepare_hybrid_write (pass 2): out [B, T, C], every element written (kept rows scattered to their positions, rows
+ *   lengths[b] .. T-1 = the last kept row).  `workspace` and `lengths` as pass 1 left them, lengths[b] <= T <= 2L-1.
+ * Both: launches on `stream` only, no atomics, bit-reproducible.  Workspace: ncde_prepare_hybrid_workspace_bytes(B, L, C).
+ * Bad arguments NCDE_ERR_INVALID (also a sample of 2^31 elements or more), a workspace too small NCDE_ERR_WORKSPACE. */
+int64_t ncde_prepare_hybrid_workspace_bytes(int B, int L, int C);
+int ncde_prepare_hybrid_count(const float* x_filled, int B, int L, int C, const int* rect_idx, int n_rect, void* workspace,
+                              size_t workspace_bytes, int* lengths, int* max_len, void* stream);
+int ncde_prepare_hybrid_write(const float* x_filled, const float* x_linear, int B, int L, int C, int n_rect, const void* workspace,
+                              size_t workspace_bytes, const int* lengths, int T, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

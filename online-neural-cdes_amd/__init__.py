@@ -12,5 +12,6 @@ from .vector_fields import (GRUGatedVectorField, LowRankVectorField, MinimalGate
                             OriginalVectorField)
 from .ncde import NeuralCDE  # noqa: F401
 from .stacked import StackedNeuralCDE  # noqa: F401
-from .coefficients import linear_interpolation_coeffs, natural_cubic_coeffs, natural_cubic_spline_coeffs  # noqa: F401
+from .coefficients import (forward_fill, linear_interpolation_coeffs, linear_rectilinear_hybrid_coeffs, natural_cubic_coeffs,  # noqa: F401
+                           natural_cubic_spline_coeffs)
 from .losses import MaskedTemporalLoss, RMSELoss, TemporalLossWrapper, masked_mean  # noqa: F401

@@ -120,6 +120,7 @@ EXPORTS = (
     "ncde_prepare_workspace_bytes", "ncde_prepare_linear", "ncde_prepare_cubic", "ncde_prepare_linear_grid", "ncde_prepare_cubic_grid",
     "ncde_prepare_kernel_name",
     "ncde_smooth_pieces", "ncde_prepare_smooth", "ncde_prepare_smooth_backward",
+    "ncde_prepare_fill", "ncde_prepare_hybrid_workspace_bytes", "ncde_prepare_hybrid_count", "ncde_prepare_hybrid_write",
     "ncde_stage_record_bytes", "ncde_forward_record", "ncde_backward",
     "ncde_time_plan_build", "ncde_dopri5_workspace_bytes", "ncde_dopri5_forward", "ncde_dopri5_adjoint",
     "ncde_dopri5_record_bytes", "ncde_dopri5_forward_record", "ncde_dopri5_backward", "ncde_dopri5_kernel_name",
@@ -211,6 +212,14 @@ def lib():
     h.ncde_prepare_cubic_grid.restype = ctypes.c_int
     h.ncde_prepare_kernel_name.argtypes = [i32, i32, i32, i32, i32, i32]
     h.ncde_prepare_kernel_name.restype = ctypes.c_char_p
+    h.ncde_prepare_fill.argtypes = [vp, i32, i32, i32, i32, ctypes.c_double, i32, vp, vp]
+    h.ncde_prepare_fill.restype = ctypes.c_int
+    h.ncde_prepare_hybrid_workspace_bytes.argtypes = [i32, i32, i32]
+    h.ncde_prepare_hybrid_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_prepare_hybrid_count.argtypes = [vp, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp]
+    h.ncde_prepare_hybrid_count.restype = ctypes.c_int
+    h.ncde_prepare_hybrid_write.argtypes = [vp, vp, i32, i32, i32, i32, vp, sz, vp, i32, vp, vp]
+    h.ncde_prepare_hybrid_write.restype = ctypes.c_int
     h.ncde_time_plan_build.argtypes = [P, ctypes.POINTER(NcdeTimeSpec), vp, sz, ctypes.POINTER(NcdeTimePlanInfo)]
     h.ncde_time_plan_build.restype = ctypes.c_int
     TS, AO, AS = ctypes.POINTER(NcdeTimeSpec), ctypes.POINTER(NcdeAdaptiveOptions), ctypes.POINTER(NcdeAdaptiveStats)

@@ -5,6 +5,7 @@
 //   forward fill + rectilinear interleave     interpolation_linear.py:85-128, misc.py:103-126
 //   NaN fill of the linear knots              interpolation_linear.py:13-82, 131-180
 //   natural cubic coefficients                interpolation_cubic.py:7-53 (tridiagonal solve: misc.py:13-67)
+//   causal fills, linear / rectilinear hybrid  interpolation_linear.py:159-173, misc.py:103-126, src/ncde/interpolation.py:191-253
 // All on the default integer time grid, fp32, operation order of the reference (build uses -ffp-contract=off).
 #include <hip/hip_runtime.h>
 
@@ -723,6 +724,164 @@ __global__ __launch_bounds__(256) void ncde_smooth_coeffs_bwd_kernel(const float
     }
 }
 
+// ---- causal control paths (interpolation_linear.py:159-173, misc.py:103-126, src/ncde/interpolation.py:191-253) ----------------------
+// Everything below copies values and compares them; nothing is computed, so the results carry the bits of the input.
+
+// initial value + forward fill: one workgroup per sample, thread <-> (time chunk k, channel c) as in ncde_linear_coeffs_lds_kernel:
+// a serial pass over the chunk (rows coalesced over the channels), then the leading gap of the chunk takes the last value of the
+// nearest earlier chunk that holds one.  C > 256: one chunk, the threads loop over the channels (no carry).
+__global__ __launch_bounds__(256) void ncde_fill_kernel(const float* __restrict__ x, int L, int C, int has_initial, float initial, int ffill,
+                                                        float* out) {
+    __shared__ float car_v[256];      // [nch][C] last value of the chunk
+    __shared__ int car_has[256];      //          ... if it holds one
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* xs = x + (long long)b * L * C;
+    float* os = out + (long long)b * L * C;
+    const int nch = C <= 256 ? 256 / C : 1;
+    const int cl = (L + nch - 1) / nch;
+    const int k = tid / C, c = tid - k * C;
+    const bool act = k < nch;
+    const int i0 = min(L, k * cl), i1 = min(L, i0 + cl);
+    for (int cc = act ? c : C; cc < C; cc += 256) {
+        float last = 0.0f;
+        int has = 0;
+        for (int i = i0; i < i1; ++i) {
+            float v = xs[i * C + cc];
+            if (i == 0 && has_initial && isnan(v)) v = initial;
+            if (ffill) {
+                if (!isnan(v)) { last = v; has = 1; }
+                else if (has) v = last;
+            }
+            os[i * C + cc] = v;
+        }
+        if (C <= 256) { car_v[k * C + cc] = last; car_has[k * C + cc] = has; }
+    }
+    __syncthreads();
+    if (ffill && C <= 256 && act && k > 0) {
+        int kk = k - 1;
+        while (kk >= 0 && !car_has[kk * C + c]) --kk;
+        if (kk >= 0) {
+            const float cin = car_v[kk * C + c];
+            for (int i = i0; i < i1 && isnan(os[i * C + c]); ++i) os[i * C + c] = cin;      // this thread's own stores of the first pass
+        }
+    }
+}
+
+__device__ __forceinline__ int wave_inclusive_sum(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// hybrid scheme, pass 1: one workgroup per sample; thread <-> row of the full table, 256 rows per chunk.  Row 0 is kept, row 2i+1
+// iff t_{i+1} != t_i, row 2i+2 iff a rectilinear channel differs between i and i+1.  Exclusive prefix sum of the keep flags: wave
+// scan, the four wave totals through LDS, the chunk total carried in a register.  pos[b][r] = position of row r among the kept
+// rows (-1: dropped), last_row[b] = the last kept row, lengths[b] = how many are kept.  Workgroup 0 also writes the channel map
+// pass 2 reads: -2 time, -1 rectilinear, n >= 0 the n-th linear channel.
+__global__ __launch_bounds__(256) void ncde_hybrid_count_kernel(const float* __restrict__ xf, int L, int C, const int* __restrict__ rect_idx, int n_rect,
+                                                                int* __restrict__ pos, int* __restrict__ last_row, int* __restrict__ cmap,
+                                                                int* __restrict__ lengths) {
+    __shared__ int wsum[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int R = 2 * L - 1;
+    if (b == 0) {
+        for (int c = tid; c < C; c += 256) {
+            int below = 0;
+            bool is_rect = false;
+            for (int q = 0; q < n_rect; ++q) {
+                const int rc = rect_idx[q];
+                is_rect = is_rect || rc == c;
+                below += (rc > 0 && rc < c) ? 1 : 0;
+            }
+            cmap[c] = c == 0 ? -2 : (is_rect ? -1 : c - 1 - below);
+        }
+    }
+    const float* xs = xf + (long long)b * L * C;
+    int* ps = pos + (long long)b * R;
+    int carry = 0, my_row = -1, my_pos = -1;
+    for (int base = 0; base < R; base += 256) {
+        const int r = base + tid;
+        int keep = 0;
+        if (r == 0) {
+            keep = 1;
+        } else if (r < R && (r & 1)) {
+            const int i = r >> 1;
+            keep = xs[(i + 1) * C] != xs[i * C] ? 1 : 0;
+        } else if (r < R) {
+            const int j = r >> 1;
+            for (int q = 0; q < n_rect; ++q) {
+                const int rc = rect_idx[q];
+                if (rc > 0 && rc < C && xs[j * C + rc] != xs[(j - 1) * C + rc]) keep = 1;
+            }
+        }
+        const int incl = wave_inclusive_sum(keep, lane);
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int ww = 0; ww < 4; ++ww) {
+            const int s = wsum[ww];
+            before += ww < w ? s : 0;
+            total += s;
+        }
+        const int p = carry + before + incl - keep;
+        if (r < R) ps[r] = keep ? p : -1;
+        if (keep) { my_row = r; my_pos = p; }
+        carry += total;
+        __syncthreads();      // wsum is written again by the next chunk
+    }
+    if (my_pos == carry - 1) last_row[b] = my_row;      // exactly one thread: row 0 is always kept
+    if (tid == 0) lengths[b] = carry;
+}
+
+// batch maximum of the kept counts: one workgroup, a fixed reduction order
+__global__ __launch_bounds__(256) void ncde_hybrid_max_kernel(const int* __restrict__ lengths, int B, int* __restrict__ max_len) {
+    __shared__ int wmax[4];
+    const int tid = threadIdx.x;
+    int m = 0;
+    for (int b = tid; b < B; b += 256) m = max(m, lengths[b]);
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_down(m, d, 64));
+    if ((tid & 63) == 0) wmax[tid >> 6] = m;
+    __syncthreads();
+    if (tid == 0) *max_len = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+}
+
+// hybrid scheme, pass 2: one workgroup per sample, thread <-> (row offset, channel) as the output loops of
+// ncde_linear_coeffs_lds_kernel.  Kept rows go to out[b][pos]; rows lengths[b] .. T-1 repeat the last kept row (read from the
+// source, not from `out`).  The positions of a sample are a bijection onto 0 .. lengths[b]-1, so every element of out[b] is written.
+__global__ __launch_bounds__(256) void ncde_hybrid_write_kernel(const float* __restrict__ xf, const float* __restrict__ xl, int L, int C, int NL,
+                                                                const int* __restrict__ pos, const int* __restrict__ last_row,
+                                                                const int* __restrict__ cmap, const int* __restrict__ lengths, int T,
+                                                                float* __restrict__ out) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int R = 2 * L - 1;
+    const float* xs = xf + (long long)b * L * C;
+    const float* xls = xl + (long long)b * L * NL;      // (not dereferenced when NL == 0)
+    const int* ps = pos + (long long)b * R;
+    float* os = out + (long long)b * T * C;
+    const int count = max(lengths[b], 0), lr = last_row[b];
+    const int rp = 256 / C > 0 ? 256 / C : 1;
+    const int r0 = tid / C, c = tid - r0 * C;
+    const bool active = C <= 256 ? r0 < rp : true;
+    for (int cc = c; cc < C && active; cc += 256) {
+        const int m = cmap[cc];
+        // row r of the full table: time and the linear channels are those of raw index (r+1)/2, the rectilinear ones of r/2
+        auto value = [&](int r) { return m == -2 ? xs[((r + 1) >> 1) * C] : (m == -1 ? xs[(r >> 1) * C + cc] : xls[((r + 1) >> 1) * NL + m]); };
+        for (int r = r0; r < R; r += rp) {
+            const int p = ps[r];
+            if (p >= 0 && p < T) os[p * C + cc] = value(r);
+        }
+        if (count < T && lr >= 0 && lr < R) {
+            const float v = value(lr);
+            for (int p = count + r0; p < T; p += rp) os[p * C + cc] = v;
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -869,6 +1028,55 @@ int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C,
 
 int ncde_prepare_cubic(const float* x, int B, int L, int C, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     return ncde_prepare_cubic_grid(x, nullptr, B, L, C, out, workspace, workspace_bytes, stream);
+}
+
+// ---- causal control paths: fills and the linear / rectilinear hybrid scheme -----------------------------------------------------
+// one sample is indexed with int: its largest table, (2L-1) x C, has to stay below 2^31 elements
+static bool causal_shape_ok(int B, int L, int C) {
+    return B >= 1 && L >= 1 && C >= 1 && (2 * (long long)L - 1) * C <= 0x7fffffffLL;
+}
+
+int ncde_prepare_fill(const float* x, int B, int L, int C, int has_initial, double initial_value, int forward_fill, float* out, void* stream) {
+    if (!x || !out || x == out || !causal_shape_ok(B, L, C)) return NCDE_ERR_INVALID;
+    hipLaunchKernelGGL(ncde_fill_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, L, C, has_initial != 0 ? 1 : 0, (float)initial_value,
+                       forward_fill != 0 ? 1 : 0, out);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+}
+
+// workspace of the hybrid scheme (int32): pos [B][2L-1] | last_row [B] | cmap [C]
+int64_t ncde_prepare_hybrid_workspace_bytes(int B, int L, int C) {
+    if (L < 2 || C < 2 || !causal_shape_ok(B, L, C)) return NCDE_ERR_INVALID;
+    return (int64_t)sizeof(int) * ((int64_t)B * (2 * (int64_t)L - 1) + B + C) + 256;
+}
+
+int ncde_prepare_hybrid_count(const float* x_filled, int B, int L, int C, const int* rect_idx, int n_rect, void* workspace,
+                              size_t workspace_bytes, int* lengths, int* max_len, void* stream) {
+    const int64_t need = ncde_prepare_hybrid_workspace_bytes(B, L, C);
+    if (need < 0 || !x_filled || !workspace || !lengths || !max_len || n_rect < 0 || n_rect > C - 1 || (n_rect > 0 && !rect_idx))
+        return NCDE_ERR_INVALID;
+    if ((int64_t)workspace_bytes < need) return NCDE_ERR_WORKSPACE;
+    int* pos = (int*)workspace;
+    int* last_row = pos + (size_t)B * (2 * (size_t)L - 1);
+    int* cmap = last_row + B;
+    hipLaunchKernelGGL(ncde_hybrid_count_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_filled, L, C, rect_idx, n_rect, pos, last_row, cmap,
+                       lengths);
+    hipLaunchKernelGGL(ncde_hybrid_max_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)lengths, B, max_len);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
+}
+
+int ncde_prepare_hybrid_write(const float* x_filled, const float* x_linear, int B, int L, int C, int n_rect, const void* workspace,
+                              size_t workspace_bytes, const int* lengths, int T, float* out, void* stream) {
+    const int64_t need = ncde_prepare_hybrid_workspace_bytes(B, L, C);
+    if (need < 0 || !x_filled || !workspace || !lengths || !out || n_rect < 0 || n_rect > C - 1 || T < 1 || T > 2 * L - 1) return NCDE_ERR_INVALID;
+    const int NL = C - 1 - n_rect;
+    if (NL > 0 && !x_linear) return NCDE_ERR_INVALID;
+    if ((int64_t)workspace_bytes < need) return NCDE_ERR_WORKSPACE;
+    const int* pos = (const int*)workspace;
+    const int* last_row = pos + (size_t)B * (2 * (size_t)L - 1);
+    const int* cmap = last_row + B;
+    hipLaunchKernelGGL(ncde_hybrid_write_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_filled, x_linear, L, C, NL, pos, last_row, cmap, lengths,
+                       T, out);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
 }  // extern "C"
