@@ -436,6 +436,54 @@ int ncde_prepare_hybrid_count(const float* x_filled, int B, int L, int C, const 
 int ncde_prepare_hybrid_write(const float* x_filled, const float* x_linear, int B, int L, int C, int n_rect, const void* workspace,
                               size_t workspace_bytes, const int* lengths, int T, float* out, void* stream);
 
+/* ---- online inference: carry the CDE state of B independent streams from one observation to the next --------------------------
+ * What a served model needs instead of NeuralCDE(return_sequences=True) on the whole prefix (src/ncde/ncde.py:214-243): after the
+ * k-th observation the state z equals row 2k (rectilinear) / row k (linear) of the batch solve on t = X.grid_points with
+ * step_size 1, at the cost of the one or two solver steps the new observation adds.
+ *   fill       NaN = not observed.  NaNs of a stream's FIRST row become initial_value_if_nan, later NaNs the stream's last filled
+ *              value: linear_interpolation_coeffs(x, rectilinear=time_index, initial_value_if_nan=v) for a rectilinear stream,
+ *              linear_interpolation_coeffs(x, initial_value_if_nan=v, forward_fill=True) for a linear one
+ *              (interpolation_linear.py:159-173).  Values are copied, never computed; the time channel is never NaN.
+ *   pieces     linear: one piece per observation;  rectilinear: two (first only the time channel moves, then only the values).
+ *   solve      one step of p->method per piece; stage 1 of a step reads the piece to the LEFT of its knot -- the previous piece, or
+ *              the step's own piece at a stream's very first step (interpolation_linear.py:212-219) -- every later stage its own.
+ *   state      z [B, H], last_row [B, C] (the last filled row), prev_dx [B, C] (dX/dt of the last piece), count [B] int32
+ *              (observations received).  A stream's first row (count == 0) initialises it: the row is filled and kept, count
+ *              becomes 1, z is left as the caller set it (z(t0): the read-in layer of the model) and no solver step is taken.
+ *   active     uint8 [n_rows, B] or NULL = every stream receives every row.  A stream whose entry is 0 keeps its state untouched;
+ *              its output row is the readout of its unchanged z.
+ *   readout    out [n_rows, B, n_out] = Wf z + bf after each row (Wf [n_out, H] row-major, bf [n_out] or NULL);  Wf == NULL: no
+ *              readout, z_out is then required.  z_out (optional) [n_rows, B, H]: z after each row.
+ * The step reads of the problem: batch, channels, hidden, method and the vector field (original field, matmul input; interp must be
+ * NCDE_INTERP_LINEAR) -- coeffs, z0, n_knots, output and the time plan are ignored.  ONE launch on `stream`, one workgroup per
+ * 16 streams, no workspace, no atomics, no synchronisation; rows of one call are processed in order.  The caller owns every buffer.
+ * ncde_stream_workspace_bytes: 0, or the status the step would answer for this problem (NCDE_ERR_UNSUPPORTED for a gated / low-rank
+ * field, the evaluate / derivative inputs and shapes beyond the generic forward's LDS plan; NCDE_ERR_INVALID for a malformed
+ * problem).  ncde_stream_kernel_name: "ncde_stream_step", or NULL on such a problem. */
+typedef struct NcdeStream {
+    int32_t n_rows;             /* m >= 1 new observation rows */
+    int32_t rectilinear;        /* 0: linear stream, else rectilinear */
+    int32_t time_index;         /* rectilinear: the time channel */
+    int32_t n_out;              /* rows of Wf */
+    const float* x;             /* x[r * x_stride_m + b * x_stride_b + c], element strides, channel stride 1 */
+    int64_t x_stride_m;
+    int64_t x_stride_b;         /* >= channels */
+    const uint8_t* active;      /* [n_rows, B] or NULL */
+    float initial_value_if_nan;
+    int32_t reserved_;
+    float* z;                   /* [B, H]  in / out */
+    float* last_row;            /* [B, C]  in / out */
+    float* prev_dx;             /* [B, C]  in / out */
+    int32_t* count;             /* [B]     in / out */
+    const float* Wf;
+    const float* bf;
+    float* out;
+    float* z_out;
+} NcdeStream;
+int64_t ncde_stream_workspace_bytes(const NcdeProblem* p);   /* < 0: status code */
+const char* ncde_stream_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,30 @@ class NcdeGrads(ctypes.Structure):
     ]
 
 
+class NcdeStream(ctypes.Structure):
+    """One online step (include/ncde_hip.h): the new rows, the four state buffers, the readout."""
+    _fields_ = [
+        ("n_rows", ctypes.c_int32),
+        ("rectilinear", ctypes.c_int32),
+        ("time_index", ctypes.c_int32),
+        ("n_out", ctypes.c_int32),
+        ("x", _c_float_p),
+        ("x_stride_m", ctypes.c_int64),
+        ("x_stride_b", ctypes.c_int64),
+        ("active", ctypes.c_void_p),
+        ("initial_value_if_nan", ctypes.c_float),
+        ("reserved_", ctypes.c_int32),
+        ("z", _c_float_p),
+        ("last_row", _c_float_p),
+        ("prev_dx", _c_float_p),
+        ("count", ctypes.c_void_p),
+        ("Wf", _c_float_p),
+        ("bf", _c_float_p),
+        ("out", _c_float_p),
+        ("z_out", _c_float_p),
+    ]
+
+
 EXPORTS = (
     "ncde_version", "ncde_last_error_string", "ncde_num_outputs", "ncde_workspace_bytes",
     "ncde_kernel_name", "ncde_forward", "ncde_adjoint", "ncde_time_kernel",
@@ -126,6 +150,7 @@ EXPORTS = (
     "ncde_dopri5_record_bytes", "ncde_dopri5_forward_record", "ncde_dopri5_backward", "ncde_dopri5_kernel_name",
     "ncde_coop_status_offset",
     "ncde_control_workspace_bytes", "ncde_control_kernel_name", "ncde_backward_control",
+    "ncde_stream_workspace_bytes", "ncde_stream_kernel_name", "ncde_stream_step",
 )
 
 _LIB = None
@@ -193,6 +218,12 @@ def lib():
     h.ncde_control_kernel_name.restype = ctypes.c_char_p
     h.ncde_backward_control.argtypes = [P, vp, vp, G, vp, vp, sz, vp]
     h.ncde_backward_control.restype = ctypes.c_int
+    h.ncde_stream_workspace_bytes.argtypes = [P]
+    h.ncde_stream_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_stream_kernel_name.argtypes = [P]
+    h.ncde_stream_kernel_name.restype = ctypes.c_char_p
+    h.ncde_stream_step.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
+    h.ncde_stream_step.restype = ctypes.c_int
     i32 = ctypes.c_int
     h.ncde_prepare_workspace_bytes.argtypes = [i32, i32, i32, i32]
     h.ncde_prepare_workspace_bytes.restype = ctypes.c_int64

@@ -104,6 +104,13 @@ class NeuralCDE(nn.Module):
         y = self.final_linear(z)
         return y[:, ::2] if (self.interpolation == "rectilinear" and self.return_filtered_rectilinear) else y
 
+    def online(self, batch_size, *, initial_value_if_nan=0.0, time_index=0):
+        """A handle that carries the state of ``batch_size`` streams from one observation to the next (online.py): ``step(x_new)``
+        answers what ``return_sequences=True`` on the whole prefix gives at the newest knot.  Over this module's own parameters
+        (no copies); interpolation 'linear' or 'rectilinear' only."""
+        from .online import OnlineNeuralCDE
+        return OnlineNeuralCDE(self, batch_size, initial_value_if_nan=initial_value_if_nan, time_index=time_index)
+
     def forward(self, inputs):
         X, z0 = self._control_and_start(inputs)
         z = cdeint(X, self.func, z0, t=X.grid_points if self.return_sequences else X.interval, adjoint=self.adjoint,

@@ -1,0 +1,260 @@
+"""Online inference: carry the CDE state of a batch of streams from one observation to the next.
+
+``NeuralCDE.online(batch_size)`` returns an ``OnlineNeuralCDE`` over the module's own parameters.  ``step(x_new)`` fills the new
+observation row(s) causally, appends the one (linear) or two (rectilinear) pieces they add to the control path, takes one solver
+step per piece and returns the readout -- what ``NeuralCDE(return_sequences=True)`` on the whole prefix gives at the same knot, at
+the cost of the new pieces only.  On the GPU (fp32, original field, matmul input) a call is ONE launch of ``ncde_stream_step``
+(csrc/ncde_stream.hip); anything else takes the torch-op step below behind the once-only "unfused" warning.
+
+State per stream: ``z`` [B, H], ``last_row`` [B, C] (the last filled row), ``prev_dx`` [B, C] (dX/dt of the last piece: stage 1 of
+the next step reads it, the reference's left-piece rule, interpolation_linear.py:212-219) and ``count`` [B] (observations received).
+"""
+import ctypes
+
+import torch
+
+from . import _lib, unfused
+
+_THIRD = 1.0 / 3.0
+_STAGE_TIMES = {"euler": (0.0,), "midpoint": (0.0, 0.5), "rk4": (0.0, _THIRD, 2.0 * _THIRD, 1.0)}
+STATE_KEYS = ("z", "last_row", "prev_dx", "count")
+
+
+def _rk_increment(f, method, y):
+    """Increment of one step with dt = 1, in the operation order of unfused._step (fixed_grid.py:6-29, rk_common.py:106-114);
+    f(j, y) evaluates stage j."""
+    if method == "euler":
+        return f(0, y)
+    if method == "midpoint":
+        return f(1, y + 0.5 * f(0, y))
+    k1 = f(0, y)
+    k2 = f(1, y + k1 * _THIRD)
+    k3 = f(2, y + (k2 - k1 * _THIRD))
+    k4 = f(3, y + (k1 - k2 + k3))
+    return (k1 + 3.0 * (k2 + k3) + k4) * 0.125
+
+
+class OnlineNeuralCDE:
+    def __init__(self, model, batch_size, initial_value_if_nan=0.0, time_index=0):
+        if model.interpolation not in ("linear", "rectilinear"):
+            raise ValueError("online inference needs a causal control path: interpolation 'linear' or 'rectilinear', not '%s' (a natural "
+                             "cubic or smoothed path at knot k depends on later observations)" % model.interpolation)
+        if model.solver not in _STAGE_TIMES:
+            raise ValueError("online inference takes fixed steps (solver 'rk4', 'midpoint' or 'euler'), not '%s'" % model.solver)
+        if isinstance(initial_value_if_nan, bool) or not isinstance(initial_value_if_nan, (int, float)):
+            raise ValueError("initial_value_if_nan must be a float (a stream whose first row holds a NaN needs a value to be causal)")
+        if int(batch_size) < 1:
+            raise ValueError("batch_size must be >= 1")
+        self.model = model
+        self.batch_size = int(batch_size)
+        self.rectilinear = model.interpolation == "rectilinear"
+        self.initial_value_if_nan = float(initial_value_if_nan)
+        self.time_index = int(time_index)
+        if self.rectilinear and not 0 <= self.time_index < model.input_dim:
+            raise ValueError("Time index must be in [0, %d], was given %d." % (model.input_dim - 1, self.time_index))
+        ref = next(model.func.parameters())
+        B, C, H = self.batch_size, model.input_dim, model.hidden_dim
+        self.z = torch.zeros(B, H, dtype=ref.dtype, device=ref.device)
+        self.last_row = torch.zeros(B, C, dtype=ref.dtype, device=ref.device)
+        self.prev_dx = torch.zeros(B, C, dtype=ref.dtype, device=ref.device)
+        self.count = torch.zeros(B, dtype=torch.int32, device=ref.device)
+        self._route = {}
+        self._may_init = True      # a stream may still be waiting for its first row (known on the host without a synchronisation)
+
+    # ---- state ---------------------------------------------------------------------------------------------------------------
+    def reset(self, mask=None):
+        """Forget every stream, or the streams of ``mask`` [B] (bool): their next row is a first row again."""
+        with torch.no_grad():
+            if mask is None:
+                for k in STATE_KEYS:
+                    getattr(self, k).zero_()
+            else:
+                mask = torch.as_tensor(mask, device=self.z.device).bool()
+                if tuple(mask.shape) != (self.batch_size,):
+                    raise ValueError("mask must be [%d], got %s" % (self.batch_size, tuple(mask.shape)))
+                for k in STATE_KEYS:
+                    t = getattr(self, k)
+                    t.masked_fill_(mask if t.dim() == 1 else mask[:, None], 0)
+        self._may_init = True
+
+    def state_dict(self):
+        return {k: getattr(self, k).detach().clone() for k in STATE_KEYS}
+
+    def load_state_dict(self, state):
+        for k in STATE_KEYS:
+            if k not in state:
+                raise ValueError("state_dict lacks '%s'" % k)
+            if tuple(state[k].shape) != tuple(getattr(self, k).shape):
+                raise ValueError("state '%s' must be %s, got %s" % (k, tuple(getattr(self, k).shape), tuple(state[k].shape)))
+        with torch.no_grad():
+            for k in STATE_KEYS:
+                getattr(self, k).copy_(state[k])
+        self._may_init = True
+
+    # ---- one call ------------------------------------------------------------------------------------------------------------
+    def step(self, x_new, static=None, active=None):
+        """x_new [B, C] or [m, B, C] (NaN = not observed; the time channel is never NaN) -> [B, out] or [m, B, out] (the hidden
+        state with apply_final_linear=False).  static [B, static_dim]: read while a stream may still receive its first row.
+        active [B] or [m, B] (bool / uint8): which streams received the row; the others keep their state untouched and answer
+        the readout of their unchanged z."""
+        m_ = self.model
+        B, C = self.batch_size, m_.input_dim
+        if not torch.is_tensor(x_new) or x_new.dim() not in (2, 3) or tuple(x_new.shape[-2:]) != (B, C):
+            raise ValueError("x_new must be [%d, %d] or [m, %d, %d], got %s" % (B, C, B, C, tuple(getattr(x_new, "shape", ()))))
+        single = x_new.dim() == 2
+        x = x_new.unsqueeze(0) if single else x_new
+        m = x.size(0)
+        if m < 1:
+            raise ValueError("x_new holds no row")
+        if x.dtype != self.z.dtype or x.device != self.z.device:
+            raise ValueError("x_new is %s on %s, the model's state %s on %s" % (x.dtype, x.device, self.z.dtype, self.z.device))
+        if x.requires_grad or any(getattr(self, k).requires_grad for k in STATE_KEYS):
+            raise ValueError("online inference runs under no_grad: the state and the observations must not require grad")
+        act = None
+        if active is not None:
+            act = torch.as_tensor(active, device=x.device)
+            if act.dim() == 1 and single:
+                act = act.unsqueeze(0)
+            if tuple(act.shape) != (m, B):
+                raise ValueError("active must be [%d] or [%d, %d], got %s" % (B, m, B, tuple(act.shape)))
+            act = (act != 0).to(torch.uint8).contiguous()
+        if m_.static_dim and self._may_init:
+            if static is None or tuple(static.shape) != (B, m_.static_dim):
+                raise ValueError("static must be [%d, %d] while a stream may still receive its first row" % (B, m_.static_dim))
+        with torch.no_grad():
+            advance = self._advance_kernel if self._use_kernel(x) else self._advance_torch
+            outs, r = [], 0
+            while self._may_init and r < m:      # rows that may be a stream's first: z(t0) from the read-in layer, row by row
+                ar = None if act is None else act[r]
+                self._start(x[r], static, ar)
+                outs.append(advance(x[r:r + 1], None if act is None else act[r:r + 1]))
+                if act is None:
+                    self._may_init = False
+                r += 1
+            if r < m:
+                outs.append(advance(x[r:], None if act is None else act[r:]))
+            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return out[0] if single else out
+
+    def _start(self, xr, static, act_r):
+        """z(t0) of the streams for which this row is the first (the model's read-in layer on [static,] [filled row])."""
+        m_ = self.model
+        first = self.count == 0
+        if act_r is not None:
+            first = first & (act_r != 0)
+        x0 = torch.where(torch.isnan(xr), torch.full_like(xr, self.initial_value_if_nan), xr)
+        feats = ([static] if m_.static_dim else []) + ([x0] if m_.use_initial else [])
+        if feats:
+            h0 = m_.initial_linear(feats[0] if len(feats) == 1 else torch.cat(feats, dim=-1))
+        else:
+            h0 = torch.zeros_like(self.z)
+        self.z.copy_(torch.where(first[:, None], h0, self.z))
+
+    def _readout(self, z):
+        return self.model.final_linear(z) if self.model.apply_final_linear else z
+
+    # ---- the torch-op step (any device, any dtype, every field) ----------------------------------------------------------------
+    def _advance_torch(self, x, act):
+        m_ = self.model
+        func, mode, method = m_.func, m_.vector_field_type, m_.solver
+        t0 = x.new_zeros(())
+        outs = []
+        for r in range(x.size(0)):
+            a = torch.ones_like(self.count, dtype=torch.bool) if act is None else act[r] != 0
+            xr = x[r]
+            fresh = (self.count == 0)[:, None]
+            fill = torch.where(torch.isnan(xr), torch.where(fresh, torch.full_like(xr, self.initial_value_if_nan), self.last_row), xr)
+            steps = (a & (self.count > 0))[:, None]
+            if self.rectilinear:      # the lagged row: new time, old values
+                mid = self.last_row.clone()
+                mid[:, self.time_index] = fill[:, self.time_index]
+            else:
+                mid = fill
+            da, db = mid - self.last_row, fill - mid
+            dl = torch.where((self.count == 1)[:, None], da, self.prev_dx)
+            z = self.z
+            for start, left, own in [(self.last_row, dl, da)] + ([(mid, da, db)] if self.rectilinear else []):
+                def f(j, y, start=start, left=left, own=own):
+                    dx = left if j == 0 else own
+                    if mode == "matmul":
+                        return (func(t0, y) @ dx.unsqueeze(-1)).squeeze(-1)
+                    if mode == "derivative":
+                        return func(t0, torch.cat([y, dx], dim=-1))
+                    # evaluate: X at the stage time; at the knot it is the knot's row itself (the batch solve forms it as
+                    # prev + 1 * (next - prev) on the left piece: equal up to one rounding)
+                    return func(t0, torch.cat([y, start if j == 0 else start + _STAGE_TIMES[method][j] * own], dim=-1))
+                z = z + _rk_increment(f, method, z)
+            self.z.copy_(torch.where(steps, z, self.z))
+            self.prev_dx.copy_(torch.where(steps, db if self.rectilinear else da, self.prev_dx))
+            self.last_row.copy_(torch.where(a[:, None], fill, self.last_row))
+            self.count.add_(a.to(torch.int32))
+            outs.append(self._readout(self.z).clone())
+        return torch.stack(outs, dim=0)
+
+    # ---- the fused step --------------------------------------------------------------------------------------------------------
+    def _problem(self):
+        m_ = self.model
+        spec = m_.func.fused_spec()
+        p = _lib.NcdeProblem()
+        p.abi_version = _lib.NCDE_ABI_VERSION
+        p.batch, p.hidden, p.channels, p.n_knots = self.batch_size, m_.hidden_dim, m_.input_dim, 2
+        p.interp, p.method, p.output, p.flags = _lib.INTERP["linear"], _lib.METHOD[m_.solver], _lib.OUT_KNOTS, 0
+        if len(spec.layers) > _lib.NCDE_MAX_LAYERS:
+            raise NotImplementedError("at most %d hidden layers" % _lib.NCDE_MAX_LAYERS)
+        p.n_layers = len(spec.layers)
+        for i, (w, b) in enumerate(spec.layers):
+            p.layer_out[i], p.layer_in[i] = w.shape
+            p.layer_W[i], p.layer_b[i] = w.data_ptr(), b.data_ptr()
+        p.Wo, p.bo = spec.Wo.data_ptr(), spec.bo.data_ptr()
+        p.field_kind, p.field_input = _lib.FIELD_KIND[spec.kind], _lib.FIELD_INPUT[spec.mode]
+        return p
+
+    def _use_kernel(self, x):
+        """The route, in the house style: CUDA fp32, the original field with the matmul input and a shape the query accepts take the
+        kernel; anything else the torch-op step, behind the once-only warning."""
+        key = (x.device.type, x.dtype)
+        if key in self._route:      # (the shapes of a module do not change: one query per device / dtype)
+            return self._route[key]
+        reason = None
+        if not hasattr(self.model.func, "fused_spec"):
+            reason = "online step: func does not expose fused_spec()"
+        elif not x.is_cuda or x.dtype != torch.float32:
+            reason = "online step: tensors are not fp32 on the GPU"
+        else:
+            spec = self.model.func.fused_spec()
+            if spec.kind != "original" or spec.mode != "matmul":
+                reason = "online step: a gated or low-rank vector field or the evaluate / derivative input"
+            else:
+                rc = _lib.lib().ncde_stream_workspace_bytes(ctypes.byref(self._problem()))
+                if rc == -2:
+                    reason = "online step: " + (_lib.lib().ncde_last_error_string() or b"").decode()
+                else:
+                    _lib.check(rc, "ncde_stream_workspace_bytes")
+        if reason is not None:
+            unfused.warn_once(reason)
+        self._route[key] = reason is None
+        return reason is None
+
+    def _advance_kernel(self, x, act):
+        m_ = self.model
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        m, B, H = x.size(0), self.batch_size, m_.hidden_dim
+        p = self._problem()
+        s = _lib.NcdeStream()
+        s.n_rows, s.rectilinear, s.time_index = m, int(self.rectilinear), self.time_index
+        s.x, s.x_stride_m, s.x_stride_b = x.data_ptr(), x.stride(0), x.stride(1)
+        s.active = None if act is None else act.data_ptr()
+        s.initial_value_if_nan = self.initial_value_if_nan
+        s.z, s.last_row, s.prev_dx, s.count = self.z.data_ptr(), self.last_row.data_ptr(), self.prev_dx.data_ptr(), self.count.data_ptr()
+        if m_.apply_final_linear:
+            fl = m_.final_linear
+            out = torch.empty(m, B, fl.out_features, dtype=torch.float32, device=x.device)
+            s.n_out, s.Wf, s.bf, s.out = fl.out_features, fl.weight.data_ptr(), (None if fl.bias is None else fl.bias.data_ptr()), out.data_ptr()
+        else:
+            out = torch.empty(m, B, H, dtype=torch.float32, device=x.device)
+            s.z_out = out.data_ptr()
+        with torch.cuda.device(x.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().ncde_stream_step(ctypes.byref(p), ctypes.byref(s), stream), "ncde_stream_step")
+        return out

@@ -1,0 +1,90 @@
+"""Per-observation latency of online inference at cfg2 dimensions (C 20, H = HH = 32, three layers, rectilinear, rk4; run on the GPU box).
+
+    python tools/time_stream.py [--out profiles/online_step_latency.json]      # ROUNDS=5 STEPS=200 REPS=10
+
+Legs, per batch size B in {1, 16, 256, 4096}:
+  online step      handle.step(x_k) of NeuralCDE.online, one new observation per call (one launch of ncde_stream_step)
+  prefix k         what a server has without it: one NeuralCDE(return_sequences=False) call on the prefix of k observations
+                   (k in {10, 100, 399}; the prefix's coefficients are built BEFORE the clock starts, which flatters this leg)
+Every call is followed by a device synchronise inside the timed window -- a server reads the prediction before the next observation
+arrives -- and the clock is the host's.  Every leg is warmed up, then the legs are timed ALTERNATING for ROUNDS rounds (STEPS online
+steps / REPS prefix calls per round); one line per (leg, round) so that the spread is visible, then median, min and max per leg.
+One 16-stream tile occupies one compute unit, so B <= 16 runs on a single CU: latency-bound by design."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+import ncde_amd  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None, help="write the medians and spreads here as JSON")
+    ap.add_argument("--batches", default="1,16,256,4096")
+    ap.add_argument("--prefixes", default="10,100,399")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "a timing needs the GPU"
+    ROUNDS, STEPS, REPS = (int(os.environ.get(k, d)) for k, d in (("ROUNDS", 5), ("STEPS", 200), ("REPS", 10)))
+    c = dict(bench.CONFIGS["cfg2"])
+    prefixes = [int(k) for k in args.prefixes.split(",")]
+    L = max(prefixes + [STEPS]) + 1
+    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
+    for B in (int(b) for b in args.batches.split(",")):
+        torch.manual_seed(0)
+        model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation="rectilinear", solver="rk4").cuda()
+        x = torch.from_numpy(ncde_amd.data.synthetic_series(B, L, c["C"] - 1, missing=c["missing"], seed=1234)).cuda()
+        rows = x.transpose(0, 1).contiguous()
+        handle = model.online(B)
+        coeffs = {k: ncde_amd.linear_interpolation_coeffs(x[:, :k].contiguous(), rectilinear=0, initial_value_if_nan=0.0) for k in prefixes}
+
+        def online(n):
+            handle.reset()
+            handle.step(rows[0])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(1, n + 1):
+                handle.step(rows[k])
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / n
+
+        def prefix(k, n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                with torch.no_grad():
+                    model(coeffs[k])
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / n
+
+        legs = [("online step", lambda: online(STEPS))] + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
+        online(20)
+        for k in prefixes:
+            prefix(k, 2)
+        times = {name: [] for name, _ in legs}
+        for r in range(ROUNDS):
+            for name, fn in legs:
+                dt = fn()
+                times[name].append(dt)
+                print("B %5d round %d  %-12s %10.1f us/call" % (B, r, name, dt * 1e6), flush=True)
+        for name, _ in legs:
+            v = times[name]
+            rec = {"B": B, "leg": name, "median_us": statistics.median(v) * 1e6, "min_us": min(v) * 1e6, "max_us": max(v) * 1e6}
+            report["legs"].append(rec)
+            print("B %5d median   %-12s %10.1f us/call  (min %.1f, max %.1f over %d rounds)" % (B, name, rec["median_us"], rec["min_us"], rec["max_us"], ROUNDS),
+                  flush=True)
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(report, fh, indent=1)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main()
