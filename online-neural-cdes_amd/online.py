@@ -237,8 +237,8 @@ class OnlineNeuralCDE:
 
     def _advance_kernel(self, x, act):
         m_ = self.model
-        if x.stride(2) != 1:
-            x = x.contiguous()
+        if x.stride(2) != 1 or x.stride(1) < m_.input_dim or x.stride(0) < 0:      # what the ABI takes: unit channels, rows that do not overlap
+            x = x.contiguous()                                                       # (an expand()ed batch has stride 0: copied)
         m, B, H = x.size(0), self.batch_size, m_.hidden_dim
         p = self._problem()
         s = _lib.NcdeStream()

@@ -9,7 +9,7 @@ import torch
 
 import golden_util as gu
 
-CASES = ["g19_a_rect", "g19_b_linear_ffill", "g19_c_rect_static", "g19_d_linear_single_step"]
+CASES = ["g19_a_rect", "g19_b_linear_ffill", "g19_c_rect_static", "g19_d_linear_single_step", "g19_e_rect_time2"]
 TIGHT_Z = 2e-5      # forward bound of the project's reference goldens, |delta| / max |ref| (tests/test_control_grad_gpu.py:21)
 _CACHE = {}
 

@@ -1,13 +1,16 @@
 """Golden vectors for online inference (tests/golden/g19_*.npz + MANIFEST_stream.json), produced by IMPORTING the reference on the
 build machine -- the way tools/gen_golden_control.py does, through oracle/gen_golden.py's shims.
 
-    python tools/gen_golden_stream.py
+    python tools/gen_golden_stream.py [NAME ...]
+
+With names (``g19_e_rect_time2``), only those cases are written and their manifest entries replaced or appended; the other files stay
+as committed (the zip bytes of an .npz are not reproducible).
 
 The reference only ever solves in batch; its NeuralCDE(return_sequences=True, solver="rk4") output at knot k is what an online step
 must reproduce after the k-th observation.  Every case is that model on coefficients from the reference's OWN builder
-(torchcde.linear_interpolation_coeffs with rectilinear=0 / forward_fill=True and initial_value_if_nan), on the CPU, in fp32 and fp64.
+(torchcde.linear_interpolation_coeffs with rectilinear=<the case's time channel> / forward_fill=True and initial_value_if_nan), on the CPU, in fp32 and fp64.
 A case holds
-    x         raw observations [B, L, C] with NaNs (time in channel 0, never NaN)       static    [B, static_dim] (case c)
+    x         raw observations [B, L, C] with NaNs (time in channel meta["time_index"], never NaN)       static    [B, static_dim] (case c)
     coeffs    what the builder made of them: [B, 2L-1, C] rectilinear, [B, L, C] linear (the filled rows: every 2nd / every row)
     sd_<key>  the model's state dict
     out       [B, L, n_out] outputs per observation         hidden    [B, T, H] the whole hidden sequence (T = 2L-1 / L)
@@ -40,7 +43,9 @@ CASES = [
     ("b_linear_ffill", "linear", (5, 12, 10, 3), 18, 5, 3, None, -0.5, 0.3, 2),
     ("c_rect_static", "rectilinear", (4, 16, 16, 1), 16, 4, 2, 2, 0.25, 0.3, 3),
     ("d_linear_single_step", "linear", (2, 8, 8, 2), 1, 2, 1, None, 0.0, 0.0, 4),
+    ("e_rect_time2", "rectilinear", (5, 10, 12, 2), 7, 5, 2, None, -0.5, 0.3, 5),
 ]
+TIME_INDEX = {"e_rect_time2": 2}      # the channel that holds time (default 0)
 
 
 def observations(rng, B, L, C, missing):
@@ -51,24 +56,32 @@ def observations(rng, B, L, C, missing):
     return np.ascontiguousarray(np.concatenate([t, v], axis=2), dtype=np.float32)
 
 
-def build_coeffs(x, path, initial):
+def build_coeffs(x, path, initial, time_index=0):
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         if path == "rectilinear":
-            return torchcde.linear_interpolation_coeffs(x.clone(), rectilinear=0, initial_value_if_nan=initial)
+            return torchcde.linear_interpolation_coeffs(x.clone(), rectilinear=time_index, initial_value_if_nan=initial)
         return torchcde.linear_interpolation_coeffs(x.clone(), initial_value_if_nan=initial, forward_fill=True)
 
 
-def main():
+def main(only=()):
     report = []
     for name, path, (C, H, HH, nl), B, L, n_out, static_dim, initial, missing, seed in CASES:
+        time_index = TIME_INDEX.get(name, 0)
         name = "g19_" + name
+        if only and name not in only:
+            continue
         rng = np.random.default_rng(1900 + seed)
         x = observations(rng, B, L, C, missing)
         if missing:
             x[0, 0, 1] = NAN              # a first row with a missing value, and a value channel observed late
             x[B - 1, :2, C - 1] = NAN
             assert np.isnan(x[:, 1:]).any()
+        if time_index:      # time moves into its channel; the value channels keep their order
+            order = list(range(1, C))
+            order.insert(time_index, 0)
+            x = np.ascontiguousarray(x[:, :, order])
+            assert not np.isnan(x[:, :, time_index]).any() and np.isnan(x[:, :, 0]).any()
         static = rng.standard_normal((B, static_dim)).astype(np.float32) if static_dim else None
         ctor = dict(input_dim=C, hidden_dim=H, output_dim=n_out, static_dim=static_dim, hidden_hidden_dim=HH, num_layers=nl,
                     interpolation=path, solver="rk4", return_sequences=True)
@@ -79,7 +92,7 @@ def main():
         for dtype in (torch.float32, torch.float64):
             xt = torch.from_numpy(x).to(dtype)
             st = None if static is None else torch.from_numpy(static).to(dtype)
-            coeffs = build_coeffs(xt, path, initial)
+            coeffs = build_coeffs(xt, path, initial, time_index)
             model = RefNeuralCDE(**ctor).to(dtype)
             model.load_state_dict({k: v.to(dtype) for k, v in sd.items()})
             hid = RefNeuralCDE(**dict(ctor, apply_final_linear=False, return_filtered_rectilinear=False)).to(dtype)
@@ -89,7 +102,7 @@ def main():
                 hidden = hid(coeffs if st is None else (st, coeffs))
                 causal, causal_h = 0.0, 0.0
                 for k in range(1, L):      # the same model on the sequence truncated at k: its last output is output row k
-                    ck = build_coeffs(xt[:, :k + 1], path, initial)
+                    ck = build_coeffs(xt[:, :k + 1], path, initial, time_index)
                     ok, hk = model(ck if st is None else (st, ck)), hid(ck if st is None else (st, ck))
                     causal = max(causal, float((ok[:, -1] - out[:, k]).abs().max()))
                     causal_h = max(causal_h, float((hk[:, -1] - hidden[:, 2 * k if path == "rectilinear" else k]).abs().max()))
@@ -115,7 +128,7 @@ def main():
         for k, v in sd.items():
             rec["sd_" + k] = v.numpy().copy()
         meta = {"name": name, "path": path, "ctor": ctor, "dims": {"B": B, "L": L, "T": T, "C": C, "H": H, "HH": HH, "nl": nl, "n_out": n_out},
-                "initial_value_if_nan": initial, "time_index": 0, "state_dict_keys": list(sd.keys()), "causal_diff_hidden": causal_h, "causal_diff_hidden_fp64": causal_h64,
+                "initial_value_if_nan": initial, "time_index": time_index, "state_dict_keys": list(sd.keys()), "causal_diff_hidden": causal_h, "causal_diff_hidden_fp64": causal_h64,
                 "causal_diff": causal, "causal_diff_fp64": causal64, "ref_drift": drift, "moved": moved, "n_nan": int(np.isnan(x).sum()),
                 "n_nan_first_row": int(np.isnan(x[:, 0]).sum())}
         print(f"{name:26s} nan {meta['n_nan']:3d} (first row {meta['n_nan_first_row']}) causal_diff {causal:g} moved {moved:.2e} ref_drift "
@@ -124,10 +137,16 @@ def main():
         np.savez_compressed(path_npz, meta=np.array(json.dumps(meta)), **rec)
         assert os.path.getsize(path_npz) < 1 << 20
         report.append(meta)
-    with open(os.path.join(GOLD, "MANIFEST_stream.json"), "w") as f:
+    manifest = os.path.join(GOLD, "MANIFEST_stream.json")
+    if only:      # keep the entries of the cases that were not regenerated, in their order
+        with open(manifest) as f:
+            old = json.load(f)
+        new = {m["name"]: m for m in report}
+        report = [new.pop(m["name"], m) for m in old] + list(new.values())
+    with open(manifest, "w") as f:
         json.dump(report, f, indent=1)
         f.write("\n")
 
 
 if __name__ == "__main__":
-    main()
+    main(tuple(sys.argv[1:]))
