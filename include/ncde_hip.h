@@ -76,6 +76,12 @@ typedef enum NcdeOutput { NCDE_OUT_INTERVAL = 0, NCDE_OUT_KNOTS = 1, NCDE_OUT_TI
 #define NCDE_FLAG_ADJOINT_SPLIT_FP16 128u /* development builds (-DNCDE_DEV_KNOBS) only, ignored otherwise: split-fp16 GEMMs on the cotangent
                                        side of the specialised adjoint too (not reproducible run to run) */
 #define NCDE_FLAG_DEBUG_PROFILE 0x100u /* development: instrumented kernel variant, cycle counters land in the workspace */
+#define NCDE_FLAG_DENSE_CHANNELS 0x300u /* BOTH bits 0x100 and 0x200 (0x200 alone is an internal development switch; no single bit of `flags` is
+                                          free): the register-resident adjoint (ncde_adj_fast3) runs every channel quad of the output layer on every stage.
+                                          Default: a stage whose dX is zero in all channels >= 4 for the whole 16-sample tile -- the
+                                          time-only pieces of a rectilinear path -- runs quad 0 only.  Same results up to the sign of a
+                                          zero; the in-process reference of tests/test_zero_quad_skip.py.  Test it with
+                                          (flags & NCDE_FLAG_DENSE_CHANNELS) == NCDE_FLAG_DENSE_CHANNELS; it is not NCDE_FLAG_DEBUG_PROFILE */
 #define NCDE_FLAG_NO_COOP 0x400u       /* batch-tiled forward and backward: do not use the XCD-cooperative, weight-stationary output phase (round 5, large
                                           hidden sizes: workgroups of one launch exchange activations through L2 and spin on each other --
                                           it needs every workgroup resident, i.e. the GPU's CUs not held by another process's persistent kernel) */

@@ -182,7 +182,7 @@ PadPlan make_pad_plan(const NcdeProblem* p, int pass, const PadTarget* t) {
         if (pass < 0 || pass > 2 || !t->passes[pass] || (p->output == NCDE_OUT_TIMES && !t->time_plan)) return P;
         if (p->field_kind != NCDE_FIELD_ORIGINAL || p->hidden > t->H || p->channels > t->C) return P;
         // (any batch-tiled knob is a request for that family; the non-default adjoint variants exist for the exact shapes only)
-        if (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | NCDE_FLAG_FORCE_TILED |
+        if (ncde_dev_flags(p->flags) & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE | NCDE_FLAG_FORCE_TILED |
                         NCDE_FLAG_TILED_NS1 | NCDE_FLAG_TILED_NS2 | NCDE_FLAG_TILED_NS4 | NCDE_FLAG_TILED_WINDOW_STEPS(0xFF) | kFlagChainDump)) return P;
         for (int l = 0; l < p->n_layers; ++l)
             if (p->layer_out[l] > t->HH) return P;
@@ -749,7 +749,7 @@ int ncde_forward_record(const NcdeProblem* p, float* out, float* stages, void* w
     Call c;
     int rc = begin_call(p, 0, &c, [&](const NcdeProblem& q) {
         if (!out || !stages) return fail(NCDE_ERR_INVALID, "out/stages is NULL");
-        if (q.flags & NCDE_FLAG_DEBUG_PROFILE) return fail(NCDE_ERR_UNSUPPORTED, "no instrumented recording forward");
+        if (ncde_dev_flags(q.flags) & NCDE_FLAG_DEBUG_PROFILE) return fail(NCDE_ERR_UNSUPPORTED, "no instrumented recording forward");
         return (int)NCDE_OK;
     });
     if (rc == NCDE_OK) rc = check_workspace(c, 0, workspace, workspace_bytes, false);

@@ -113,6 +113,8 @@ struct KArgs {
     int coop_inject;         // NCDE_FLAG_COOP_FAULT_INJECT: workgroup 1 skips its first arrival (tests the time-out path)
     // low-rank field (ncde_lowrank.hip): M = tanh(P Q), P = Wo hh + bo viewed [H, R] (rows = H * R), Q = Wg hh + bg viewed [R, C]
     int rank, rows_g;        // R and R * C
+    // ncde_adj_fast3: NCDE_FLAG_DENSE_CHANNELS -- every stage runs all channel quads (no time-only narrow stages)
+    int dense_channels;
 };
 
 // every kernel of the library that takes its arguments as one KArgs

@@ -99,7 +99,7 @@ int c_set(const NcdeProblem* p) {
     for (int l = 1; l < p->n_layers; ++l)
         if (p->layer_out[l] != 32 || p->layer_in[l] != 32) return 0;
     if (!ncde_one_shared_inner_layer(p)) return 0;
-    if (p->flags & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_ADJOINT_SPLIT_FP16 |
+    if (ncde_dev_flags(p->flags) & (NCDE_FLAG_FP32_MFMA | NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_ADJOINT_SPLIT_FP16 |
                     NCDE_FLAG_DEBUG_PROFILE | kFlagChainDump)) return 0;
     return p->channels;
 }
@@ -147,7 +147,7 @@ constexpr uint32_t kDevVariantFlags = NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V
 
 // forward: the few-channel sets, the PLAN = 1 instances (general time axis), else the entry's own
 void plan_forward(const NcdeProblem* p, const Layout& y, int cset, const FastEntry* e, FastPlan* P) {
-    const uint32_t f = p->flags;
+    const uint32_t f = ncde_dev_flags(p->flags);      // (NCDE_FLAG_DENSE_CHANNELS reaches the kernels through KArgs, not through the plan)
     const bool planned = p->output == NCDE_OUT_TIMES, fp32 = (f & NCDE_FLAG_FP32_MFMA) != 0, prof = (f & NCDE_FLAG_DEBUG_PROFILE) != 0;
     const int hp = fast_hp(f, 0, true), shape = cset ? shape_index(32, cset) : (e ? shape_index(e->H, e->C) : 0);
     auto pick = [&](int h) -> NcdeKernel {
@@ -180,7 +180,7 @@ void plan_forward(const NcdeProblem* p, const Layout& y, int cset, const FastEnt
 
 // adjoint / exact discrete backward of the (32, 32, C) sets (H = 64: ncde_fast64_plan)
 void plan_adjoint(const NcdeProblem* p, const Layout& y, int pass, int cset, const FastEntry* e, FastPlan* P) {
-    const uint32_t f = p->flags;
+    const uint32_t f = ncde_dev_flags(p->flags);      // (NCDE_FLAG_DENSE_CHANNELS reaches the kernels through KArgs, not through the plan)
     const bool disc = pass == 2, planned = p->output == NCDE_OUT_TIMES;
     const bool prof = (f & NCDE_FLAG_DEBUG_PROFILE) != 0, dump = (f & kFlagChainDump) != 0;
     const int interp = p->interp, method = p->method, nl = p->n_layers;

@@ -826,7 +826,7 @@ bool f64_supported(const NcdeProblem* p, int pass) {
     if (p->hidden != 64 || p->channels > 4 || p->n_layers < 1 || p->n_layers > kF64MaxLayers) return false;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL) return false;
     if (p->output == NCDE_OUT_TIMES && pass != 1) return false;      // general time axis: the continuous adjoint (PLAN instances)
-    if (p->flags & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE)) return false;
+    if (ncde_dev_flags(p->flags) & (NCDE_FLAG_ADJOINT_V1 | NCDE_FLAG_ADJOINT_V2 | NCDE_FLAG_ADJOINT_V4 | NCDE_FLAG_DEBUG_PROFILE)) return false;
     for (int l = 0; l < p->n_layers; ++l)
         if (p->layer_in[l] != 64 || p->layer_out[l] != 64) return false;
     if (!ncde_one_shared_inner_layer(p)) return false;

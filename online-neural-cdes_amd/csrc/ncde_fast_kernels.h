@@ -1812,6 +1812,14 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                                                                       // (HP = 2 has no lo-piece image: nobody reads one)
     float* amax = reinterpret_cast<float*>(w1S3 + 2 * HT * NPF * 256); // [NW] max |a| of each chain wave's state rows; [NW] = fault word
     int* fault_s = reinterpret_cast<int*>(amax + NW);
+    // SKIP ("narrow stages"): wideq[piece % 3] = "dX of some channel >= 4 is non-zero somewhere in this tile",
+    // one word per slot of the control-path ring, in the three spare words behind the fault word.  A stage whose word is 0 -- every
+    // time-only piece of a rectilinear path -- needs channel quad 0 of the output layer only.  Both roles read the word of the stage's
+    // piece; when it is 0 the chain wave computes and publishes block 0 only, and the gradient wave polls and consumes block 0 only --
+    // the other blocks' dP, Wo^T dP and dWo terms are exact zeros.  Linear pieces on the integer grid with more than one quad;
+    // everywhere else `wide` is a compile-time true and the code is what it was.
+    constexpr bool SKIP = INTERP == NCDE_INTERP_LINEAR && PLAN == 0 && CQ > 1;
+    int* wideq = fault_s + 1;
     float mx = 0.0f;              // largest operand magnitude the split-fp16 GEMMs have seen (ncde_bf3.h)
     float sig = 1.0f;
 
@@ -1831,6 +1839,9 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
 
     for (int e = tid; e < NW * NFLAG; e += 512) flags[e] = 0;
     if (tid == 0) *fault_s = 0;
+    if constexpr (SKIP) {      // all words start at 0, a barrier ahead of the first stage_store
+        if (tid < 3) wideq[tid] = 0;
+    }
     for (int e = tid; e < NW * NTILE * 16; e += 512) {
         const int r = e & 3, gg = (e >> 2) & 3, rest = e >> 4;
         const int t2 = rest % NTILE, wv = rest / NTILE;
@@ -1869,6 +1880,7 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
         SO::store(w0T3 + wv * NP * 256, l, SO::split(tmp, mx));
     }
 
+    if constexpr (SKIP) __syncthreads();
     if (is_chain) {
         // =================================================================================================
         // chain wave
@@ -1925,11 +1937,17 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
         };
         auto stage_store = [&](int piece) {
             float* dst = dxs + (piece % 3) * 16 * DXW;
+            bool nz = false;
 #pragma unroll
             for (int q = 0; q < EPT; ++q) {
                 const int e = tid + q * NT;
-                if (e < 16 * DXW) dst[e] = INTERP == NCDE_INTERP_LINEAR ? eprev[q] - enext[q] : enext[q];
+                const float v = INTERP == NCDE_INTERP_LINEAR ? eprev[q] - enext[q] : enext[q];
+                if (e < 16 * DXW) dst[e] = v;
+                if constexpr (SKIP) nz = nz || (e < 16 * DXW && e % DXW >= 4 && v != 0.0f);      // -0 is zero; a NaN keeps the stage wide
                 eprev[q] = enext[q];
+            }
+            if constexpr (SKIP) {
+                if (nz) wideq[piece % 3] = 1;      // (every writer stores the same value; cleared in the step loop)
             }
         };
         constexpr int EPQ = PLAN ? (S * 16 * CP + NT - 1) / NT : 1;
@@ -2038,6 +2056,15 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
             } else {
                 if (n - 3 >= 0) stage_load(n - 3);
             }
+            if constexpr (SKIP) {
+                // Clear the word that stage_store(n - 3) of this step will set.  The ring is walked downwards: reverse step n reads
+                // pieces n - 1 and n - 2 only (piece_index of t in [n - 1, n]), so word (n - 3) % 3 = n % 3 is nobody's in this step
+                // until that store.  Its previous owner is piece n, read last in step n + 1 -- by both roles BEFORE barrier A of the
+                // stage (the chain wave's dxp loads and everybody's `wide` sit ahead of it) -- so that stage's barriers A and B lie
+                // between the last read and this clear, for S = 1 too.  The store runs in the last stage of this step behind ITS
+                // barrier A, which every stage has: clear | barrier A | store | barrier B | first read (step n - 1).
+                if (tid == 0 && n - 3 >= 0) wideq[(n - 3) % 3] = 0;
+            }
 #pragma unroll 1
             for (int j = 0; j < S; ++j) {
                 ++sc;
@@ -2045,6 +2072,10 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                 const float t = DISC != 0 ? (float)(n - 1) + stage_offset(METHOD, S - 1 - j) : -(-(float)n + stage_offset(METHOD, j));
                 const int idx = PLAN ? 0 : piece_index(t, a.n_pieces);
                 const float frac = t - (float)idx;
+                // workgroup-uniform: one LDS word, set before the barrier that published the piece (NCDE_FLAG_DENSE_CHANNELS: always
+                // wide); the gradient waves read the same word for the same stage
+                bool wide = true;
+                if constexpr (SKIP) wide = (__builtin_amdgcn_readfirstlane(wideq[idx % 3]) | a.dense_channels) != 0;
                 const float wq = DISC != 0 ? 1.0f : stage_weight(METHOD, j);
                 if constexpr (DISC != 0) {
                     const int lin = (n - 1) * S + (S - 1 - j);
@@ -2108,7 +2139,7 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                 // mask each (a scalar register pair, ncde_fastdefs.h) instead of 8 NL registers carried across the output tiles
                 // (round 4 packed them into one bit each of a VGPR to shed the kernel's last 32 B / lane of scratch; the lane masks
                 // take no VGPR at all and cost one compare to build and one select to apply).  A lane mask is a WAVE-wide value:
-                // every branch between here and the gates below (wq, pw, j, the role split) is wave-uniform and all 64 lanes are
+                // every branch between here and the gates below (wq, pw, j, `wide`, the role split) is wave-uniform and all 64 lanes are
                 // active (invalid samples of a tail tile compute on zeros).  A lane-divergent branch around either end would break it.
                 LaneMask relu_on[NL][8];
 #pragma unroll
@@ -2122,6 +2153,9 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                 for (int nb = 0; nb < NB; ++nb) kout[nb] = 0.0f;
 #pragma unroll
                 for (int cq = 0; cq < CQ; ++cq) {
+                    // narrow stage: dX of these quads is 0 for the whole tile -- no tiles, no kout / sdx terms, no dP, and no flag:
+                    // the gradient wave reads the same word and polls block 0 only
+                    if (SKIP && cq >= 1 && !wide) continue;
                     f32x4 o[NB];
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
@@ -2546,6 +2580,12 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                 ++sc;
                 const int par = sc & 1;
                 const float wq = DISC != 0 ? 1.0f : stage_weight(METHOD, j) * dtw;
+                // the chain wave's `wide` of this stage: same piece, same word, read between the same two barriers
+                bool wide = true;
+                if constexpr (SKIP) {
+                    const float t = DISC != 0 ? (float)(n - 1) + stage_offset(METHOD, S - 1 - j) : -(-(float)n + stage_offset(METHOD, j));
+                    wide = (__builtin_amdgcn_readfirstlane(wideq[piece_index(t, a.n_pieces) % 3]) | a.dense_channels) != 0;
+                }
                 // hidden-layer dW/db of the previous stage, under the chain wave's forward recompute
                 if (NDP == 1 && wprev != 0.0f) dw_hidden(par ^ 1, wprev);
                 NCDE_TICK(0)
@@ -2559,6 +2599,7 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                 bool have_bs = false;
 #pragma unroll
                 for (int blk = 0; blk < NBLK; ++blk) {
+                    if (SKIP && blk >= 1 && !wide) continue;      // narrow stage: not published, never polled; dP = 0
                     NCDE_TICK(2)
                     wait_flag(2 * blk + 1, sc);
                     NCDE_TICK(1)
@@ -2598,8 +2639,8 @@ __global__ __launch_bounds__(512, 2) void ncde_adj_fast3(KArgs a) {
                         Bs = x3_split(par, wq);
                     }
 #pragma unroll
-                    for (int blk = 0; blk < NBLK; ++blk)
-                        if (blk >= 1 || DWO0_LATE) dwo_block(Bs, wq, blk);
+                    for (int blk = 0; blk < NBLK; ++blk)      // (narrow stage: block 0 alone, here also where it is otherwise slotted in early)
+                        if (blk >= 1 ? wide : (DWO0_LATE || !wide)) dwo_block(Bs, wq, blk);
 
                 }
                 __syncthreads();  // barrier B

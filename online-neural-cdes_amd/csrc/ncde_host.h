@@ -28,6 +28,10 @@ int ncde_fail_text(int code, const char* text);
 // cubic + midpoint only) also write the per-stage chain values of workgroup 0 to the tail of the workspace, and every split-GEMM
 // choice of that set falls back to split-bf16.  A problem that carries it is never zero-padded onto a kernel set.
 constexpr uint32_t kFlagChainDump = 0x200u;
+// NCDE_FLAG_DENSE_CHANNELS is BOTH development bits (0x100 | 0x200: no bit of `flags` was free, and an instrumented chain dump never
+// existed).  ncde_dev_flags: the flags with that request taken out -- what every test of a development bit looks at.
+inline bool ncde_dense_channels(uint32_t flags) { return (flags & NCDE_FLAG_DENSE_CHANNELS) == NCDE_FLAG_DENSE_CHANNELS; }
+inline uint32_t ncde_dev_flags(uint32_t flags) { return ncde_dense_channels(flags) ? flags & ~NCDE_FLAG_DENSE_CHANNELS : flags; }
 
 // Development switches are environment variables ONLY in builds with -DNCDE_DEV_KNOBS; the shipped library is stateless and
 // reads nothing but its arguments.
@@ -160,6 +164,7 @@ inline void fill_kargs(const NcdeProblem* p, const Layout& y, KArgs* a) {
     a->gWg_off = y.gWg_off; a->gbg_off = y.gbg_off; a->gWr_off = y.gWr_off; a->gbr_off = y.gbr_off;
     a->gacc_in_lds = y.gacc_in_lds;
     a->rank = y.rank; a->rows_g = y.rows_g;
+    a->dense_channels = ncde_dense_channels(p->flags);
     // internal (zero-padded problems, see KArgs): reserved_ = (real hidden size << 12) | real channel count, 0 = not padded
     a->Hr = p->reserved_ ? (p->reserved_ >> 12) : p->hidden;
     a->Cc = p->reserved_ ? (p->reserved_ & 0xFFF) : p->channels;

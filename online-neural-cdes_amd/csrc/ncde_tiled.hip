@@ -3231,7 +3231,7 @@ void coop_mark_in_flight(hipStream_t st) {      // after the last cooperative la
 // workgroup resident at once (one per CU).
 CoopPlan tiled_coop_plan(const NcdeProblem* p) {
     CoopPlan c{};
-    if (p->flags & (NCDE_FLAG_NO_COOP | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_DEBUG_PROFILE)) return c;
+    if (ncde_dev_flags(p->flags) & (NCDE_FLAG_NO_COOP | NCDE_FLAG_FP32_MFMA | NCDE_FLAG_DEBUG_PROFILE)) return c;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL || p->n_layers < 1) return c;      // (any time axis: round 6)
     if (p->interp == NCDE_INTERP_QUINTIC) return c;      // piecewise-quintic controls: the per-workgroup kernels only
     if (p->layer_out[p->n_layers - 1] != 128 || p->hidden > 128 || p->hidden % 16 || p->channels % 4) return c;

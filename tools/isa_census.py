@@ -25,6 +25,9 @@ cycles per instruction -- not the maximum of the two pipes.
 `issue_ceiling_ms`: a wave issues at most one instruction per 4-cycle slot (MI355X_MICROARCH.md: "32 cyc/SIMD ~ 8 issue slots of ~4
 cyc"), so its own stream -- every class, waits and nops included -- takes instructions x 4 cycles at least; for kernels whose waves
 play different roles the longest role counts.  With ONE wave per SIMD (the register-resident kernels) this, not a pipe, is the floor.
+Branches inside a stage are not modelled: every instruction of a loop body counts on every trip.  For ncde_adj_fast3 that prices the
+narrow (time-only) stages of a rectilinear path as wide ones -- the cfg2.backward ceilings are those of the all-wide stream, an upper
+bound of what the kernel issues on such a path (DESIGN.md section 6 has the measured split).
 """
 import argparse
 import json
