@@ -388,6 +388,18 @@ int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C,
  * NULL for arguments the builders refuse.  The string lives in thread-local storage until the next call. */
 const char* ncde_prepare_kernel_name(int kind, int B, int L, int C, int has_grid, int rectilinear_time_index);
 
+/* Hermite cubic with backward differences (upstream torchcde's hermite_cubic_coefficients_with_backward_differences): a smooth path
+ * whose piece on [t_i, t_i+1] reads knots i-1, i, i+1 only.  knots [B, L, C]: the LINEAR knots (ncde_prepare_linear_grid's output:
+ * no NaN left; built with both causal options, knot k sees x[:k+1] only).  t: DEVICE pointer to L strictly increasing fp32 times,
+ * NULL = the integer grid (h = 1).  out [B, L-1, 4C] = a|b|2c|3d, an NCDE_INTERP_CUBIC tensor.  Per piece i and channel, in fp32 and
+ * in this operation order, with h = t[i+1] - t[i], d_i = (knots[i+1] - knots[i]) / h and dprev = d_{i-1} (d_0 for i = 0):
+ *   a = knots[i];  b = dprev;  2c = 2 * (3 * ((knots[i+1] - knots[i]) / h - b) - d_i + dprev) / h;  3d = (1 / h^2) * (d_i - b) - 2c / h
+ * The first piece is linear: its 2c and 3d are exactly zero.  One launch on `stream`, one thread per (piece, channel) looping over the
+ * four parts, every element of `out` written; no workspace, no atomics, bit-reproducible.  Bad arguments NCDE_ERR_INVALID.
+ * ncde_prepare_hermite_kernel_name: "ncde_hermite_coeffs", or NULL for arguments the builder refuses. */
+int ncde_prepare_hermite(const float* knots, const float* t, int B, int L, int C, float* out, void* stream);
+const char* ncde_prepare_hermite_kernel_name(int B, int L, int C);
+
 
 /* Smoothed-linear control paths (SmoothLinearInterpolation, src/ncde/interpolation.py:6-123: cubic / quintic matching of the
  * slopes in (k, k + eps) after every interior knot k of the integer grid) as a piecewise polynomial on the REFINED knot grid
@@ -489,6 +501,20 @@ typedef struct NcdeStream {
 int64_t ncde_stream_workspace_bytes(const NcdeProblem* p);   /* < 0: status code */
 const char* ncde_stream_kernel_name(const NcdeProblem* p);   /* NULL on error */
 int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream);
+
+/* The same step on the Hermite cubic with backward differences (ncde_prepare_hermite on the integer grid, built with
+ * initial_value_if_nan = v and forward_fill): the one cubic that is causal.  Same structs, same state; prev_dx holds the backward
+ * difference of the last piece.  Per new row of a stream with count >= 1, elementwise per channel and in this operation order:
+ *   dn = fill - last_row;  b = count == 1 ? dn : prev_dx;  two_c = 2 * (3 * (dn - b) - dn + b);  three_d = (dn - b) - two_c
+ *   stage 1 sits on the knot and reads the piece to its left at frac = 1, which in exact arithmetic is b: the step reads b
+ *   stage j > 1 reads b + (two_c + three_d * s_j) * s_j, s_j the stage's offset in the piece (the cubic branch of the batch kernels)
+ *   then prev_dx = dn, last_row = fill, count += 1.  A stream's first row initialises it, as for ncde_stream_step.
+ * The problem must say interp = NCDE_INTERP_CUBIC (the layout of the path's coefficients) and s->rectilinear must be 0.  The LDS
+ * plan is that of ncde_stream_step (dn, b and ONE stage image rebuilt per stage take its three dX/dt slots), so the two queries
+ * accept the same shapes; everything else stated for ncde_stream_step holds.  The kernel name is "ncde_stream_step_hermite". */
+int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p);   /* < 0: status code */
+const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream);
 
 #ifdef __cplusplus
 }

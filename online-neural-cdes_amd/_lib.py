@@ -143,7 +143,7 @@ EXPORTS = (
     "ncde_version", "ncde_last_error_string", "ncde_num_outputs", "ncde_workspace_bytes",
     "ncde_kernel_name", "ncde_forward", "ncde_adjoint", "ncde_time_kernel",
     "ncde_prepare_workspace_bytes", "ncde_prepare_linear", "ncde_prepare_cubic", "ncde_prepare_linear_grid", "ncde_prepare_cubic_grid",
-    "ncde_prepare_kernel_name",
+    "ncde_prepare_kernel_name", "ncde_prepare_hermite", "ncde_prepare_hermite_kernel_name",
     "ncde_smooth_pieces", "ncde_prepare_smooth", "ncde_prepare_smooth_backward",
     "ncde_prepare_fill", "ncde_prepare_hybrid_workspace_bytes", "ncde_prepare_hybrid_count", "ncde_prepare_hybrid_write",
     "ncde_stage_record_bytes", "ncde_forward_record", "ncde_backward",
@@ -152,6 +152,7 @@ EXPORTS = (
     "ncde_coop_status_offset",
     "ncde_control_workspace_bytes", "ncde_control_kernel_name", "ncde_backward_control",
     "ncde_stream_workspace_bytes", "ncde_stream_kernel_name", "ncde_stream_step",
+    "ncde_stream_hermite_workspace_bytes", "ncde_stream_hermite_kernel_name", "ncde_stream_step_hermite",
 )
 
 _LIB = None
@@ -225,6 +226,12 @@ def lib():
     h.ncde_stream_kernel_name.restype = ctypes.c_char_p
     h.ncde_stream_step.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
     h.ncde_stream_step.restype = ctypes.c_int
+    h.ncde_stream_hermite_workspace_bytes.argtypes = [P]
+    h.ncde_stream_hermite_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_stream_hermite_kernel_name.argtypes = [P]
+    h.ncde_stream_hermite_kernel_name.restype = ctypes.c_char_p
+    h.ncde_stream_step_hermite.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
+    h.ncde_stream_step_hermite.restype = ctypes.c_int
     i32 = ctypes.c_int
     h.ncde_prepare_workspace_bytes.argtypes = [i32, i32, i32, i32]
     h.ncde_prepare_workspace_bytes.restype = ctypes.c_int64
@@ -244,6 +251,10 @@ def lib():
     h.ncde_prepare_cubic_grid.restype = ctypes.c_int
     h.ncde_prepare_kernel_name.argtypes = [i32, i32, i32, i32, i32, i32]
     h.ncde_prepare_kernel_name.restype = ctypes.c_char_p
+    h.ncde_prepare_hermite.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    h.ncde_prepare_hermite.restype = ctypes.c_int
+    h.ncde_prepare_hermite_kernel_name.argtypes = [i32, i32, i32]
+    h.ncde_prepare_hermite_kernel_name.restype = ctypes.c_char_p
     h.ncde_prepare_fill.argtypes = [vp, i32, i32, i32, i32, ctypes.c_double, i32, vp, vp]
     h.ncde_prepare_fill.restype = ctypes.c_int
     h.ncde_prepare_hybrid_workspace_bytes.argtypes = [i32, i32, i32]

@@ -1,8 +1,8 @@
 """GPU construction of control-path coefficients: mirrors of ``torchcde.linear_interpolation_coeffs`` and
 ``torchcde.natural_cubic_coeffs`` (/root/reference/modules/torchcde/torchcde/interpolation_linear.py:131-180,
-interpolation_cubic.py:170-190) for fp32 CUDA tensors, on the default integer time grid or a user grid ``t``, and of the causal
-builders of online prediction (the fill options, ``forward_fill``, the linear / rectilinear hybrid scheme), backed by the
-HIP kernels in csrc/ncde_prepare.hip.  (Host/numpy mirrors used to build test inputs live in data.py.)"""
+interpolation_cubic.py:170-190) for fp32 CUDA tensors, on the default integer time grid or a user grid ``t``, of the causal
+builders of online prediction (the fill options, ``forward_fill``, the linear / rectilinear hybrid scheme) and of upstream
+torchcde's ``hermite_cubic_coefficients_with_backward_differences``, backed by the HIP kernels in csrc/ncde_prepare.hip.  (Host/numpy mirrors used to build test inputs live in data.py.)"""
 import ctypes
 
 import torch
@@ -180,3 +180,22 @@ def natural_cubic_coeffs(x, t=None):
 
 
 natural_cubic_spline_coeffs = natural_cubic_coeffs
+
+
+def hermite_cubic_coefficients_with_backward_differences(x, t=None, initial_value_if_nan=None, forward_fill=False):
+    """a | b | 2c | 3d of the Hermite cubic with backward differences (upstream torchcde's function of this name): the piece on
+    [t_i, t_i+1] goes from knot i to knot i+1, starts with the slope of the linear piece before it (its own for i = 0, so the first
+    piece is linear) and ends with its own.  The knots are ``linear_interpolation_coeffs(x, t, None, initial_value_if_nan,
+    forward_fill)``; with both causal options piece i depends on x[..., :i+2, :] only -- the smooth path that can be stepped online
+    (``NeuralCDE(interpolation="cubic_hermite").online``).  include/ncde_hip.h states the formulas (ncde_prepare_hermite).
+    [..., L, C] fp32 CUDA -> [..., L-1, 4C], read by ``CubicSpline`` / ``NaturalCubicSpline``.  ``x`` is never modified."""
+    knots = linear_interpolation_coeffs(x, t=t, initial_value_if_nan=initial_value_if_nan, forward_fill=forward_fill)      # (validates x and t)
+    k3 = knots.reshape(-1, x.size(-2), x.size(-1))
+    B, L, C = k3.shape
+    tg = _grid(t, L, x.device)
+    out = torch.empty(B, L - 1, 4 * C, dtype=torch.float32, device=x.device)
+    if out.numel():
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().ncde_prepare_hermite(k3.data_ptr(), None if tg is None else tg.data_ptr(), B, L, C, out.data_ptr(), _stream())
+        _lib.check(rc, "ncde_prepare_hermite")
+    return out.reshape(*x.shape[:-2], L - 1, 4 * C)

@@ -724,6 +724,31 @@ __global__ __launch_bounds__(256) void ncde_smooth_coeffs_bwd_kernel(const float
     }
 }
 
+// Hermite cubic with backward differences (include/ncde_hip.h states the formulas, which are the contract: fp32, this operation order,
+// no contraction).  One thread per (sample, piece, channel), channels fastest: the three knot loads and the four stores of a wave are
+// contiguous runs.  Piece i reads knots i-1, i, i+1 only; piece 0 takes its own slope for the one before it and comes out linear.
+__global__ __launch_bounds__(256) void ncde_hermite_coeffs_kernel(const float* __restrict__ knots, const float* __restrict__ t, int B, int L, int C,
+                                                                  float* __restrict__ out) {
+    const int P = L - 1;
+    const long long total = (long long)B * P * C;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const int c = (int)(e % C), i = (int)((e / C) % P), b = (int)(e / ((long long)C * P));
+        const float* kr = knots + ((long long)b * L + i) * C + c;
+        const float xk = kr[0], xn = kr[C];
+        const float h = t ? t[i + 1] - t[i] : 1.0f;
+        const float d = (xn - xk) / h;
+        float dprev = d;
+        if (i > 0) dprev = (xk - kr[-C]) / (t ? t[i] - t[i - 1] : 1.0f);
+        const float two_c = 2.0f * (3.0f * ((xn - xk) / h - dprev) - d + dprev) / h;
+        const float three_d = (1.0f / (h * h)) * (d - dprev) - two_c / h;
+        float* o = out + ((long long)b * P + i) * (4 * C) + c;
+        o[0] = xk;
+        o[C] = dprev;
+        o[2 * C] = two_c;
+        o[3 * C] = three_d;
+    }
+}
+
 // ---- causal control paths (interpolation_linear.py:159-173, misc.py:103-126, src/ncde/interpolation.py:191-253) ----------------------
 // Everything below copies values and compares them; nothing is computed, so the results carry the bits of the input.
 
@@ -1028,6 +1053,19 @@ int ncde_prepare_cubic_grid(const float* x, const float* t, int B, int L, int C,
 
 int ncde_prepare_cubic(const float* x, int B, int L, int C, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     return ncde_prepare_cubic_grid(x, nullptr, B, L, C, out, workspace, workspace_bytes, stream);
+}
+
+// ---- Hermite cubic with backward differences: one elementwise launch, the same for every shape ---------------------------------------
+static bool hermite_shape_ok(int B, int L, int C) { return B >= 1 && L >= 2 && C >= 1 && 4LL * C <= 0x7fffffffLL; }      // (a row of 4C is indexed with int)
+
+const char* ncde_prepare_hermite_kernel_name(int B, int L, int C) { return hermite_shape_ok(B, L, C) ? "ncde_hermite_coeffs" : nullptr; }
+
+int ncde_prepare_hermite(const float* knots, const float* t, int B, int L, int C, float* out, void* stream) {
+    if (!knots || !out || knots == out || !hermite_shape_ok(B, L, C)) return NCDE_ERR_INVALID;
+    const long long total = (long long)B * (L - 1) * C;
+    const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(ncde_hermite_coeffs_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, knots, t, B, L, C, out);
+    return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
 // ---- causal control paths: fills and the linear / rectilinear hybrid scheme -----------------------------------------------------

@@ -10,6 +10,13 @@
 // Which derivative a stage reads is the reference's left-piece rule (interpolation_linear.py:212-219: bucketize(right=False) - 1):
 // stage 1 of a step sits ON a knot and reads the piece to its left -- the previous piece, or its own at the very first step of a
 // stream -- every later stage reads the step's own piece.  The clamp is per stream, from the stream's own count.
+//
+// The Hermite cubic with backward differences (ncde_stream_step_hermite, the HERMITE instantiation of the same body) is the one cubic
+// with that property: its piece reads the new row, the last row and the previous piece's slope.  The row is filled and differenced
+// exactly as on the linear path (DXA = dn, DXL = b: per stream the previous dn, or its own at the first step); stage 1 reads b -- the
+// left piece's end slope at frac = 1 in exact arithmetic --, every later stage the image b + (2c + 3d s) s, rebuilt into the DXB slot
+// (free: no rectilinear form) by the combine phase of the stage before it, under that phase's barrier.  s is per stream: the frac
+// default_stage hands load_dx at the stream's own step index, (n + offset) - n in fp32.
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -34,7 +41,8 @@ struct StreamArgs {
     float* z_out;
 };
 
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) {
+template <bool HERMITE>
+__device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * NCDE_TILE;
@@ -51,10 +59,10 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kerne
     float* KO = K2 + HS;
     float* DXL = KO + HS;        // stage 1 of the first piece: the piece to the left (per stream: the previous one, or its own)
     float* DXA = DXL + CS;       // first piece
-    float* DXB = DXA + CS;       // second piece (rectilinear)
+    float* DXB = DXA + CS;       // second piece (rectilinear); HERMITE: the stage image
     float* LAST = DXB + CS;      // last filled row
     float* PDX = LAST + CS;      // dX/dt of the last piece taken
-    int* CNT = (int*)(PDX + CS); // observations received; then: steps at this row, received a row in this launch
+    int* CNT = (int*)(PDX + CS); // observations received; then: steps at this row (0: no; else the step's index + 1), received a row in this launch
     int* STEP = CNT + 16;
     int* EVER = STEP + 16;
     const int total = 5 * HS + 2 * DS + 5 * CS + 48;
@@ -107,7 +115,7 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kerne
         if (tid < 16) {
             const int b = b0 + tid;
             const int act = b < a.B && (!q.active || q.active[(long long)r * a.B + b]);
-            STEP[tid] = act && CNT[tid] > 0;      // the first row of a stream initialises it: no solver step
+            STEP[tid] = act ? CNT[tid] : 0;       // the first row of a stream (count 0) initialises it: no solver step
             CNT[tid] += act;
             EVER[tid] |= act;
         }
@@ -118,7 +126,7 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kerne
         // 4. the Butcher stages, one step per piece
         if (any_step) {
             for (int pc = 0; pc < n_pieces; ++pc) {
-                const float* dx_own = pc == 0 ? DXA : DXB;
+                const float* dx_own = (HERMITE || pc != 0) ? DXB : DXA;
                 const float* dx_left = pc == 0 ? DXL : DXA;
                 for (int j = 0; j < S; ++j) {
                     gen_stage_forward(a, YS, ACT0, ACT1, j == 0 ? dx_left : dx_own, KO, Hp, Cp, tid);
@@ -131,6 +139,18 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kerne
                         K1[e] = k1;
                         K2[e] = k2;
                         if (last) Y0[e] = y0;
+                    }
+                    if constexpr (HERMITE) {
+                        if (j + 1 < S) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
+                            for (int e = tid; e < CS; e += GEN_THREADS) {
+                                const float frac = default_stage(a.method, (float)(STEP[e & 15] - 1) + stage_offset(a.method, j + 1), 0x7fffffff).frac;
+                                const float bb = DXL[e], dn = DXA[e];
+                                const float two_c = 2.0f * (3.0f * (dn - bb) - dn + bb);
+                                const float three_d = (dn - bb) - two_c;
+                                const float inner = two_c + three_d * frac;
+                                DXB[e] = bb + inner * frac;
+                            }
+                        }
                     }
                     __syncthreads();
                 }
@@ -171,6 +191,9 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kerne
     if (tid < 16 && b0 + tid < a.B && EVER[tid]) q.count[b0 + tid] = CNT[tid];
 }
 
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) { stream_step_body<false>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hermite_kernel(KArgs a, StreamArgs q) { stream_step_body<true>(a, q); }
+
 namespace {
 
 int sfail(int code, const char* fmt, ...) {
@@ -184,7 +207,8 @@ int sfail(int code, const char* fmt, ...) {
 
 // The problem as the stream step reads it: batch, channels, hidden, method, flags and the field.  coeffs, z0, n_knots, output and the
 // time plan are NOT read (the rows arrive through NcdeStream, the state lives in its buffers).
-int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
+// hermite: the Hermite step's problem says interp = NCDE_INTERP_CUBIC; the LDS plan is the same (the stage image takes the DXB slot).
+int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
     if (!in) return sfail(NCDE_ERR_INVALID, "problem is NULL");
     if (in->abi_version < 1 || in->abi_version > NCDE_ABI_VERSION)
         return sfail(NCDE_ERR_INVALID, "abi_version %d not in [1, %d]", in->abi_version, NCDE_ABI_VERSION);
@@ -195,7 +219,9 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
     p->time_plan = nullptr;
     p->output = NCDE_OUT_KNOTS;
     if (p->batch < 1 || p->channels < 1 || p->hidden < 1) return sfail(NCDE_ERR_INVALID, "batch/channels/hidden must be >= 1");
-    if (p->interp != NCDE_INTERP_LINEAR)
+    if (hermite && p->interp != NCDE_INTERP_CUBIC)
+        return sfail(NCDE_ERR_INVALID, "online Hermite step: the path's coefficients are a|b|2c|3d, interp must be NCDE_INTERP_CUBIC (interp %d)", p->interp);
+    if (!hermite && p->interp != NCDE_INTERP_LINEAR)
         return sfail(NCDE_ERR_INVALID, "online step: only a linear or rectilinear path is causal (interp %d)", p->interp);
     if (p->method != NCDE_EULER && p->method != NCDE_MIDPOINT && p->method != NCDE_RK4_38)
         return sfail(NCDE_ERR_INVALID, "Invalid method %d. Must be one of {euler, midpoint, rk4}", p->method);
@@ -238,11 +264,11 @@ extern "C" const char* ncde_stream_kernel_name(const NcdeProblem* p) {
     return stream_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step" : nullptr;
 }
 
-extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) {
+static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, bool hermite) {
     NcdeProblem q;
     Layout y;
     size_t lds;
-    const int rc = stream_problem(p, &q, &y, &lds);
+    const int rc = stream_problem(p, &q, &y, &lds, hermite);
     if (rc != NCDE_OK) return rc;
     if (!s) return sfail(NCDE_ERR_INVALID, "stream is NULL");
     if (s->n_rows < 1) return sfail(NCDE_ERR_INVALID, "n_rows %d: at least one new row", s->n_rows);
@@ -250,6 +276,7 @@ extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void*
     if (s->x_stride_b < q.channels || s->x_stride_m < 0) return sfail(NCDE_ERR_INVALID, "x strides (%lld, %lld): rows of %d channels", (long long)s->x_stride_m, (long long)s->x_stride_b, q.channels);
     if (s->rectilinear && (s->time_index < 0 || s->time_index >= q.channels))
         return sfail(NCDE_ERR_INVALID, "Time index must be in [0, %d], was given %d.", q.channels - 1, s->time_index);
+    if (hermite && s->rectilinear) return sfail(NCDE_ERR_INVALID, "online Hermite step: rectilinear must be 0 (the scheme has no rectilinear form)");
     if (s->Wf ? (s->n_out < 1 || !s->out) : !s->z_out) return sfail(NCDE_ERR_INVALID, "readout: Wf needs n_out >= 1 and out; without Wf pass z_out");
     KArgs a;
     fill_kargs(&q, y, &a);
@@ -259,9 +286,29 @@ extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void*
     k.active = s->active; k.init = s->initial_value_if_nan;
     k.z = s->z; k.last = s->last_row; k.pdx = s->prev_dx; k.count = s->count;
     k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
-    if (ncde_lds_optin((const void*)ncde_stream_step_kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
-    hipLaunchKernelGGL(ncde_stream_step_kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
+    void (*kernel)(KArgs, StreamArgs) = hermite ? ncde_stream_step_hermite_kernel : ncde_stream_step_kernel;
+    if (ncde_lds_optin((const void*)kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
+    hipLaunchKernelGGL(kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "ncde_stream_step launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "%s launch failed: %s", hermite ? "ncde_stream_step_hermite" : "ncde_stream_step", hipGetErrorString(e));
     return NCDE_OK;
 }
+
+extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, false); }
+
+extern "C" int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    const int rc = stream_problem(p, &q, &y, &lds, true);
+    return rc == NCDE_OK ? 0 : rc;
+}
+
+extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    return stream_problem(p, &q, &y, &lds, true) == NCDE_OK ? "ncde_stream_step_hermite" : nullptr;
+}
+
+extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, true); }

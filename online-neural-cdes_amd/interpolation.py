@@ -162,6 +162,9 @@ class NaturalCubicSpline(_ControlBase):
         return b + (two_c + three_d * frac) * frac
 
 
+CubicSpline = NaturalCubicSpline      # upstream torchcde's name for the evaluator of any a | b | 2c | 3d tensor (natural or Hermite)
+
+
 class SmoothLinearInterpolation(_ControlBase):
     """Piecewise linear path whose corners are rounded off: in ``(k, k + eps)`` after every interior knot ``k`` of the integer grid
     a cubic (``match_second_derivatives=False``) or quintic (``True``) polynomial takes the path from the slope of the piece before

@@ -16,6 +16,7 @@ from .vector_fields import GRUGatedVectorField, LowRankVectorField, MinimalGated
 
 SPLINES = {
     "cubic": NaturalCubicSpline,
+    "cubic_hermite": NaturalCubicSpline,      # hermite_cubic_coefficients_with_backward_differences: the same a | b | 2c | 3d tensor
     "linear": LinearInterpolation,
     "rectilinear": LinearInterpolation,
 }
@@ -107,7 +108,7 @@ class NeuralCDE(nn.Module):
     def online(self, batch_size, *, initial_value_if_nan=0.0, time_index=0):
         """A handle that carries the state of ``batch_size`` streams from one observation to the next (online.py): ``step(x_new)``
         answers what ``return_sequences=True`` on the whole prefix gives at the newest knot.  Over this module's own parameters
-        (no copies); interpolation 'linear' or 'rectilinear' only."""
+        (no copies); interpolation 'linear', 'rectilinear' or 'cubic_hermite' (the causal paths) only."""
         from .online import OnlineNeuralCDE
         return OnlineNeuralCDE(self, batch_size, initial_value_if_nan=initial_value_if_nan, time_index=time_index)
 

@@ -1,10 +1,15 @@
 """Online inference: carry the CDE state of a batch of streams from one observation to the next.
 
 ``NeuralCDE.online(batch_size)`` returns an ``OnlineNeuralCDE`` over the module's own parameters.  ``step(x_new)`` fills the new
-observation row(s) causally, appends the one (linear) or two (rectilinear) pieces they add to the control path, takes one solver
-step per piece and returns the readout -- what ``NeuralCDE(return_sequences=True)`` on the whole prefix gives at the same knot, at
-the cost of the new pieces only.  On the GPU (fp32, original field, matmul input) a call is ONE launch of ``ncde_stream_step``
-(csrc/ncde_stream.hip); anything else takes the torch-op step below behind the once-only "unfused" warning.
+observation row(s) causally, appends the one (linear, Hermite cubic) or two (rectilinear) pieces they add to the control path, takes
+one solver step per piece and returns the readout -- what ``NeuralCDE(return_sequences=True)`` on the whole prefix gives at the same
+knot, at the cost of the new pieces only.  On the GPU (fp32, original field, matmul input) a call is ONE launch of
+``ncde_stream_step`` / ``ncde_stream_step_hermite`` (csrc/ncde_stream.hip); anything else takes the torch-op step below behind the
+once-only "unfused" warning.
+
+``interpolation="cubic_hermite"`` is the smooth path that is causal: the Hermite cubic with backward differences
+(``hermite_cubic_coefficients_with_backward_differences(x, initial_value_if_nan=v, forward_fill=True)``), whose piece reads the new
+row, the last row and the previous piece's slope -- the state below, unchanged.
 
 State per stream: ``z`` [B, H], ``last_row`` [B, C] (the last filled row), ``prev_dx`` [B, C] (dX/dt of the last piece: stage 1 of
 the next step reads it, the reference's left-piece rule, interpolation_linear.py:212-219) and ``count`` [B] (observations received).
@@ -36,7 +41,7 @@ def _rk_increment(f, method, y):
 
 class OnlineNeuralCDE:
     def __init__(self, model, batch_size, initial_value_if_nan=0.0, time_index=0):
-        if model.interpolation not in ("linear", "rectilinear"):
+        if model.interpolation not in ("linear", "rectilinear", "cubic_hermite"):
             raise ValueError("online inference needs a causal control path: interpolation 'linear' or 'rectilinear', not '%s' (a natural "
                              "cubic or smoothed path at knot k depends on later observations)" % model.interpolation)
         if model.solver not in _STAGE_TIMES:
@@ -48,6 +53,7 @@ class OnlineNeuralCDE:
         self.model = model
         self.batch_size = int(batch_size)
         self.rectilinear = model.interpolation == "rectilinear"
+        self.hermite = model.interpolation == "cubic_hermite"
         self.initial_value_if_nan = float(initial_value_if_nan)
         self.time_index = int(time_index)
         if self.rectilinear and not 0 <= self.time_index < model.input_dim:
@@ -172,10 +178,21 @@ class OnlineNeuralCDE:
                 mid = fill
             da, db = mid - self.last_row, fill - mid
             dl = torch.where((self.count == 1)[:, None], da, self.prev_dx)
+            if self.hermite:      # the piece's b is dl; a stage's offset in the piece as the batch solve forms it, (n + offset) - n
+                two_c = 2 * (3 * (da - dl) - da + dl)
+                three_d = (da - dl) - two_c
+                n = (self.count - 1).to(xr.dtype)[:, None]
+                frac = [(n + s) - n for s in _STAGE_TIMES[method]]
             z = self.z
             for start, left, own in [(self.last_row, dl, da)] + ([(mid, da, db)] if self.rectilinear else []):
                 def f(j, y, start=start, left=left, own=own):
-                    dx = left if j == 0 else own
+                    if self.hermite and j > 0:      # stage 1 sits on the knot: the left piece at frac = 1, which is b (and X = the knot)
+                        s = frac[j]
+                        if mode == "evaluate":
+                            return func(t0, torch.cat([y, start + (left + (0.5 * two_c + three_d * s / 3) * s) * s], dim=-1))
+                        dx = left + (two_c + three_d * s) * s
+                    else:
+                        dx = left if j == 0 else own
                     if mode == "matmul":
                         return (func(t0, y) @ dx.unsqueeze(-1)).squeeze(-1)
                     if mode == "derivative":
@@ -198,7 +215,7 @@ class OnlineNeuralCDE:
         p = _lib.NcdeProblem()
         p.abi_version = _lib.NCDE_ABI_VERSION
         p.batch, p.hidden, p.channels, p.n_knots = self.batch_size, m_.hidden_dim, m_.input_dim, 2
-        p.interp, p.method, p.output, p.flags = _lib.INTERP["linear"], _lib.METHOD[m_.solver], _lib.OUT_KNOTS, 0
+        p.interp, p.method, p.output, p.flags = _lib.INTERP["cubic" if self.hermite else "linear"], _lib.METHOD[m_.solver], _lib.OUT_KNOTS, 0
         if len(spec.layers) > _lib.NCDE_MAX_LAYERS:
             raise NotImplementedError("at most %d hidden layers" % _lib.NCDE_MAX_LAYERS)
         p.n_layers = len(spec.layers)
@@ -225,11 +242,12 @@ class OnlineNeuralCDE:
             if spec.kind != "original" or spec.mode != "matmul":
                 reason = "online step: a gated or low-rank vector field or the evaluate / derivative input"
             else:
-                rc = _lib.lib().ncde_stream_workspace_bytes(ctypes.byref(self._problem()))
+                query = "ncde_stream_hermite_workspace_bytes" if self.hermite else "ncde_stream_workspace_bytes"
+                rc = getattr(_lib.lib(), query)(ctypes.byref(self._problem()))
                 if rc == -2:
                     reason = "online step: " + (_lib.lib().ncde_last_error_string() or b"").decode()
                 else:
-                    _lib.check(rc, "ncde_stream_workspace_bytes")
+                    _lib.check(rc, query)
         if reason is not None:
             unfused.warn_once(reason)
         self._route[key] = reason is None
@@ -256,5 +274,6 @@ class OnlineNeuralCDE:
             s.z_out = out.data_ptr()
         with torch.cuda.device(x.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            _lib.check(_lib.lib().ncde_stream_step(ctypes.byref(p), ctypes.byref(s), stream), "ncde_stream_step")
+            entry = "ncde_stream_step_hermite" if self.hermite else "ncde_stream_step"
+            _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(p), ctypes.byref(s), stream), entry)
         return out

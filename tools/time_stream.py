@@ -1,6 +1,8 @@
 """Per-observation latency of online inference at cfg2 dimensions (C 20, H = HH = 32, three layers, rectilinear, rk4; run on the GPU box).
 
     python tools/time_stream.py [--out profiles/online_step_latency.json]      # ROUNDS=5 STEPS=200 REPS=10
+    python tools/time_stream.py --interpolation linear,cubic_hermite           # the Hermite step (ncde_stream_step_hermite) next to the
+                                                                               # linear step at the same shape: legs alternate in ONE process
 
 Legs, per batch size B in {1, 16, 256, 4096}:
   online step      handle.step(x_k) of NeuralCDE.online, one new observation per call (one launch of ncde_stream_step)
@@ -30,22 +32,36 @@ def main():
     ap.add_argument("--out", default=None, help="write the medians and spreads here as JSON")
     ap.add_argument("--batches", default="1,16,256,4096")
     ap.add_argument("--prefixes", default="10,100,399")
+    ap.add_argument("--interpolation", default="rectilinear", help="the causal control path: rectilinear, linear or cubic_hermite; a comma "
+                    "list times one online leg per path (the prefix legs run on the first)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a timing needs the GPU"
     ROUNDS, STEPS, REPS = (int(os.environ.get(k, d)) for k, d in (("ROUNDS", 5), ("STEPS", 200), ("REPS", 10)))
     c = dict(bench.CONFIGS["cfg2"])
     prefixes = [int(k) for k in args.prefixes.split(",")]
     L = max(prefixes + [STEPS]) + 1
-    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
+    paths = args.interpolation.split(",")
+    assert all(p in ("rectilinear", "linear", "cubic_hermite") for p in paths), paths
+    path = paths[0]
+    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "interpolation": paths, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
     for B in (int(b) for b in args.batches.split(",")):
         torch.manual_seed(0)
-        model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation="rectilinear", solver="rk4").cuda()
+        model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=path, solver="rk4").cuda()
         x = torch.from_numpy(ncde_amd.data.synthetic_series(B, L, c["C"] - 1, missing=c["missing"], seed=1234)).cuda()
         rows = x.transpose(0, 1).contiguous()
-        handle = model.online(B)
-        coeffs = {k: ncde_amd.linear_interpolation_coeffs(x[:, :k].contiguous(), rectilinear=0, initial_value_if_nan=0.0) for k in prefixes}
+        handles = {path: model.online(B)}
+        for q in paths[1:]:      # the same weights on the other paths
+            other = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=q, solver="rk4").cuda()
+            other.load_state_dict(model.state_dict())
+            handles[q] = other.online(B)
+        if path == "rectilinear":
+            coeffs = {k: ncde_amd.linear_interpolation_coeffs(x[:, :k].contiguous(), rectilinear=0, initial_value_if_nan=0.0) for k in prefixes}
+        else:
+            build = ncde_amd.hermite_cubic_coefficients_with_backward_differences if path == "cubic_hermite" else ncde_amd.linear_interpolation_coeffs
+            coeffs = {k: build(x[:, :k].contiguous(), initial_value_if_nan=0.0, forward_fill=True) for k in prefixes}
 
-        def online(n):
+        def online(n, q=path):
+            handle = handles[q]
             handle.reset()
             handle.step(rows[0])
             torch.cuda.synchronize()
@@ -64,8 +80,9 @@ def main():
                 torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
-        legs = [("online step", lambda: online(STEPS))] + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
-        online(20)
+        legs = [("online step" if q == path else "online " + q, lambda q=q: online(STEPS, q)) for q in paths] + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
+        for q in paths:
+            online(20, q)
         for k in prefixes:
             prefix(k, 2)
         times = {name: [] for name, _ in legs}
@@ -73,12 +90,12 @@ def main():
             for name, fn in legs:
                 dt = fn()
                 times[name].append(dt)
-                print("B %5d round %d  %-12s %10.1f us/call" % (B, r, name, dt * 1e6), flush=True)
+                print("B %5d round %d  %-20s %10.1f us/call" % (B, r, name, dt * 1e6), flush=True)
         for name, _ in legs:
             v = times[name]
             rec = {"B": B, "leg": name, "median_us": statistics.median(v) * 1e6, "min_us": min(v) * 1e6, "max_us": max(v) * 1e6}
             report["legs"].append(rec)
-            print("B %5d median   %-12s %10.1f us/call  (min %.1f, max %.1f over %d rounds)" % (B, name, rec["median_us"], rec["min_us"], rec["max_us"], ROUNDS),
+            print("B %5d median   %-20s %10.1f us/call  (min %.1f, max %.1f over %d rounds)" % (B, name, rec["median_us"], rec["min_us"], rec["max_us"], ROUNDS),
                   flush=True)
     if args.out:
         with open(args.out, "w") as fh:
