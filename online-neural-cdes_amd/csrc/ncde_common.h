@@ -241,6 +241,40 @@ struct StageCombine {
     }
 };
 
+struct StageTranspose {
+    // The exact transpose of StageCombine's step, walked backwards: reverse stage j handles forward stage S-1-j.  a0 = dL/dy1 of the
+    // step, d = dL/dY of the forward stage just differentiated (its VJP with the cotangent this function returned one stage earlier),
+    // ka1 / ka2 / ky1 keep d of reverse stages 0 / 1 / 2.  With d1..d4 the d of forward stages 1..4 of RK4 (3/8) and c_i the cotangent
+    // of k_i:  c4 = a dt/8;  c3 = 3 c4 + dt d4;  c2 = 3 c4 - dt d4 + dt d3;  c1 = c4 + dt d4 - dt/3 d3 + dt/3 d2;  a += d4+d3+d2+d1.
+    // Midpoint: c2 = dt a;  c1 = dt/2 d2;  a += d2 + d1.  Euler: c1 = dt a;  a += d1.
+    // Returns the cotangent of the next (earlier) forward stage's k; after the last reverse stage (`last`) a0 = dL/dy0 instead and
+    // the caller seeds the next step with seed().
+    __device__ static __forceinline__ float apply(int method, int j, float d, float dt, float& a0, float& ka1, float& ka2, float& ky1, bool& last) {
+        last = false;
+        if (method == NCDE_RK4_38) {
+            const float c4 = (a0 * dt) * 0.125f;
+            const float dt3 = dt * 0.333333343267440796f;
+            if (j == 0) { ka1 = d; return 3.0f * c4 + dt * d; }
+            if (j == 1) { ka2 = d; return (3.0f * c4 - dt * ka1) + dt * d; }
+            if (j == 2) { ky1 = d; return ((c4 + dt * ka1) - dt3 * ka2) + dt3 * d; }
+            last = true;
+            a0 = (((a0 + ka1) + ka2) + ky1) + d;
+            return 0.0f;
+        }
+        if (method == NCDE_MIDPOINT) {
+            if (j == 0) { ka1 = d; return (0.5f * dt) * d; }
+            last = true;
+            a0 = (a0 + ka1) + d;
+            return 0.0f;
+        }
+        last = true;
+        a0 = a0 + d;
+        return 0.0f;
+    }
+    // cotangent of the LAST forward stage's k of a step whose y1 has cotangent a0: rk4 (a dt)/8, midpoint / euler dt a
+    __device__ static __forceinline__ float seed(int method, float a0, float dt) { return method == NCDE_RK4_38 ? (a0 * dt) * 0.125f : dt * a0; }
+};
+
 // stage descriptor of stage j of forward step n on the default integer grid with step 1
 __device__ __forceinline__ StageDesc default_stage(int method, float t, int n_pieces) {
     StageDesc d;

@@ -1,5 +1,6 @@
 // Stage-level building blocks of the generic (runtime-dimension) family, shared by the persistent fixed-step kernels
-// (ncde_generic.hip) and the adaptive dopri5 kernels (ncde_adaptive.hip).  One workgroup = one tile of 16 samples, 4 waves;
+// (ncde_generic.hip; the gradient accumulation also by ncde_variant.hip and ncde_lowrank.hip) and the adaptive dopri5 kernels
+// (ncde_adaptive.hip).  One workgroup = one tile of 16 samples, 4 waves;
 // every activation lives in LDS as [unit][sample] (see ncde_generic.hip for the layout rationale).
 #pragma once
 #include "ncde_common.h"
@@ -63,6 +64,49 @@ __device__ void dense_relu(const float* __restrict__ W, const float* __restrict_
     }
 }
 
+// *p += v on this workgroup's PRIVATE gradient partial.  In global memory (in_lds == 0; matmul heads of the variant family: 41k floats
+// per stage at cfg2 dims): a hardware float add without return instead of load / add / store, so nothing waits for the old value --
+// the read-modify-write round trips were the longest thing in a stage (gru/matmul 268 -> 205 ms).  Every address is only ever
+// touched by one wave, in program order, so the sum order -- and the result -- is the same on every run.  In LDS a plain
+// read-modify-write is the faster one (flat atomics into the LDS aperture: evaluate 32 -> 38 ms).
+__device__ __forceinline__ void grad_accum(float* p, float v, int in_lds) {
+    if (in_lds) *p += v;
+    else unsafeAtomicAdd(p, v);
+}
+
+// rows of a gradient segment of the partial: row r starts at p + r ld (a bias vector: ld = 1)
+struct GradRows {
+    float* p;
+    long long ld;
+    __device__ __forceinline__ float* operator()(int r) const { return p + r * ld; }
+};
+
+// gW[j][i] += w sum_s gpre[j][s] xin[i][s];  gb[j] += w sum_s gpre[j][s]   (samples are the K dim of the MFMA).  row_w(j) /
+// row_b(j): where row j of the weight gradient / its bias entry live in the partial (GradRows for one matrix; the stacked head rows
+// of the low-rank field sit in two segments)
+template <class RowW, class RowB>
+__device__ void dw_acc(const float* gpre, const float* xin, int N, int K, float w, RowW row_w, RowB row_b, int tid, int wave, int lane, int in_lds) {
+    const int li = lane & 15, lk = lane >> 4;
+    for (int jj = tid; jj < N; jj += GEN_THREADS) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) sum += gpre[jj * 16 + s];
+        grad_accum(row_b(jj), w * sum, in_lds);
+    }
+    const int njt = (N + 15) >> 4, nit = (K + 15) >> 4;
+    for (int tt = wave; tt < njt * nit; tt += GEN_NW) {
+        const int jt = tt / nit, it = tt - jt * nit;
+        f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) g = mfma16(gpre[(16 * jt + li) * 16 + 4 * ks + lk], xin[(16 * it + li) * 16 + 4 * ks + lk], g);
+        const int col = 16 * it + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * jt + 4 * lk + r;
+            if (row < N && col < K) grad_accum(row_w(row) + col, w * g[r], in_lds);
+        }
+    }
+}
 
 // One evaluation of f_theta(YS) . dX/dt for the tile: hidden layers (relu) -> output tiles -> tanh -> channel
 // contraction; KO[h][s] receives the stage derivative.  Ends with a workgroup barrier.

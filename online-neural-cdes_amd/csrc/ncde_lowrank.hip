@@ -12,6 +12,7 @@
 #include "ncde_generic_stage.h"
 #include "ncde_host.h"
 #include "ncde_lowrank.h"
+#include "ncde_timeloop.h"
 
 #define LR_THREADS GEN_THREADS
 #define LR_NW GEN_NW
@@ -120,10 +121,8 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_fwd_lowrank(KArgs 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b0 = blockIdx.x * NCDE_TILE;
-    const int H = a.H, Hp = ru16(H), Cp = ru4(a.C), L = a.n_layers;
-    int Dp = Hp;
-    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    const int HS = Hp * 16, DS = Dp * 16;
+    const TileDims td = tile_dims(a);
+    const int H = a.H, Cp = td.Cp, HS = td.HS, DS = td.DS, L = a.n_layers;
     const LrDims d = lr_dims(a, lds);
     float* U = lds;              // stage state [Dp][16] (rows >= H stay 0)
     float* XA = U + DS;          // ping-pong activations of the inner net (2 buffers)
@@ -146,25 +145,15 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_fwd_lowrank(KArgs 
             a.out[((long long)b * a.n_out) * H + h] = v;
         }
     }
-    const int S = n_stages(a.method);
-    const bool planned = a.plan != nullptr;
-    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier of the loop)
-    const int n_steps = planned ? a.n_steps_fwd : a.T - 1;
-    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
-    for (int n = 0; n < n_steps; ++n) {
-        const int* pstep = planned ? a.plan + plan_off_fwd() + n * plan_step_words(S) : nullptr;
-        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
-        for (int j = 0; j < S; ++j) {
-            const StageDesc sd = planned ? plan_stage(pstep, j) : default_stage(a.method, (float)n + stage_offset(a.method, j), a.n_pieces);
+    if (!plan_ok(a)) return;      // (uniform: before the first barrier of the loop)
+    const FwdWalk walk = fwd_walk(a);
+    for (int n = 0; n < walk.n_steps; ++n) {
+        const FwdStep st = fwd_step(a, walk, n);
+        for (int j = 0; j < walk.S; ++j) {
+            const StageDesc sd = fwd_stage(a, walk, st.pstep, n, j);
             __syncthreads();      // U of this stage is complete (first stage: the z0 load above)
             load_dx(a, b0, sd, CIN, Cp, tid);
-            if (a.stages) {
-                float* rec = a.stages + ((long long)(n * S + j) * a.B + b0) * H;
-                for (int e = tid; e < 16 * H; e += LR_THREADS) {
-                    const int s = e / H, h = e - s * H;
-                    if (b0 + s < a.B) rec[e] = U[h * 16 + s];
-                }
-            }
+            if (a.stages) stage_record_store(a, n * walk.S + j, b0, U, tid, LR_THREADS);
             const float* in = U;
             for (int l = 0; l < L; ++l) {
                 float* outb = XA + (l & 1) * DS;
@@ -176,30 +165,7 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_fwd_lowrank(KArgs 
             __syncthreads();
             lr_contract(d, PQ, CIN, KO, HS, tid);
             __syncthreads();
-            for (int e = tid; e < HS; e += LR_THREADS) {
-                float y0 = Y0[e], k1 = K1[e], k2 = K2[e];
-                const float yprev = y0;
-                bool last;
-                const float ys = StageCombine::apply(a.method, j, KO[e], dt, y0, k1, k2, last);
-                U[e] = ys;
-                K1[e] = k1;
-                K2[e] = k2;
-                if (last) {
-                    Y0[e] = y0;
-                    const int h = e >> 4, s = e & 15, b = b0 + s;
-                    if (h < H && b < a.B) {
-                        if (planned) {
-                            const int q0 = pstep[1], q1 = q0 + pstep[2];
-                            for (int q = q0; q < q1; ++q) {
-                                const int kind = pout[2 * q];
-                                const float slope = __int_as_float(pout[2 * q + 1]);
-                                a.out[((long long)b * a.n_out + q) * H + h] = kind == 1 ? y0 : (kind == 0 ? yprev : yprev + slope * (y0 - yprev));
-                            }
-                        } else if (a.output == NCDE_OUT_KNOTS) a.out[((long long)b * a.n_out + (n + 1)) * H + h] = y0;
-                        else if (n == a.T - 2) a.out[((long long)b * a.n_out + 1) * H + h] = y0;
-                    }
-                }
-            }
+            for (int e = tid; e < HS; e += LR_THREADS) fwd_bookkeep(a, walk, st.pstep, n, j, st.dt, e, b0, KO, U, Y0, K1, K2);
         }
     }
 }
@@ -208,39 +174,6 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_fwd_lowrank(KArgs 
 // adjoint / exact discrete backward
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-// *p += v on this workgroup's PRIVATE gradient partial: every address is only ever touched by one thread, in program order, so
-// the result is the same on every run (global memory: a float add without return, as in ncde_variant.hip)
-__device__ __forceinline__ void lr_accum(float* p, float v, int in_lds) {
-    if (in_lds) *p += v;
-    else unsafeAtomicAdd(p, v);
-}
-
-// gW[j][i] += w sum_s gpre[j][s] xin[i][s];  gb[j] += w sum_s gpre[j][s]   (samples are the K dim of the MFMA).  row_w(j) /
-// row_b(j): where row j of the weight gradient / its bias entry live in the partial (the stacked head rows sit in two segments)
-template <class RowW, class RowB>
-__device__ void lr_dw_acc(const float* gpre, const float* xin, int N, int K, float w, RowW row_w, RowB row_b, int tid, int wave, int lane, int in_lds) {
-    const int li = lane & 15, lk = lane >> 4;
-    for (int jj = tid; jj < N; jj += LR_THREADS) {
-        float sum = 0.0f;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) sum += gpre[jj * 16 + s];
-        lr_accum(row_b(jj), w * sum, in_lds);
-    }
-    const int njt = (N + 15) >> 4, nit = (K + 15) >> 4;
-    for (int tt = wave; tt < njt * nit; tt += LR_NW) {
-        const int jt = tt / nit, it = tt - jt * nit;
-        f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) g = mfma16(gpre[(16 * jt + li) * 16 + 4 * ks + lk], xin[(16 * it + li) * 16 + 4 * ks + lk], g);
-        const int col = 16 * it + li;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * jt + 4 * lk + r;
-            if (row < N && col < K) lr_accum(row_w(row) + col, w * g[r], in_lds);
-        }
-    }
-}
 
 // out[i][s] = sum_j W(j)[i] gpre[j][s], i < ru16(K); optionally x relu'(mask[i][s]).  wrow(j): row j of the [N][K] matrix
 template <class WRow>
@@ -337,10 +270,8 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_adj_lowrank(KArgs 
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b0 = blockIdx.x * NCDE_TILE;
-    const int H = a.H, Hp = ru16(H), Cp = ru4(a.C), L = a.n_layers;
-    int Dp = Hp;
-    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    const int HS = Hp * 16, DS = Dp * 16;
+    const TileDims td = tile_dims(a);
+    const int H = a.H, Cp = td.Cp, HS = td.HS, DS = td.DS, L = a.n_layers;
     const LrDims d = lr_dims(a, lds);
     float* U = lds;                  // stage input (rows >= H stay 0)
     float* XI = U + DS;              // [L] activations of the inner net
@@ -366,54 +297,22 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_adj_lowrank(KArgs 
     if (!a.gacc_in_lds)
         for (int e = tid; e < a.theta_size; e += LR_THREADS) gacc[e] = 0.0f;
     __syncthreads();
-    const int last_row = a.n_out - 1;
-    const int S = n_stages(a.method);
-    const bool disc = a.discrete != 0;
-    const bool planned = a.plan != nullptr;
-    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier of the loop)
-    const int pw_ = plan_step_words(S);
-    const int* pfwd = planned ? a.plan + plan_off_fwd() : nullptr;
-    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
-    const int* padj = planned ? a.plan + plan_off_adj(S, a.n_steps_fwd, a.n_out) : nullptr;
-    const int n_rsteps = planned ? (disc ? a.n_steps_fwd : a.n_steps_adj) : a.T - 1;
-    for (int e = tid; e < HS; e += LR_THREADS) {
-        const int h = e >> 4, s = e & 15, b = b0 + s;
-        if (h < H && b < a.B) {
-            const long long o = ((long long)b * a.n_out + last_row) * H + h;
-            float g = a.grad_out[o];
-            if (planned && disc) g = plan_out_cotangent(a, pfwd + (a.n_steps_fwd - 1) * pw_, pout, 1, (long long)b * a.n_out, h);
-            A0[e] = g;
-            if (disc) {
-                const float dtl = planned ? __int_as_float(pfwd[(a.n_steps_fwd - 1) * pw_]) : 1.0f;
-                AS[e] = a.method == NCDE_RK4_38 ? (g * dtl) * 0.125f : dtl * g;
-            } else {
-                const float y = a.z_out[o];
-                Y0[e] = y; U[e] = y; AS[e] = g;
-            }
-        }
-    }
+    if (!plan_ok(a)) return;      // (uniform: before the first barrier of the loop)
+    const RevWalk walk = rev_walk(a);
+    const AdjLds bk = {U, AS, Y0, KY1, KY2, A0, KA1, KA2};
+    for (int e = tid; e < HS; e += LR_THREADS) adj_init(a, walk, e, b0, bk);
     const float* xl = XI + (L - 1) * DS;
     auto head_w = [&](int n) { return gacc + (n < d.NH ? a.gWo_off + (long long)n * d.dlast : a.gWg_off + (long long)(n - d.NH) * d.dlast); };
     auto head_b = [&](int n) { return gacc + (n < d.NH ? a.gbo_off + n : a.gbg_off + (n - d.NH)); };
     auto head_row = [&](int n) { return lr_wrow(a, d, n); };
-    for (int rstep = 0; rstep < n_rsteps; ++rstep) {
-        const int n = a.T - 1 - rstep, m = n_rsteps - 1 - rstep;   // default grid: reverse step n -> n-1; m = forward step transposed
-        const int* pstep = planned ? (disc ? pfwd + m * pw_ : padj + rstep * pw_) : nullptr;
-        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
-        for (int j = 0; j < S; ++j) {
-            StageDesc sd;
-            if (planned) sd = plan_stage(pstep, disc ? S - 1 - j : j);
-            else sd = default_stage(a.method, disc ? (float)(n - 1) + stage_offset(a.method, S - 1 - j) : -(-(float)n + stage_offset(a.method, j)), a.n_pieces);
-            const float w = disc ? 1.0f : stage_weight(a.method, j) * dt;
+    for (int rstep = 0; rstep < walk.n_rsteps; ++rstep) {
+        const RevStep st = rev_step(a, walk, rstep);
+        for (int j = 0; j < walk.S; ++j) {
+            const RevStage rs = rev_stage(a, walk, st, j);
+            const float w = rs.w;
             __syncthreads();      // U / AS of this stage are complete (first stage: the loads above)
-            load_dx(a, b0, sd, CIN, Cp, tid);
-            if (disc) {
-                const float* rec = a.stages + ((long long)(m * S + (S - 1 - j)) * a.B + b0) * H;
-                for (int e = tid; e < 16 * H; e += LR_THREADS) {
-                    const int s = e / H, h = e - s * H;
-                    U[h * 16 + s] = b0 + s < a.B ? rec[e] : 0.0f;
-                }
-            }
+            load_dx(a, b0, rs.sd, CIN, Cp, tid);
+            if (walk.disc) stage_record_load(a, rev_record_index(walk, st, j), b0, U, tid, LR_THREADS);
             __syncthreads();
             // ---- the stage forward, every layer kept ------------------------------------------------------------------------
             const float* in = U;
@@ -428,7 +327,7 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_adj_lowrank(KArgs 
             lr_head_vjp(d, PQ, CIN, AS, G, KOY, HS, tid);
             __syncthreads();
             // ---- dM_h | dM_o += w G (x) x_L, their biases;  dL/dpre_L = (M_h^T gP + M_o^T gQ) * relu'(x_L): one GEMM over the stacked rows
-            if (w != 0.0f) lr_dw_acc(G, xl, d.NT, d.dlast, w, head_w, head_b, tid, wave, lane, a.gacc_in_lds);
+            if (w != 0.0f) dw_acc(G, xl, d.NT, d.dlast, w, head_w, head_b, tid, wave, lane, a.gacc_in_lds);
             lr_bwd_data(head_row, d.NT, d.dlast, G, xl, GA, wave, lane);
             __syncthreads();
             // ---- the inner net backwards (the generic family's) ----------------------------------------------------------------
@@ -441,82 +340,14 @@ extern "C" __global__ __launch_bounds__(LR_THREADS) void ncde_adj_lowrank(KArgs 
                 if (w != 0.0f) {
                     float* gW = gacc + a.gW_off[l];
                     float* gb = gacc + a.gb_off[l];
-                    lr_dw_acc(gpre, xin, N, K, w, [&](int r) { return gW + (long long)r * K; }, [&](int r) { return gb + r; }, tid, wave, lane, a.gacc_in_lds);
+                    dw_acc(gpre, xin, N, K, w, GradRows{gW, K}, GradRows{gb, 1}, tid, wave, lane, a.gacc_in_lds);
                 }
                 lr_bwd_data([&](int r) { return Wl + (long long)r * K; }, N, K, gpre, l > 0 ? xin : nullptr, l == 0 ? DU : gx, wave, lane);
                 __syncthreads();
                 float* tmp = gpre; gpre = gx; gx = tmp;
             }
-            // ---- Butcher bookkeeping (d = dL/dy of the stage) ---------------------------------------------------------------------
-            for (int e = tid; e < HS; e += LR_THREADS) {
-                const int h = e >> 4, s = e & 15, b = b0 + s;
-                const bool valid = h < H && b < a.B;
-                const float dd = h < H ? DU[e] : 0.0f;
-                if (disc) {
-                    float a0 = A0[e];
-                    bool last = false;
-                    float next = 0.0f;
-                    if (a.method == NCDE_RK4_38) {
-                        const float c4 = (a0 * dt) * 0.125f;
-                        const float dt3 = dt * 0.333333343267440796f;
-                        if (j == 0) { KA1[e] = dd; next = 3.0f * c4 + dt * dd; }
-                        else if (j == 1) { KA2[e] = dd; next = (3.0f * c4 - dt * KA1[e]) + dt * dd; }
-                        else if (j == 2) { KY1[e] = dd; next = ((c4 + dt * KA1[e]) - dt3 * KA2[e]) + dt3 * dd; }
-                        else { a0 = (((a0 + KA1[e]) + KA2[e]) + KY1[e]) + dd; last = true; }
-                    } else if (a.method == NCDE_MIDPOINT) {
-                        if (j == 0) { KA1[e] = dd; next = (0.5f * dt) * dd; }
-                        else { a0 = (a0 + KA1[e]) + dd; last = true; }
-                    } else {
-                        a0 = a0 + dd; last = true;
-                    }
-                    if (last) {
-                        float dtp = 1.0f;
-                        if (planned) {
-                            if (valid) {
-                                const long long brow = (long long)b * a.n_out;
-                                a0 = a0 + plan_out_cotangent(a, pstep, pout, 0, brow, h);
-                                if (m > 0) a0 = a0 + plan_out_cotangent(a, pstep - pw_, pout, 1, brow, h);
-                                else a0 = a0 + a.grad_out[brow * H + h];
-                            }
-                            if (m > 0) dtp = __int_as_float(pstep[-pw_]);
-                        } else if (a.output == NCDE_OUT_KNOTS || n == 1) {
-                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out + (a.output == NCDE_OUT_KNOTS ? n - 1 : 0)) * H + h] : 0.0f);
-                        }
-                        A0[e] = a0;
-                        next = a.method == NCDE_RK4_38 ? (a0 * dtp) * 0.125f : dtp * a0;
-                        if (m == 0 && valid) a.grad_z0[(long long)b * H + h] = a0;
-                    }
-                    AS[e] = next;
-                } else {
-                    float y0 = Y0[e], k1 = KY1[e], k2 = KY2[e];
-                    bool last;
-                    const float ys = StageCombine::apply(a.method, j, -KOY[e], dt, y0, k1, k2, last);
-                    U[e] = ys; KY1[e] = k1; KY2[e] = k2;
-                    float a0 = A0[e], q1 = KA1[e], q2 = KA2[e];
-                    const float as = StageCombine::apply(a.method, j, dd, dt, a0, q1, q2, last);
-                    KA1[e] = q1; KA2[e] = q2;
-                    if (!last) {
-                        AS[e] = as;
-                    } else {
-                        if (planned) {
-                            const int row = pstep[1];
-                            if (row >= 0) {
-                                const long long o = ((long long)b * a.n_out + row) * H + h;
-                                y0 = valid ? a.z_out[o] : 0.0f;
-                                a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
-                            }
-                        } else if (a.output == NCDE_OUT_KNOTS) {
-                            const long long o = ((long long)b * a.n_out + (n - 1)) * H + h;
-                            y0 = valid ? a.z_out[o] : 0.0f;
-                            a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
-                        } else if (n == 1) {
-                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out) * H + h] : 0.0f);
-                        }
-                        Y0[e] = y0; U[e] = y0; A0[e] = a0; AS[e] = a0;
-                        if (rstep == n_rsteps - 1 && valid) a.grad_z0[(long long)b * H + h] = a0;
-                    }
-                }
-            }
+            // ---- Butcher bookkeeping (d = dL/dy of the stage = the first H rows of DU) ----------------------------------------------
+            for (int e = tid; e < HS; e += LR_THREADS) adj_bookkeep(a, walk, st, rstep, j, e, b0, (e >> 4) < H ? DU[e] : 0.0f, KOY[e], bk);
         }
     }
     if (a.gacc_in_lds) {

@@ -2357,7 +2357,7 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
                     const int H = a.Hr;                          // row width of the caller's z_out / grad_out / grad_z0
                     const float d = KOA[e];
                     if (disc) {
-                        // transpose of the Butcher step: d = dL/dY of this stage (see ncde_generic.hip / ncde_variant.hip)
+                        // transpose of the Butcher step: d = dL/dY of this stage (see StageTranspose, ncde_common.h)
                         bool last = false;
                         float next = 0.0f;
                         if (a.method == NCDE_RK4_38) {

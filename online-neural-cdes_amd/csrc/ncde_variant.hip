@@ -9,12 +9,13 @@
 // the whole time loop inside the kernel, per-workgroup parameter-gradient partials); the head loop carries two
 // accumulators (tanh and sigmoid head), the inner net can run twice per stage (GRU), the field input has H + C rows
 // in the evaluate / derivative modes.  The continuous adjoint and the exact discrete backward share one kernel.
-#include "ncde_common.h"
+#include "ncde_generic_stage.h"
 #include "ncde_host.h"
+#include "ncde_timeloop.h"
 #include "ncde_variant.h"
 
-#define VR_NW 4
-#define VR_THREADS (64 * VR_NW)
+#define VR_NW GEN_NW
+#define VR_THREADS GEN_THREADS
 #define VR_MAXJT 8  // last hidden width <= 128
 
 namespace {
@@ -230,10 +231,9 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_fwd_variant(KArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int b0 = blockIdx.x * NCDE_TILE;
-    const int H = a.H, C = a.C, Hp = ru16(H), Cp = ru4(C), d0 = a.d0, L = a.n_layers;
-    int Dp = max(Hp, ru16(d0));
-    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    const int HS = Hp * 16, DS = Dp * 16;
+    const int H = a.H, C = a.C, d0 = a.d0, L = a.n_layers;
+    const TileDims td = tile_dims(a, d0);
+    const int Hp = td.Hp, Cp = td.Cp, HS = td.HS, DS = td.DS;
     const bool matmul = a.field_input == NCDE_INPUT_MATMUL, gru = a.field_kind == NCDE_FIELD_GRU, gated = a.field_kind != NCDE_FIELD_ORIGINAL;
     float* U = lds;              // field input [d0][16]: rows < H = stage state, rows H.. = control input
     float* RU = U + DS;          // rg * u (gru)
@@ -261,29 +261,19 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_fwd_variant(KArgs 
             a.out[((long long)b * a.n_out) * H + h] = v;
         }
     }
-    const int S = n_stages(a.method);
     const int dlast = L ? a.dout[L - 1] : d0;
     const int ncq = Cp >> 2, ngrp = matmul ? (Hp >> 2) : (Hp >> 4), per_grp = matmul ? ncq : 1;
-    const bool planned = a.plan != nullptr;
-    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier)
-    const int n_steps = planned ? a.n_steps_fwd : a.T - 1;
-    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
-    for (int n = 0; n < n_steps; ++n) {
-        const int* pstep = planned ? a.plan + plan_off_fwd() + n * plan_step_words(S) : nullptr;
-        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
-        for (int j = 0; j < S; ++j) {
-            const StageDesc sd = planned ? plan_stage(pstep, j) : default_stage(a.method, (float)n + stage_offset(a.method, j), a.n_pieces);
+    if (!plan_ok(a)) return;      // (uniform: before the first barrier)
+    const FwdWalk walk = fwd_walk(a);
+    for (int n = 0; n < walk.n_steps; ++n) {
+        const FwdStep st = fwd_step(a, walk, n);
+        for (int j = 0; j < walk.S; ++j) {
+            const StageDesc sd = fwd_stage(a, walk, st.pstep, n, j);
             vr_load_cin(a, b0, sd, a.field_input == NCDE_INPUT_EVALUATE, CIN, Cp, tid);
             __syncthreads();
             if (!matmul)
                 for (int e = tid; e < C * 16; e += VR_THREADS) U[H * 16 + e] = CIN[e];
-            if (a.stages) {
-                float* rec = a.stages + ((long long)(n * S + j) * a.B + b0) * H;
-                for (int e = tid; e < 16 * H; e += VR_THREADS) {
-                    const int s = e / H, h = e - s * H;
-                    if (b0 + s < a.B) rec[e] = U[h * 16 + s];
-                }
-            }
+            if (a.stages) stage_record_store(a, n * walk.S + j, b0, U, tid, VR_THREADS);
             __syncthreads();
             if (gru) {
                 vr_dense<1>(a.Wr, a.br, d0, d0, U, RG, wave, lane, wl_r);
@@ -314,30 +304,7 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_fwd_variant(KArgs 
                 if (matmul && 4 * grp + lk < Hp) KO[(4 * grp + lk) * 16 + li] = ksum;
             }
             __syncthreads();
-            for (int e = tid; e < HS; e += VR_THREADS) {
-                float y0 = Y0[e], k1 = K1[e], k2 = K2[e];
-                const float yprev = y0;
-                bool last;
-                const float ys = StageCombine::apply(a.method, j, KO[e], dt, y0, k1, k2, last);
-                U[e] = ys;
-                K1[e] = k1;
-                K2[e] = k2;
-                if (last) {
-                    Y0[e] = y0;
-                    const int h = e >> 4, s = e & 15, b = b0 + s;
-                    if (h < H && b < a.B) {
-                        if (planned) {
-                            const int q0 = pstep[1], q1 = q0 + pstep[2];
-                            for (int q = q0; q < q1; ++q) {
-                                const int kind = pout[2 * q];
-                                const float slope = __int_as_float(pout[2 * q + 1]);
-                                a.out[((long long)b * a.n_out + q) * H + h] = kind == 1 ? y0 : (kind == 0 ? yprev : yprev + slope * (y0 - yprev));
-                            }
-                        } else if (a.output == NCDE_OUT_KNOTS) a.out[((long long)b * a.n_out + (n + 1)) * H + h] = y0;
-                        else if (n == a.T - 2) a.out[((long long)b * a.n_out + 1) * H + h] = y0;
-                    }
-                }
-            }
+            for (int e = tid; e < HS; e += VR_THREADS) fwd_bookkeep(a, walk, st.pstep, n, j, st.dt, e, b0, KO, U, Y0, K1, K2);
             __syncthreads();
         }
     }
@@ -347,40 +314,6 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_fwd_variant(KArgs 
 // adjoint / exact discrete backward
 // ------------------------------------------------------------------------------------------------
 namespace {
-
-// *p += v on this workgroup's PRIVATE gradient partial.  In global memory (in_lds == 0; matmul heads: 41k floats per stage at
-// cfg2 dims): a hardware float add without return instead of load / add / store, so nothing waits for the old value -- the
-// read-modify-write round trips were the longest thing in a stage (gru/matmul 268 -> 205 ms).  Every address is only ever
-// touched by one wave, in program order, so the sum order -- and the result -- is the same on every run.  In LDS a plain
-// read-modify-write is the faster one (flat atomics into the LDS aperture: evaluate 32 -> 38 ms).
-__device__ __forceinline__ void vr_accum(float* p, float v, int in_lds) {
-    if (in_lds) *p += v;
-    else unsafeAtomicAdd(p, v);
-}
-
-// gW[j][i] += w sum_s gpre[j][s] xin[i][s];  gb[j] += w sum_s gpre[j][s]      (samples are the K dim of the MFMA)
-__device__ void vr_dw_acc(const float* gpre, const float* xin, int N, int K, float w, float* gW, float* gb, int tid, int wave, int lane, int in_lds) {
-    const int li = lane & 15, lk = lane >> 4;
-    for (int jj = tid; jj < N; jj += VR_THREADS) {
-        float sum = 0.0f;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) sum += gpre[jj * 16 + s];
-        vr_accum(gb + jj, w * sum, in_lds);
-    }
-    const int njt = (N + 15) >> 4, nit = (K + 15) >> 4;
-    for (int tt = wave; tt < njt * nit; tt += VR_NW) {
-        const int jt = tt / nit, it = tt - jt * nit;
-        f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) g = mfma16(gpre[(16 * jt + li) * 16 + 4 * ks + lk], xin[(16 * it + li) * 16 + 4 * ks + lk], g);
-        const int col = 16 * it + li;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = 16 * jt + 4 * lk + r;
-            if (row < N && col < K) vr_accum(gW + (long long)row * K + col, w * g[r], in_lds);
-        }
-    }
-}
 
 // The same weight gradient kept in this wave's REGISTERS for the whole sweep (tiles tt = wave + 4 q, q < VR_DWT): no
 // read-modify-write of the partial and no guards per stage -- the partial is touched once, at the end (vr_dw_flush).  Used
@@ -394,7 +327,7 @@ __device__ __forceinline__ void vr_dw_acc_reg(const float* gpre, const float* xi
         float sum = 0.0f;
 #pragma unroll
         for (int s = 0; s < 16; ++s) sum += gpre[jj * 16 + s];
-        vr_accum(gb + jj, w * sum, in_lds);
+        grad_accum(gb + jj, w * sum, in_lds);
     }
     const int nit = (K + 15) >> 4, ntile = ((N + 15) >> 4) * nit;
 #pragma unroll
@@ -475,10 +408,9 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lk = lane >> 4;
     const int b0 = blockIdx.x * NCDE_TILE;
-    const int H = a.H, C = a.C, Hp = ru16(H), Cp = ru4(C), d0 = a.d0, L = a.n_layers;
-    int Dp = max(Hp, ru16(d0));
-    for (int l = 0; l < L; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    const int HS = Hp * 16, DS = Dp * 16;
+    const int H = a.H, C = a.C, d0 = a.d0, L = a.n_layers;
+    const TileDims td = tile_dims(a, d0);
+    const int Hp = td.Hp, Cp = td.Cp, HS = td.HS, DS = td.DS;
     const bool matmul = a.field_input == NCDE_INPUT_MATMUL, gru = a.field_kind == NCDE_FIELD_GRU, gated = a.field_kind != NCDE_FIELD_ORIGINAL;
     float* U = lds;                  // field input (rows < H: y stage input)
     float* RG = U + DS;
@@ -512,32 +444,10 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
     if (!a.gacc_in_lds)
         for (int e = tid; e < a.theta_size; e += VR_THREADS) gacc[e] = 0.0f;
     __syncthreads();
-    const int last_row = a.n_out - 1;
-    const int S = n_stages(a.method);
-    const bool disc = a.discrete != 0;
-    const bool planned = a.plan != nullptr;
-    if (planned && !plan_header_ok(a, S)) return;      // (uniform: before the first barrier)
-    const int pw_ = plan_step_words(S);
-    const int* pfwd = planned ? a.plan + plan_off_fwd() : nullptr;
-    const int* pout = planned ? a.plan + plan_off_out(S, a.n_steps_fwd) : nullptr;
-    const int* padj = planned ? a.plan + plan_off_adj(S, a.n_steps_fwd, a.n_out) : nullptr;
-    const int n_rsteps = planned ? (disc ? a.n_steps_fwd : a.n_steps_adj) : a.T - 1;
-    for (int e = tid; e < HS; e += VR_THREADS) {
-        const int h = e >> 4, s = e & 15, b = b0 + s;
-        if (h < H && b < a.B) {
-            const long long o = ((long long)b * a.n_out + last_row) * H + h;
-            float g = a.grad_out[o];
-            if (planned && disc) g = plan_out_cotangent(a, pfwd + (a.n_steps_fwd - 1) * pw_, pout, 1, (long long)b * a.n_out, h);
-            A0[e] = g;
-            if (disc) {
-                const float dtl = planned ? __int_as_float(pfwd[(a.n_steps_fwd - 1) * pw_]) : 1.0f;
-                AS[e] = a.method == NCDE_RK4_38 ? (g * dtl) * 0.125f : dtl * g;
-            } else {
-                const float y = a.z_out[o];
-                Y0[e] = y; U[e] = y; AS[e] = g;
-            }
-        }
-    }
+    if (!plan_ok(a)) return;      // (uniform: before the first barrier)
+    const RevWalk walk = rev_walk(a);
+    const AdjLds bk = {U, AS, Y0, KY1, KY2, A0, KA1, KA2};
+    for (int e = tid; e < HS; e += VR_THREADS) adj_init(a, walk, e, b0, bk);
     const int dlast = a.dout[L - 1];
     const int ncq = Cp >> 2, ngrp = matmul ? (Hp >> 2) : (Hp >> 4), per_grp = matmul ? ncq : 1;
     const int njt = (dlast + 15) >> 4;
@@ -558,23 +468,13 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
         dw_reg = dw_reg && tiles(a.dout[0], a.din[0]) <= VR_NW * VR_DWT && (l_other < 0 || tiles(a.dout[l_other], a.din[l_other]) <= VR_NW * VR_DWT) &&
                  (!gru || tiles(d0, d0) <= VR_NW * VR_DWT);
     }
-    for (int rstep = 0; rstep < n_rsteps; ++rstep) {
-        const int n = a.T - 1 - rstep, m = n_rsteps - 1 - rstep;   // default grid: reverse step n -> n-1; m = forward step transposed
-        const int* pstep = planned ? (disc ? pfwd + m * pw_ : padj + rstep * pw_) : nullptr;
-        const float dt = planned ? __int_as_float(pstep[0]) : 1.0f;
-        for (int j = 0; j < S; ++j) {
-            StageDesc sd;
-            if (planned) sd = plan_stage(pstep, disc ? S - 1 - j : j);
-            else sd = default_stage(a.method, disc ? (float)(n - 1) + stage_offset(a.method, S - 1 - j) : -(-(float)n + stage_offset(a.method, j)), a.n_pieces);
-            const float w = disc ? 1.0f : stage_weight(a.method, j) * dt;
-            vr_load_cin(a, b0, sd, a.field_input == NCDE_INPUT_EVALUATE, CIN, Cp, tid);
-            if (disc) {
-                const float* rec = a.stages + ((long long)(m * S + (S - 1 - j)) * a.B + b0) * H;
-                for (int e = tid; e < 16 * H; e += VR_THREADS) {
-                    const int s = e / H, h = e - s * H;
-                    U[h * 16 + s] = b0 + s < a.B ? rec[e] : 0.0f;
-                }
-            }
+    for (int rstep = 0; rstep < walk.n_rsteps; ++rstep) {
+        const RevStep st = rev_step(a, walk, rstep);
+        for (int j = 0; j < walk.S; ++j) {
+            const RevStage rs = rev_stage(a, walk, st, j);
+            const float w = rs.w;
+            vr_load_cin(a, b0, rs.sd, a.field_input == NCDE_INPUT_EVALUATE, CIN, Cp, tid);
+            if (walk.disc) stage_record_load(a, rev_record_index(walk, st, j), b0, U, tid, VR_THREADS);
             __syncthreads();
             if (!matmul) {
                 for (int e = tid; e < C * 16; e += VR_THREADS) U[H * 16 + e] = CIN[e];
@@ -648,7 +548,7 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 const float sum = row16_sum(dP[r]);
-                                if (li == 0 && ht.rowD[r] >= 0) vr_accum(gbh + ht.rowD[r], w * sum, a.gacc_in_lds);
+                                if (li == 0 && ht.rowD[r] >= 0) grad_accum(gbh + ht.rowD[r], w * sum, a.gacc_in_lds);
                             }
                             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -661,7 +561,7 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
                                 const int jcol = 16 * jt + li;
 #pragma unroll
                                 for (int r = 0; r < 4; ++r)
-                                    if (ht.rowD[r] >= 0 && jcol < dlast) vr_accum(gWh + (long long)ht.rowD[r] * dlast + jcol, g[r], a.gacc_in_lds);
+                                    if (ht.rowD[r] >= 0 && jcol < dlast) grad_accum(gWh + (long long)ht.rowD[r] * dlast + jcol, g[r], a.gacc_in_lds);
                             }
                         }
                     }
@@ -701,7 +601,7 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
                     const int N = a.dout[l], K = a.din[l];
                     const float* xin = l == 0 ? x0 : Xp + (l - 1) * DS;
                     if (w != 0.0f) {
-                        if (!dw_reg) vr_dw_acc(gpre, xin, N, K, w, gacc + a.gW_off[l], gacc + a.gb_off[l], tid, wave, lane, a.gacc_in_lds);
+                        if (!dw_reg) dw_acc(gpre, xin, N, K, w, GradRows{gacc + a.gW_off[l], K}, GradRows{gacc + a.gb_off[l], 1}, tid, wave, lane, a.gacc_in_lds);
                         else if (a.gW_off[l] == a.gW_off[0]) vr_dw_acc_reg(gpre, xin, N, K, w, dwA, gacc + a.gb_off[l], tid, wave, lane, a.gacc_in_lds);
                         else vr_dw_acc_reg(gpre, xin, N, K, w, dwB, gacc + a.gb_off[l], tid, wave, lane, a.gacc_in_lds);
                     }
@@ -720,78 +620,69 @@ extern "C" __global__ __launch_bounds__(VR_THREADS) void ncde_adj_variant(KArgs 
                 __syncthreads();
                 if (w != 0.0f) {
                     if (dw_reg) vr_dw_acc_reg(GA, U, d0, d0, w, dwR, gacc + a.gbr_off, tid, wave, lane, a.gacc_in_lds);
-                    else vr_dw_acc(GA, U, d0, d0, w, gacc + a.gWr_off, gacc + a.gbr_off, tid, wave, lane, a.gacc_in_lds);
+                    else dw_acc(GA, U, d0, d0, w, GradRows{gacc + a.gWr_off, d0}, GradRows{gacc + a.gbr_off, 1}, tid, wave, lane, a.gacc_in_lds);
                 }
                 vr_bwd_data(a.Wr, d0, d0, GA, nullptr, DUI, true, wave, lane, wl_r);
                 __syncthreads();
             }
-            // ---- Butcher bookkeeping (KOA = dL/dy of the stage = the first H rows of du) -----------------------------------
+            // ---- Butcher bookkeeping (d = dL/dy of the stage = the first H rows of du).  The text of adj_bookkeep (ncde_timeloop.h), kept
+            // INLINE in this one kernel: behind the helper's call boundary the register allocator leaves a fourth, unused 16 B frame
+            // object and the private segment grows from 68 to 84 B per lane (the kernel sits at the SGPR limit: 240 spills to lanes);
+            // the other two families call the helper.  A change to either text goes into both; tools/family_bits.py compares them.
             for (int e = tid; e < HS; e += VR_THREADS) {
                 const int h = e >> 4, s = e & 15, b = b0 + s;
                 const bool valid = h < H && b < a.B;
                 const float d = h < H ? DUI[e] : 0.0f;
-                if (disc) {
-                    float a0 = A0[e];
-                    bool last = false;
-                    float next = 0.0f;
-                    if (a.method == NCDE_RK4_38) {
-                        const float c4 = (a0 * dt) * 0.125f;
-                        const float dt3 = dt * 0.333333343267440796f;
-                        if (j == 0) { KA1[e] = d; next = 3.0f * c4 + dt * d; }
-                        else if (j == 1) { KA2[e] = d; next = (3.0f * c4 - dt * KA1[e]) + dt * d; }
-                        else if (j == 2) { KY1[e] = d; next = ((c4 + dt * KA1[e]) - dt3 * KA2[e]) + dt3 * d; }
-                        else { a0 = (((a0 + KA1[e]) + KA2[e]) + KY1[e]) + d; last = true; }
-                    } else if (a.method == NCDE_MIDPOINT) {
-                        if (j == 0) { KA1[e] = d; next = (0.5f * dt) * d; }
-                        else { a0 = (a0 + KA1[e]) + d; last = true; }
-                    } else {
-                        a0 = a0 + d; last = true;
-                    }
+                if (walk.disc) {
+                    float a0 = A0[e], ka1 = KA1[e], ka2 = KA2[e], ky1 = KY1[e];
+                    bool last;
+                    float next = StageTranspose::apply(a.method, j, d, st.dt, a0, ka1, ka2, ky1, last);
+                    KA1[e] = ka1; KA2[e] = ka2; KY1[e] = ky1;
                     if (last) {
                         float dtp = 1.0f;
-                        if (planned) {
+                        if (walk.planned) {
                             if (valid) {
                                 const long long brow = (long long)b * a.n_out;
-                                a0 = a0 + plan_out_cotangent(a, pstep, pout, 0, brow, h);
-                                if (m > 0) a0 = a0 + plan_out_cotangent(a, pstep - pw_, pout, 1, brow, h);
+                                a0 = a0 + plan_out_cotangent(a, st.pstep, walk.pout, 0, brow, h);
+                                if (st.m > 0) a0 = a0 + plan_out_cotangent(a, st.pstep - walk.pw_, walk.pout, 1, brow, h);
                                 else a0 = a0 + a.grad_out[brow * H + h];
                             }
-                            if (m > 0) dtp = __int_as_float(pstep[-pw_]);
-                        } else if (a.output == NCDE_OUT_KNOTS || n == 1) {
-                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out + (a.output == NCDE_OUT_KNOTS ? n - 1 : 0)) * H + h] : 0.0f);
+                            if (st.m > 0) dtp = __int_as_float(st.pstep[-walk.pw_]);
+                        } else if (a.output == NCDE_OUT_KNOTS || st.n == 1) {
+                            a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out + (a.output == NCDE_OUT_KNOTS ? st.n - 1 : 0)) * H + h] : 0.0f);
                         }
                         A0[e] = a0;
-                        next = a.method == NCDE_RK4_38 ? (a0 * dtp) * 0.125f : dtp * a0;
-                        if (m == 0 && valid) a.grad_z0[(long long)b * H + h] = a0;
+                        next = StageTranspose::seed(a.method, a0, dtp);
+                        if (st.m == 0 && valid) a.grad_z0[(long long)b * H + h] = a0;
                     }
                     AS[e] = next;
                 } else {
                     float y0 = Y0[e], k1 = KY1[e], k2 = KY2[e];
                     bool last;
-                    const float ys = StageCombine::apply(a.method, j, -KOY[e], dt, y0, k1, k2, last);
+                    const float ys = StageCombine::apply(a.method, j, -KOY[e], st.dt, y0, k1, k2, last);
                     U[e] = ys; KY1[e] = k1; KY2[e] = k2;
                     float a0 = A0[e], q1 = KA1[e], q2 = KA2[e];
-                    const float as = StageCombine::apply(a.method, j, d, dt, a0, q1, q2, last);
+                    const float as = StageCombine::apply(a.method, j, d, st.dt, a0, q1, q2, last);
                     KA1[e] = q1; KA2[e] = q2;
                     if (!last) {
                         AS[e] = as;
                     } else {
-                        if (planned) {
-                            const int row = pstep[1];
+                        if (walk.planned) {
+                            const int row = st.pstep[1];
                             if (row >= 0) {
                                 const long long o = ((long long)b * a.n_out + row) * H + h;
                                 y0 = valid ? a.z_out[o] : 0.0f;
                                 a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
                             }
                         } else if (a.output == NCDE_OUT_KNOTS) {
-                            const long long o = ((long long)b * a.n_out + (n - 1)) * H + h;
+                            const long long o = ((long long)b * a.n_out + (st.n - 1)) * H + h;
                             y0 = valid ? a.z_out[o] : 0.0f;
                             a0 = a0 + (valid ? a.grad_out[o] : 0.0f);
-                        } else if (n == 1) {
+                        } else if (st.n == 1) {
                             a0 = a0 + (valid ? a.grad_out[((long long)b * a.n_out) * H + h] : 0.0f);
                         }
                         Y0[e] = y0; U[e] = y0; A0[e] = a0; AS[e] = a0;
-                        if (rstep == n_rsteps - 1 && valid) a.grad_z0[(long long)b * H + h] = a0;
+                        if (rstep == walk.n_rsteps - 1 && valid) a.grad_z0[(long long)b * H + h] = a0;
                     }
                 }
             }
