@@ -516,6 +516,28 @@ int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p);   /* < 0: sta
 const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p);   /* NULL on error */
 int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream);
 
+/* The stacked step: n_stack chained linear CDE layers (StackedNeuralCDE: layer i + 1 reads layer i's hidden sequence as the linear
+ * coefficients of its control) advance by s[0]->n_rows rows in ONE launch, one workgroup per 16 streams walking the layers of a row.
+ *   layer 0    fills its row from s[0]->x exactly as ncde_stream_step does.
+ *   layer i>0  takes as its new row z of layer i - 1 after that layer's step for this row (a stream's first row: layer i - 1's z as
+ *              the caller set it), so p[i]->channels == p[i - 1]->hidden.  It never passes through global memory.
+ *   per layer  its own problem p[i] (shape, field, method) and its own state s[i]->z / last_row / prev_dx / count; pieces, the
+ *              left-piece rule from the stream's own count, stages and bookkeeping are those of ncde_stream_step.  A first row
+ *              (count == 0) takes no step at any layer: the caller sets z(t0) of EVERY layer beforehand.
+ *   s[0]       carries x and its strides, active, initial_value_if_nan and n_rows for the whole stack; those fields of s[i], i > 0,
+ *              are ignored.  rectilinear must be 0 and every interp NCDE_INTERP_LINEAR.
+ *   readout    Wf / bf / out / n_out and z_out of s[i] are honoured per layer as in the single step; they are optional for inner
+ *              layers, the last layer needs Wf + out or z_out.
+ * NCDE_ERR_INVALID: n_stack outside [1, NCDE_STREAM_MAX_STACK], a NULL entry, p[i]->channels != p[i - 1]->hidden, differing batch,
+ * rectilinear, a non-linear interp.  NCDE_ERR_UNSUPPORTED: what ncde_stream_step refuses at any layer, and a stack whose LDS plan (the
+ * stage scratch of the widest layer + z, last_row, prev_dx, count of every layer) exceeds the limit; the message says the bytes
+ * needed.  A refusal leaves every state buffer untouched.  n_stack == 1 is ncde_stream_step, bit for bit.  The two queries answer as
+ * those of the single step do; the kernel name is "ncde_stream_stack_step". */
+#define NCDE_STREAM_MAX_STACK 4
+int64_t ncde_stream_stack_workspace_bytes(const NcdeProblem* const* p, int n_stack);   /* 0, or < 0: status code */
+const char* ncde_stream_stack_kernel_name(const NcdeProblem* const* p, int n_stack);   /* NULL on error */
+int ncde_stream_stack_step(const NcdeProblem* const* p, const NcdeStream* const* s, int n_stack, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,7 @@ from .solver import FieldSpec, cdeint, coop_status  # noqa: F401
 from .vector_fields import (GRUGatedVectorField, LowRankVectorField, MinimalGatedVectorField, MLPField,  # noqa: F401
                             OriginalVectorField)
 from .ncde import NeuralCDE  # noqa: F401
-from .online import OnlineNeuralCDE  # noqa: F401
+from .online import OnlineNeuralCDE, OnlineStackedNeuralCDE  # noqa: F401
 from .stacked import StackedNeuralCDE  # noqa: F401
 from .coefficients import (forward_fill, hermite_cubic_coefficients_with_backward_differences, linear_interpolation_coeffs,  # noqa: F401
                            linear_rectilinear_hybrid_coeffs, natural_cubic_coeffs, natural_cubic_spline_coeffs)

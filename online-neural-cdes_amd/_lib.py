@@ -8,6 +8,7 @@ import os
 
 NCDE_ABI_VERSION = 4
 NCDE_MAX_LAYERS = 8
+NCDE_STREAM_MAX_STACK = 4
 
 INTERP = {"linear": 0, "cubic": 1, "quintic": 2}
 INTERP_PARTS = {"linear": 1, "cubic": 4, "quintic": 6}      # floats per channel of one coefficient row
@@ -153,6 +154,7 @@ EXPORTS = (
     "ncde_control_workspace_bytes", "ncde_control_kernel_name", "ncde_backward_control",
     "ncde_stream_workspace_bytes", "ncde_stream_kernel_name", "ncde_stream_step",
     "ncde_stream_hermite_workspace_bytes", "ncde_stream_hermite_kernel_name", "ncde_stream_step_hermite",
+    "ncde_stream_stack_workspace_bytes", "ncde_stream_stack_kernel_name", "ncde_stream_stack_step",
 )
 
 _LIB = None
@@ -232,6 +234,13 @@ def lib():
     h.ncde_stream_hermite_kernel_name.restype = ctypes.c_char_p
     h.ncde_stream_step_hermite.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
     h.ncde_stream_step_hermite.restype = ctypes.c_int
+    PP, SS = ctypes.POINTER(P), ctypes.POINTER(ctypes.POINTER(NcdeStream))      # one pointer per layer of the stack
+    h.ncde_stream_stack_workspace_bytes.argtypes = [PP, ctypes.c_int]
+    h.ncde_stream_stack_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_stream_stack_kernel_name.argtypes = [PP, ctypes.c_int]
+    h.ncde_stream_stack_kernel_name.restype = ctypes.c_char_p
+    h.ncde_stream_stack_step.argtypes = [PP, SS, ctypes.c_int, vp]
+    h.ncde_stream_stack_step.restype = ctypes.c_int
     i32 = ctypes.c_int
     h.ncde_prepare_workspace_bytes.argtypes = [i32, i32, i32, i32]
     h.ncde_prepare_workspace_bytes.restype = ctypes.c_int64

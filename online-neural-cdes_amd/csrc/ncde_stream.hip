@@ -17,6 +17,9 @@
 // left piece's end slope at frac = 1 in exact arithmetic --, every later stage the image b + (2c + 3d s) s, rebuilt into the DXB slot
 // (free: no rectilinear form) by the combine phase of the stage before it, under that phase's barrier.  s is per stream: the frac
 // default_stage hands load_dx at the stream's own step index, (n + offset) - n in fp32.
+//
+// The phases are device functions of their own (stream_load_state .. stream_store_state); ncde_stream_stack_step runs them layer by
+// layer for a chain of linear CDEs in one launch (see StreamStackArgs).
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -41,158 +44,274 @@ struct StreamArgs {
     float* z_out;
 };
 
-template <bool HERMITE>
-__device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArgs& q) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * NCDE_TILE;
-    const int H = a.H, C = a.C, Hp = ru16(H), Cp = ru4(C);
-    int Dp = Hp;
+// The LDS of one 16-stream tile.  StreamScratch: what a stage works in -- one set per workgroup, whatever the number of layers.
+// StreamState: what a layer carries from row to row.
+struct StreamScratch {
+    float *YS, *ACT0, *ACT1, *K1, *K2, *KO;
+    float* DXL;      // stage 1 of the first piece: the piece to the left (per stream: the previous one, or its own)
+    float* DXA;      // first piece
+    float* DXB;      // second piece (rectilinear); HERMITE: the stage image
+    int* STEP;       // steps at this row (0: no; else the step's index + 1)
+    int* EVER;       // received a row in this launch
+};
+struct StreamState {
+    float* Y0;
+    float* LAST;     // last filled row
+    float* PDX;      // dX/dt of the last piece taken
+    int* CNT;        // observations received
+};
+
+__device__ __forceinline__ int stream_dp(const KArgs& a) {
+    int Dp = ru16(a.H);
     for (int l = 0; l < a.n_layers; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    const int HS = Hp * 16, DS = Dp * 16, CS = Cp * 16;
-    float* YS = lds;
-    float* ACT0 = YS + HS;
-    float* ACT1 = ACT0 + DS;
-    float* Y0 = ACT1 + DS;
-    float* K1 = Y0 + HS;
-    float* K2 = K1 + HS;
-    float* KO = K2 + HS;
-    float* DXL = KO + HS;        // stage 1 of the first piece: the piece to the left (per stream: the previous one, or its own)
-    float* DXA = DXL + CS;       // first piece
-    float* DXB = DXA + CS;       // second piece (rectilinear); HERMITE: the stage image
-    float* LAST = DXB + CS;      // last filled row
-    float* PDX = LAST + CS;      // dX/dt of the last piece taken
-    int* CNT = (int*)(PDX + CS); // observations received; then: steps at this row (0: no; else the step's index + 1), received a row in this launch
-    int* STEP = CNT + 16;
-    int* EVER = STEP + 16;
-    const int total = 5 * HS + 2 * DS + 5 * CS + 48;
-    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
-    __syncthreads();
-    // 1. load the state
+    return Dp;
+}
+__device__ __forceinline__ int stream_scratch_floats(int HS, int DS, int CS) { return 4 * HS + 2 * DS + 3 * CS + 32; }
+__device__ __forceinline__ int stream_state_floats(const KArgs& a) { return ru16(a.H) * 16 + 2 * ru4(a.C) * 16 + 16; }
+__device__ __forceinline__ float* stream_carve_scratch(float* p, int HS, int DS, int CS, StreamScratch& w) {
+    w.YS = p;
+    w.ACT0 = w.YS + HS;
+    w.ACT1 = w.ACT0 + DS;
+    w.K1 = w.ACT1 + DS;
+    w.K2 = w.K1 + HS;
+    w.KO = w.K2 + HS;
+    w.DXL = w.KO + HS;
+    w.DXA = w.DXL + CS;
+    w.DXB = w.DXA + CS;
+    w.STEP = (int*)(w.DXB + CS);
+    w.EVER = w.STEP + 16;
+    return (float*)(w.EVER + 16);
+}
+__device__ __forceinline__ StreamState stream_carve_state(float* p, const KArgs& a) {
+    StreamState t;
+    t.Y0 = p;
+    t.LAST = t.Y0 + ru16(a.H) * 16;
+    t.PDX = t.LAST + ru4(a.C) * 16;
+    t.CNT = (int*)(t.PDX + ru4(a.C) * 16);
+    return t;
+}
+
+// 1. load a layer's state (YS != NULL: z is the first stage input as well)
+__device__ __forceinline__ void stream_load_state(const KArgs& a, const StreamArgs& q, const StreamState& t, float* YS, int b0, int tid) {
+    const int H = a.H, C = a.C, HS = ru16(H) * 16, Cp = ru4(C);
     for (int e = tid; e < HS; e += GEN_THREADS) {
         const int h = e >> 4, s = e & 15, b = b0 + s;
         if (h < H && b < a.B) {
             const float v = q.z[(long long)b * H + h];
-            Y0[e] = v;
-            YS[e] = v;
+            t.Y0[e] = v;
+            if (YS) YS[e] = v;
         }
     }
     for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
         const int s = e / Cp, c = e - s * Cp, b = b0 + s;
         if (c < C && b < a.B) {
-            LAST[c * 16 + s] = q.last[(long long)b * C + c];
-            PDX[c * 16 + s] = q.pdx[(long long)b * C + c];
+            t.LAST[c * 16 + s] = q.last[(long long)b * C + c];
+            t.PDX[c * 16 + s] = q.pdx[(long long)b * C + c];
         }
     }
-    if (tid < 16 && b0 + tid < a.B) CNT[tid] = q.count[b0 + tid];
-    __syncthreads();
-    const int S = n_stages(a.method);
-    const int n_pieces = q.rect ? 2 : 1;
-    for (int r = 0; r < q.m; ++r) {
-        // 2. fill the new row, 3. the pieces' dX/dt
-        for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
-            const int s = e / Cp, c = e - s * Cp, b = b0 + s;
-            float dl = 0.0f, da = 0.0f, db = 0.0f;
-            if (c < C && b < a.B && (!q.active || q.active[(long long)r * a.B + b])) {
-                const int cnt = CNT[s];
-                const float xv = q.x[(long long)r * q.xs_m + (long long)b * q.xs_b + c];
-                const float last = LAST[c * 16 + s];
-                const float fill = xv != xv ? (cnt == 0 ? q.init : last) : xv;
-                if (cnt > 0) {
-                    const float mid = (q.rect && c != q.ti) ? last : fill;      // rectilinear: the lagged row (new time, old values)
-                    da = mid - last;
-                    db = fill - mid;
-                    dl = cnt == 1 ? da : PDX[c * 16 + s];
-                    PDX[c * 16 + s] = q.rect ? db : da;
-                }
-                LAST[c * 16 + s] = fill;
+    if (tid < 16 && b0 + tid < a.B) t.CNT[tid] = q.count[b0 + tid];
+}
+
+// 2. fill row r, 3. the pieces' dX/dt; then the row's bookkeeping.  from: the row as a [c][s] image in LDS (the layer below of a
+// stack: its Y0 after its step for this row), NULL: row r of q.x.  Returns whether any stream of the tile steps (uniform: every
+// thread reads the same 16 flags).  Ends behind a barrier.
+__device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, const float* from,
+                                               int r, int b0, int tid) {
+    const int C = a.C, Cp = ru4(C);
+    for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
+        const int s = e / Cp, c = e - s * Cp, b = b0 + s;
+        float dl = 0.0f, da = 0.0f, db = 0.0f;
+        if (c < C && b < a.B && (!q.active || q.active[(long long)r * a.B + b])) {
+            const int cnt = t.CNT[s];
+            const float xv = from ? from[c * 16 + s] : q.x[(long long)r * q.xs_m + (long long)b * q.xs_b + c];
+            const float last = t.LAST[c * 16 + s];
+            const float fill = xv != xv ? (cnt == 0 ? q.init : last) : xv;
+            if (cnt > 0) {
+                const float mid = (q.rect && c != q.ti) ? last : fill;      // rectilinear: the lagged row (new time, old values)
+                da = mid - last;
+                db = fill - mid;
+                dl = cnt == 1 ? da : t.PDX[c * 16 + s];
+                t.PDX[c * 16 + s] = q.rect ? db : da;
             }
-            DXL[c * 16 + s] = dl;
-            DXA[c * 16 + s] = da;
-            DXB[c * 16 + s] = db;
+            t.LAST[c * 16 + s] = fill;
         }
-        __syncthreads();
-        if (tid < 16) {
-            const int b = b0 + tid;
-            const int act = b < a.B && (!q.active || q.active[(long long)r * a.B + b]);
-            STEP[tid] = act ? CNT[tid] : 0;       // the first row of a stream (count 0) initialises it: no solver step
-            CNT[tid] += act;
-            EVER[tid] |= act;
-        }
-        __syncthreads();
-        int any_step = 0;      // (uniform: every thread reads the same 16 flags)
+        w.DXL[c * 16 + s] = dl;
+        w.DXA[c * 16 + s] = da;
+        w.DXB[c * 16 + s] = db;
+    }
+    __syncthreads();
+    if (tid < 16) {
+        const int b = b0 + tid;
+        const int act = b < a.B && (!q.active || q.active[(long long)r * a.B + b]);
+        w.STEP[tid] = act ? t.CNT[tid] : 0;       // the first row of a stream (count 0) initialises it: no solver step
+        t.CNT[tid] += act;
+        w.EVER[tid] |= act;
+    }
+    __syncthreads();
+    int any_step = 0;
 #pragma unroll
-        for (int s = 0; s < 16; ++s) any_step |= STEP[s];
-        // 4. the Butcher stages, one step per piece
-        if (any_step) {
-            for (int pc = 0; pc < n_pieces; ++pc) {
-                const float* dx_own = (HERMITE || pc != 0) ? DXB : DXA;
-                const float* dx_left = pc == 0 ? DXL : DXA;
-                for (int j = 0; j < S; ++j) {
-                    gen_stage_forward(a, YS, ACT0, ACT1, j == 0 ? dx_left : dx_own, KO, Hp, Cp, tid);
-                    for (int e = tid; e < HS; e += GEN_THREADS) {
-                        if (!STEP[e & 15]) continue;
-                        float y0 = Y0[e], k1 = K1[e], k2 = K2[e];
-                        bool last;
-                        const float ys = StageCombine::apply(a.method, j, KO[e], 1.0f, y0, k1, k2, last);
-                        YS[e] = ys;
-                        K1[e] = k1;
-                        K2[e] = k2;
-                        if (last) Y0[e] = y0;
+    for (int s = 0; s < 16; ++s) any_step |= w.STEP[s];
+    return any_step;
+}
+
+// 4. the Butcher stages, one step per piece
+template <bool HERMITE>
+__device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid) {
+    const int Hp = ru16(a.H), Cp = ru4(a.C), HS = Hp * 16, CS = Cp * 16;
+    const int S = n_stages(a.method);
+    for (int pc = 0; pc < n_pieces; ++pc) {
+        const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
+        const float* dx_left = pc == 0 ? w.DXL : w.DXA;
+        for (int j = 0; j < S; ++j) {
+            gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, j == 0 ? dx_left : dx_own, w.KO, Hp, Cp, tid);
+            for (int e = tid; e < HS; e += GEN_THREADS) {
+                if (!w.STEP[e & 15]) continue;
+                float y0 = t.Y0[e], k1 = w.K1[e], k2 = w.K2[e];
+                bool last;
+                const float ys = StageCombine::apply(a.method, j, w.KO[e], 1.0f, y0, k1, k2, last);
+                w.YS[e] = ys;
+                w.K1[e] = k1;
+                w.K2[e] = k2;
+                if (last) t.Y0[e] = y0;
+            }
+            if constexpr (HERMITE) {
+                if (j + 1 < S) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
+                    for (int e = tid; e < CS; e += GEN_THREADS) {
+                        const float frac = default_stage(a.method, (float)(w.STEP[e & 15] - 1) + stage_offset(a.method, j + 1), 0x7fffffff).frac;
+                        const float bb = w.DXL[e], dn = w.DXA[e];
+                        const float two_c = 2.0f * (3.0f * (dn - bb) - dn + bb);
+                        const float three_d = (dn - bb) - two_c;
+                        const float inner = two_c + three_d * frac;
+                        w.DXB[e] = bb + inner * frac;
                     }
-                    if constexpr (HERMITE) {
-                        if (j + 1 < S) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
-                            for (int e = tid; e < CS; e += GEN_THREADS) {
-                                const float frac = default_stage(a.method, (float)(STEP[e & 15] - 1) + stage_offset(a.method, j + 1), 0x7fffffff).frac;
-                                const float bb = DXL[e], dn = DXA[e];
-                                const float two_c = 2.0f * (3.0f * (dn - bb) - dn + bb);
-                                const float three_d = (dn - bb) - two_c;
-                                const float inner = two_c + three_d * frac;
-                                DXB[e] = bb + inner * frac;
-                            }
-                        }
-                    }
-                    __syncthreads();
                 }
             }
+            __syncthreads();
         }
-        // 5. readout of every stream of the tile (a stream without a row: of its unchanged z)
-        if (q.Wf) {
-            for (int e = tid; e < 16 * q.n_out; e += GEN_THREADS) {
-                const int s = e / q.n_out, o = e - s * q.n_out, b = b0 + s;
-                if (b < a.B) {
-                    const float* w = q.Wf + (long long)o * H;
-                    float acc = q.bf ? q.bf[o] : 0.0f;
-                    for (int h = 0; h < H; ++h) acc = fmaf(w[h], Y0[h * 16 + s], acc);
-                    q.out[((long long)r * a.B + b) * q.n_out + o] = acc;
-                }
-            }
-        }
-        if (q.z_out) {
-            for (int e = tid; e < 16 * H; e += GEN_THREADS) {
-                const int s = e / H, h = e - s * H, b = b0 + s;
-                if (b < a.B) q.z_out[((long long)r * a.B + b) * H + h] = Y0[h * 16 + s];
+    }
+}
+
+// 5. readout of every stream of the tile at row r (a stream without a row: of its unchanged z)
+__device__ __forceinline__ void stream_readout(const KArgs& a, const StreamArgs& q, const StreamState& t, int r, int b0, int tid) {
+    const int H = a.H;
+    if (q.Wf) {
+        for (int e = tid; e < 16 * q.n_out; e += GEN_THREADS) {
+            const int s = e / q.n_out, o = e - s * q.n_out, b = b0 + s;
+            if (b < a.B) {
+                const float* wf = q.Wf + (long long)o * H;
+                float acc = q.bf ? q.bf[o] : 0.0f;
+                for (int h = 0; h < H; ++h) acc = fmaf(wf[h], t.Y0[h * 16 + s], acc);
+                q.out[((long long)r * a.B + b) * q.n_out + o] = acc;
             }
         }
     }
-    __syncthreads();
-    // 6. write the state back: only the streams that received a row
+    if (q.z_out) {
+        for (int e = tid; e < 16 * H; e += GEN_THREADS) {
+            const int s = e / H, h = e - s * H, b = b0 + s;
+            if (b < a.B) q.z_out[((long long)r * a.B + b) * H + h] = t.Y0[h * 16 + s];
+        }
+    }
+}
+
+// 6. write a layer's state back: only the streams that received a row
+__device__ __forceinline__ void stream_store_state(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, int b0, int tid) {
+    const int H = a.H, C = a.C, Cp = ru4(C);
     for (int e = tid; e < 16 * H; e += GEN_THREADS) {
         const int s = e / H, h = e - s * H, b = b0 + s;
-        if (b < a.B && EVER[s]) q.z[(long long)b * H + h] = Y0[h * 16 + s];
+        if (b < a.B && w.EVER[s]) q.z[(long long)b * H + h] = t.Y0[h * 16 + s];
     }
     for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
         const int s = e / Cp, c = e - s * Cp, b = b0 + s;
-        if (c < C && b < a.B && EVER[s]) {
-            q.last[(long long)b * C + c] = LAST[c * 16 + s];
-            q.pdx[(long long)b * C + c] = PDX[c * 16 + s];
+        if (c < C && b < a.B && w.EVER[s]) {
+            q.last[(long long)b * C + c] = t.LAST[c * 16 + s];
+            q.pdx[(long long)b * C + c] = t.PDX[c * 16 + s];
         }
     }
-    if (tid < 16 && b0 + tid < a.B && EVER[tid]) q.count[b0 + tid] = CNT[tid];
+    if (tid < 16 && b0 + tid < a.B && w.EVER[tid]) q.count[b0 + tid] = t.CNT[tid];
+}
+
+template <bool HERMITE>
+__device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArgs& q) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
+    StreamScratch w;
+    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w), a);
+    const int total = stream_scratch_floats(HS, DS, CS) + stream_state_floats(a);
+    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
+    __syncthreads();
+    stream_load_state(a, q, t, w.YS, b0, tid);
+    __syncthreads();
+    for (int r = 0; r < q.m; ++r) {
+        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid);
+        stream_readout(a, q, t, r, b0, tid);
+    }
+    __syncthreads();
+    stream_store_state(a, q, w, t, b0, tid);
 }
 
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) { stream_step_body<false>(a, q); }
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hermite_kernel(KArgs a, StreamArgs q) { stream_step_body<true>(a, q); }
+
+// The stacked step (ncde_stream_stack_step): n_stack chained linear layers, layer l + 1 reading layer l's hidden state as its
+// observation.  Everything a layer reads of the one below is per stream, so the tile's workgroup walks the layers of a row with
+// barriers only: layer l's new row is the Y0 image of layer l - 1 after that layer's step for this row -- [h][s] there, [c][s]
+// here, the same image.  Layer 0's q carries the rows, the mask and the fill value; the host copies m / active / init into
+// every layer's q.  The scratch is shared and sized by the widest layer, the state is per layer.
+//
+// Narrow after wide, wide after narrow: nothing is re-zeroed between layers, because every scratch element a layer READS it has
+// WRITTEN itself since the previous layer left: YS rows < Hp from its own Y0 (whose pad rows and pad samples are zero from the
+// launch's clear and stay zero: KO's pad rows are sums of tanh(0) = 0 terms); DXL / DXA / DXB all 16 Cp entries by its fill
+// phase, zeros where c >= C or the sample is beyond B; ACT0 / ACT1 rows < ru16(dout) by dense_relu before the next layer of the
+// field reads rows < ru4(dout) of them; KO rows < Hp by every stage; K1 / K2 by stage 1 / 2 of a step before stage 2 / 3 reads
+// them (midpoint and euler carry them through without using them).  Rows beyond its own extents a layer does not read.
+struct StreamStackArgs {
+    int n_stack;
+    KArgs a[NCDE_STREAM_MAX_STACK];
+    StreamArgs q[NCDE_STREAM_MAX_STACK];
+};
+static_assert(sizeof(StreamStackArgs) <= 4096, "the stacked step passes every layer's arguments by value: HIP's kernel arguments end at 4 KiB");
+
+__device__ __forceinline__ StreamState stream_stack_state(const StreamStackArgs& k, float* states, int l) {
+    for (int i = 0; i < l; ++i) states += stream_state_floats(k.a[i]);
+    return stream_carve_state(states, k.a[l]);
+}
+
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_stack_step_kernel(StreamStackArgs k) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const int L = k.n_stack;
+    int HS = 0, DS = 0, CS = 0, total = 0;
+    for (int l = 0; l < L; ++l) {
+        HS = max(HS, ru16(k.a[l].H) * 16);
+        DS = max(DS, stream_dp(k.a[l]) * 16);
+        CS = max(CS, ru4(k.a[l].C) * 16);
+        total += stream_state_floats(k.a[l]);
+    }
+    total += stream_scratch_floats(HS, DS, CS);
+    StreamScratch w;
+    float* states = stream_carve_scratch(lds, HS, DS, CS, w);
+    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
+    __syncthreads();
+    for (int l = 0; l < L; ++l) stream_load_state(k.a[l], k.q[l], stream_stack_state(k, states, l), nullptr, b0, tid);
+    __syncthreads();
+    for (int r = 0; r < k.q[0].m; ++r) {
+        const float* below = nullptr;
+        for (int l = 0; l < L; ++l) {
+            const KArgs& a = k.a[l];
+            const StreamState t = stream_stack_state(k, states, l);
+            // the stage input of this layer (the last readers of YS, the layer before, ended behind a barrier; readers start behind fill's)
+            for (int e = tid; e < ru16(a.H) * 16; e += GEN_THREADS) w.YS[e] = t.Y0[e];
+            if (stream_fill_row(a, k.q[l], w, t, below, r, b0, tid)) stream_stages<false>(a, w, t, 1, tid);
+            stream_readout(a, k.q[l], t, r, b0, tid);
+            below = t.Y0;
+        }
+    }
+    __syncthreads();
+    for (int l = 0; l < L; ++l) stream_store_state(k.a[l], k.q[l], w, stream_stack_state(k, states, l), b0, tid);
+}
 
 namespace {
 
@@ -312,3 +431,87 @@ extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) {
 }
 
 extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, true); }
+
+// ---- the stacked step ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Every layer as stream_problem reads it, the chain between the layers and the LDS plan of the whole stack.
+int stream_stack_problems(const NcdeProblem* const* p, int n_stack, NcdeProblem* q, Layout* y, size_t* lds) {
+    if (n_stack < 1 || n_stack > NCDE_STREAM_MAX_STACK) return sfail(NCDE_ERR_INVALID, "n_stack %d outside [1, %d]", n_stack, NCDE_STREAM_MAX_STACK);
+    if (!p) return sfail(NCDE_ERR_INVALID, "the list of problems is NULL");
+    for (int i = 0; i < n_stack; ++i)
+        if (!p[i]) return sfail(NCDE_ERR_INVALID, "stacked online step: problem %d is NULL", i);
+    int HS = 0, DS = 0, CS = 0;
+    size_t states = 0;
+    for (int i = 0; i < n_stack; ++i) {
+        size_t own;
+        const int rc = stream_problem(p[i], &q[i], &y[i], &own);
+        if (rc != NCDE_OK) return rc;
+        if (i > 0 && q[i].channels != q[i - 1].hidden)
+            return sfail(NCDE_ERR_INVALID, "stacked online step: layer %d reads %d channels, layer %d has %d hidden units", i, q[i].channels, i - 1, q[i - 1].hidden);
+        if (q[i].batch != q[0].batch) return sfail(NCDE_ERR_INVALID, "stacked online step: layer %d has batch %d, layer 0 has %d", i, q[i].batch, q[0].batch);
+        HS = std::max(HS, y[i].HS);
+        DS = std::max(DS, y[i].DS);
+        CS = std::max(CS, y[i].Cp * 16);
+        states += (size_t)(y[i].HS + 2 * y[i].Cp * 16 + 16);
+    }
+    *lds = sizeof(float) * ((size_t)(4 * HS + 2 * DS + 3 * CS + 32) + states);
+    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "stacked online step of %d layers needs %zu B of LDS (> %d)", n_stack, *lds, kLdsLimit);
+    return NCDE_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t ncde_stream_stack_workspace_bytes(const NcdeProblem* const* p, int n_stack) {
+    NcdeProblem q[NCDE_STREAM_MAX_STACK];
+    Layout y[NCDE_STREAM_MAX_STACK];
+    size_t lds;
+    const int rc = stream_stack_problems(p, n_stack, q, y, &lds);
+    return rc == NCDE_OK ? 0 : rc;
+}
+
+extern "C" const char* ncde_stream_stack_kernel_name(const NcdeProblem* const* p, int n_stack) {
+    NcdeProblem q[NCDE_STREAM_MAX_STACK];
+    Layout y[NCDE_STREAM_MAX_STACK];
+    size_t lds;
+    return stream_stack_problems(p, n_stack, q, y, &lds) == NCDE_OK ? "ncde_stream_stack_step" : nullptr;
+}
+
+extern "C" int ncde_stream_stack_step(const NcdeProblem* const* p, const NcdeStream* const* s, int n_stack, void* stream) {
+    NcdeProblem q[NCDE_STREAM_MAX_STACK];
+    Layout y[NCDE_STREAM_MAX_STACK];
+    size_t lds;
+    const int rc = stream_stack_problems(p, n_stack, q, y, &lds);
+    if (rc != NCDE_OK) return rc;
+    if (!s) return sfail(NCDE_ERR_INVALID, "the list of streams is NULL");
+    for (int i = 0; i < n_stack; ++i)
+        if (!s[i]) return sfail(NCDE_ERR_INVALID, "stacked online step: stream %d is NULL", i);
+    const NcdeStream* s0 = s[0];
+    if (s0->n_rows < 1) return sfail(NCDE_ERR_INVALID, "n_rows %d: at least one new row", s0->n_rows);
+    if (s0->rectilinear) return sfail(NCDE_ERR_INVALID, "stacked online step: rectilinear must be 0 (a layer's hidden sequence is a linear path)");
+    if (!s0->x) return sfail(NCDE_ERR_INVALID, "NULL x");
+    if (s0->x_stride_b < q[0].channels || s0->x_stride_m < 0)
+        return sfail(NCDE_ERR_INVALID, "x strides (%lld, %lld): rows of %d channels", (long long)s0->x_stride_m, (long long)s0->x_stride_b, q[0].channels);
+    StreamStackArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_stack = n_stack;
+    for (int i = 0; i < n_stack; ++i) {
+        const NcdeStream* si = s[i];
+        if (!si->z || !si->last_row || !si->prev_dx || !si->count) return sfail(NCDE_ERR_INVALID, "layer %d: NULL z / last_row / prev_dx / count", i);
+        const bool last = i == n_stack - 1;
+        if (si->Wf ? (si->n_out < 1 || !si->out) : (last && !si->z_out))
+            return sfail(NCDE_ERR_INVALID, "layer %d readout: Wf needs n_out >= 1 and out; the last layer without Wf needs z_out", i);
+        fill_kargs(&q[i], y[i], &k.a[i]);
+        StreamArgs& t = k.q[i];
+        t.m = s0->n_rows; t.rect = 0; t.ti = 0; t.n_out = si->Wf ? si->n_out : 0;
+        t.x = s0->x; t.xs_m = s0->x_stride_m; t.xs_b = s0->x_stride_b;
+        t.active = s0->active; t.init = s0->initial_value_if_nan;
+        t.z = si->z; t.last = si->last_row; t.pdx = si->prev_dx; t.count = si->count;
+        t.Wf = si->Wf; t.bf = si->bf; t.out = si->out; t.z_out = si->z_out;
+    }
+    if (ncde_lds_optin((const void*)ncde_stream_stack_step_kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
+    hipLaunchKernelGGL(ncde_stream_stack_step_kernel, dim3(y[0].n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, k);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "ncde_stream_stack_step launch failed: %s", hipGetErrorString(e));
+    return NCDE_OK;
+}

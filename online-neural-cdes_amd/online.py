@@ -97,12 +97,8 @@ class OnlineNeuralCDE:
                 getattr(self, k).copy_(state[k])
         self._may_init = True
 
-    # ---- one call ------------------------------------------------------------------------------------------------------------
-    def step(self, x_new, static=None, active=None):
-        """x_new [B, C] or [m, B, C] (NaN = not observed; the time channel is never NaN) -> [B, out] or [m, B, out] (the hidden
-        state with apply_final_linear=False).  static [B, static_dim]: read while a stream may still receive its first row.
-        active [B] or [m, B] (bool / uint8): which streams received the row; the others keep their state untouched and answer
-        the readout of their unchanged z."""
+    def _check_step(self, x_new, static, active):
+        """The arguments of step() as the advance routines take them: (x [m, B, C], act [m, B] uint8 or None, whether x_new was one row)."""
         m_ = self.model
         B, C = self.batch_size, m_.input_dim
         if not torch.is_tensor(x_new) or x_new.dim() not in (2, 3) or tuple(x_new.shape[-2:]) != (B, C):
@@ -127,6 +123,16 @@ class OnlineNeuralCDE:
         if m_.static_dim and self._may_init:
             if static is None or tuple(static.shape) != (B, m_.static_dim):
                 raise ValueError("static must be [%d, %d] while a stream may still receive its first row" % (B, m_.static_dim))
+        return x, act, single
+
+    # ---- one call ------------------------------------------------------------------------------------------------------------
+    def step(self, x_new, static=None, active=None):
+        """x_new [B, C] or [m, B, C] (NaN = not observed; the time channel is never NaN) -> [B, out] or [m, B, out] (the hidden
+        state with apply_final_linear=False).  static [B, static_dim]: read while a stream may still receive its first row.
+        active [B] or [m, B] (bool / uint8): which streams received the row; the others keep their state untouched and answer
+        the readout of their unchanged z."""
+        x, act, single = self._check_step(x_new, static, active)
+        m = x.size(0)
         with torch.no_grad():
             advance = self._advance_kernel if self._use_kernel(x) else self._advance_torch
             outs, r = [], 0
@@ -253,27 +259,146 @@ class OnlineNeuralCDE:
         self._route[key] = reason is None
         return reason is None
 
-    def _advance_kernel(self, x, act):
+    def _stream_args(self, x, act, m, readout=True):
+        """NcdeStream of this handle's state, the rows x [m, B, C] (act [m, B] uint8 or None) and the readout -> (struct, the output
+        tensor it writes, the tensors its pointers must outlive).  An inner layer of a stack: x None, and readout=False (the state only)."""
         m_ = self.model
-        if x.stride(2) != 1 or x.stride(1) < m_.input_dim or x.stride(0) < 0:      # what the ABI takes: unit channels, rows that do not overlap
-            x = x.contiguous()                                                       # (an expand()ed batch has stride 0: copied)
-        m, B, H = x.size(0), self.batch_size, m_.hidden_dim
-        p = self._problem()
+        B, H = self.batch_size, m_.hidden_dim
         s = _lib.NcdeStream()
         s.n_rows, s.rectilinear, s.time_index = m, int(self.rectilinear), self.time_index
-        s.x, s.x_stride_m, s.x_stride_b = x.data_ptr(), x.stride(0), x.stride(1)
+        if x is not None:
+            if x.stride(2) != 1 or x.stride(1) < m_.input_dim or x.stride(0) < 0:      # what the ABI takes: unit channels, rows that do not overlap
+                x = x.contiguous()                                                       # (an expand()ed batch has stride 0: copied)
+            s.x, s.x_stride_m, s.x_stride_b = x.data_ptr(), x.stride(0), x.stride(1)
         s.active = None if act is None else act.data_ptr()
         s.initial_value_if_nan = self.initial_value_if_nan
         s.z, s.last_row, s.prev_dx, s.count = self.z.data_ptr(), self.last_row.data_ptr(), self.prev_dx.data_ptr(), self.count.data_ptr()
-        if m_.apply_final_linear:
+        out = None
+        if readout and m_.apply_final_linear:
             fl = m_.final_linear
-            out = torch.empty(m, B, fl.out_features, dtype=torch.float32, device=x.device)
+            out = torch.empty(m, B, fl.out_features, dtype=torch.float32, device=self.z.device)
             s.n_out, s.Wf, s.bf, s.out = fl.out_features, fl.weight.data_ptr(), (None if fl.bias is None else fl.bias.data_ptr()), out.data_ptr()
-        else:
-            out = torch.empty(m, B, H, dtype=torch.float32, device=x.device)
+        elif readout:
+            out = torch.empty(m, B, H, dtype=torch.float32, device=self.z.device)
             s.z_out = out.data_ptr()
+        return s, out, (x, act)
+
+    def _advance_kernel(self, x, act):
+        p = self._problem()
+        s, out, keep = self._stream_args(x, act, x.size(0))
         with torch.cuda.device(x.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             entry = "ncde_stream_step_hermite" if self.hermite else "ncde_stream_step"
             _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(p), ctypes.byref(s), stream), entry)
         return out
+
+
+class OnlineStackedNeuralCDE:
+    """``StackedNeuralCDE.online(batch_size)``: what ``StackedNeuralCDE(return_sequences=True)`` on the whole prefix gives at the newest
+    knot, carried forward.  ``layers[i]`` is the ``OnlineNeuralCDE`` of ``ncdes[i]`` and owns that layer's state; layer i + 1 reads
+    layer i's hidden state as its observation.  By default the layer handles' own ``step`` are chained, each on its own route (one
+    launch of ``ncde_stream_step`` per layer on the GPU): measured, that is the faster form, because the host prepares layer i + 1's
+    launch while layer i's kernel runs ("Stacked step").  ``one_launch=True`` asks for ONE launch of
+    ``ncde_stream_stack_step`` for all layers where it applies (CUDA fp32, every layer's field fused, a stack the query accepts), bit
+    for bit the chain's results.  ``fused`` says which route the last step took (None before the first)."""
+
+    def __init__(self, model, batch_size, initial_value_if_nan=0.0, one_launch=False):
+        self.model = model
+        self.one_launch = bool(one_launch)
+        self.layers = [OnlineNeuralCDE(ncde, batch_size, initial_value_if_nan=initial_value_if_nan) for ncde in model.ncdes]
+        self.batch_size = self.layers[0].batch_size
+        self.fused = None
+        self._route = {}
+
+    @property
+    def _may_init(self):
+        return any(lay._may_init for lay in self.layers)
+
+    # ---- state ---------------------------------------------------------------------------------------------------------------
+    def reset(self, mask=None):
+        for lay in self.layers:
+            lay.reset(mask)
+
+    def state_dict(self):
+        return {"layers.%d.%s" % (i, k): v for i, lay in enumerate(self.layers) for k, v in lay.state_dict().items()}
+
+    def load_state_dict(self, state):
+        per_layer = []
+        for i, lay in enumerate(self.layers):
+            for k in STATE_KEYS:
+                if "layers.%d.%s" % (i, k) not in state:
+                    raise ValueError("state_dict lacks 'layers.%d.%s'" % (i, k))
+            per_layer.append({k: state["layers.%d.%s" % (i, k)] for k in STATE_KEYS})
+            for k in STATE_KEYS:      # every shape before any layer is written
+                if tuple(per_layer[i][k].shape) != tuple(getattr(lay, k).shape):
+                    raise ValueError("state 'layers.%d.%s' must be %s, got %s" % (i, k, tuple(getattr(lay, k).shape), tuple(per_layer[i][k].shape)))
+        for lay, st in zip(self.layers, per_layer):
+            lay.load_state_dict(st)
+
+    # ---- one call ------------------------------------------------------------------------------------------------------------
+    def _static_of(self, i, static):
+        return static if self.layers[i].model.static_dim else None
+
+    def step(self, x_new, static=None, active=None):
+        """The contract of OnlineNeuralCDE.step: x_new [B, C] or [m, B, C] -> [B, output_dim] or [m, B, output_dim], the last
+        layer's final_linear as StackedNeuralCDE.forward returns it.  static goes to layer 0, and to the inner layers with
+        static_in_all_layers; active governs every layer."""
+        x, act, single = self.layers[0]._check_step(x_new, static, active)
+        if self.model.static_in_all_layers and self.model.static_dim and self._may_init and static is None:
+            raise ValueError("static must be [%d, %d] while a stream may still receive its first row" % (self.batch_size, self.model.static_dim))
+        self.fused = self._use_kernel(x)
+        if not self.fused:      # the chain: every layer steps on its own route
+            h = x
+            for i, lay in enumerate(self.layers):
+                h = lay.step(h, static=self._static_of(i, static), active=act)
+            return h[0] if single else h
+        m = x.size(0)
+        with torch.no_grad():
+            outs, r = [], 0
+            while self._may_init and r < m:      # rows that may be a stream's first: z(t0) of every layer, layer i from layer i - 1's
+                ar = None if act is None else act[r]
+                h = x[r]
+                for i, lay in enumerate(self.layers):
+                    lay._start(h, self._static_of(i, static), ar)
+                    h = lay.z
+                outs.append(self._advance_kernel(x[r:r + 1], None if act is None else act[r:r + 1]))
+                if act is None:
+                    for lay in self.layers:
+                        lay._may_init = False
+                r += 1
+            if r < m:
+                outs.append(self._advance_kernel(x[r:], None if act is None else act[r:]))
+            out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return out[0] if single else out
+
+    def _problems(self):
+        ps = [lay._problem() for lay in self.layers]
+        return ps, (ctypes.POINTER(_lib.NcdeProblem) * len(ps))(*[ctypes.pointer(p) for p in ps])
+
+    def _use_kernel(self, x):
+        """one_launch, CUDA fp32 and a stack ncde_stream_stack_workspace_bytes accepts take the one launch.  Anything else takes the
+        chain without a warning of its own: each layer handle then picks, and announces, its own route."""
+        if not self.one_launch:
+            return False
+        key = (x.device.type, x.dtype)
+        if key not in self._route:
+            ok = x.is_cuda and x.dtype == torch.float32 and all(hasattr(lay.model.func, "fused_spec") for lay in self.layers)
+            if ok:
+                ps, arr = self._problems()
+                rc = _lib.lib().ncde_stream_stack_workspace_bytes(arr, len(ps))
+                if rc == -2:
+                    ok = False
+                else:
+                    _lib.check(rc, "ncde_stream_stack_workspace_bytes")
+            self._route[key] = ok
+        return self._route[key]
+
+    def _advance_kernel(self, x, act):
+        ps, parr = self._problems()
+        n = len(self.layers)
+        args = [lay._stream_args(x if i == 0 else None, act, x.size(0), readout=i == n - 1) for i, lay in enumerate(self.layers)]
+        sarr = (ctypes.POINTER(_lib.NcdeStream) * n)(*[ctypes.pointer(a[0]) for a in args])
+        with torch.cuda.device(x.device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            _lib.check(_lib.lib().ncde_stream_stack_step(parr, sarr, n, stream), "ncde_stream_stack_step")
+        return args[-1][1]

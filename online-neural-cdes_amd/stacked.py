@@ -46,6 +46,14 @@ class StackedNeuralCDE(nn.Module):
             return hidden_state
         return [x[0], hidden_state]
 
+    def online(self, batch_size, *, initial_value_if_nan=0.0, one_launch=False):
+        """A handle that carries every layer's state of ``batch_size`` streams from one observation to the next (online.py):
+        ``step(x_new)`` answers what ``return_sequences=True`` on the whole prefix gives at the newest knot.  Over this module's own
+        parameters (no copies).  one_launch=True: all layers in one launch of ncde_stream_stack_step instead of one launch per layer
+        (the same bits; measured slower per call, hence not the default)."""
+        from .online import OnlineStackedNeuralCDE
+        return OnlineStackedNeuralCDE(self, batch_size, initial_value_if_nan=initial_value_if_nan, one_launch=one_launch)
+
     def forward(self, x):
         hidden_state = self.ncdes[0](x)
         for ncde in self.ncdes[1:]:
