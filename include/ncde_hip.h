@@ -516,6 +516,26 @@ int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p);   /* < 0: sta
 const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p);   /* NULL on error */
 int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream);
 
+/* The field step: the same step, same structs and same state for five further (field, input) pairs on linear and rectilinear
+ * streams, with euler, midpoint or rk4 -- NCDE_FIELD_ORIGINAL with the evaluate / derivative input, NCDE_FIELD_MINIMAL with the
+ * matmul / evaluate / derivative input.  The problem carries field_kind, field_input, Wg / bg for the gate, and for the direct
+ * inputs a layer chain that starts at d0 = hidden + channels (layer_in[0], or the columns of Wo / Wg when n_layers == 0).
+ *   matmul, derivative   the control input of a stage is the dX/dt of the left-piece rule above.
+ *   evaluate             X at the stage time: stage 1 reads the row at the piece's first knot itself (the stream's last row before
+ *                        this fill; the lagged row for the second rectilinear piece), stage j > 1 that row + frac_j * the piece's own
+ *                        dX/dt, frac_j = (n + offset_j) - n in fp32 at the stream's own step index n = count - 1 (linear),
+ *                        2 (count - 1) and 2 (count - 1) + 1 (rectilinear) -- the batch kernels' arithmetic.
+ * Every weight is streamed from L2; results agree with a batch solve to rounding, not bit for bit (a batch solve that keeps
+ * weights resident in LDS sums in another order).  NCDE_ERR_INVALID: what ncde_stream_step answers it for (a non-linear interp
+ * among it), a NULL Wg / bg on a gated field, a layer chain that does not start at d0.  NCDE_ERR_UNSUPPORTED, each with a message:
+ * the GRU-gated field, the low-rank field, the original field with the matmul input (ncde_stream_step's) and a shape whose LDS
+ * plan, 4 (3 DS + 4 HS + 7 CS + 48) bytes with HS = 16 ru16(hidden), DS = 16 max(ru16(d0), ru16(hidden), ru16(layer widths)),
+ * CS = 16 ru4(channels), exceeds 160 KiB (the message carries the bytes).  A refusal launches nothing and leaves every state
+ * buffer untouched.  The kernel name is "ncde_stream_step_field". */
+int64_t ncde_stream_field_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_field_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream);
+
 /* The stacked step: n_stack chained linear CDE layers (StackedNeuralCDE: layer i + 1 reads layer i's hidden sequence as the linear
  * coefficients of its control) advance by s[0]->n_rows rows in ONE launch, one workgroup per 16 streams walking the layers of a row.
  *   layer 0    fills its row from s[0]->x exactly as ncde_stream_step does.

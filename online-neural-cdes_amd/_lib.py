@@ -155,6 +155,7 @@ EXPORTS = (
     "ncde_stream_workspace_bytes", "ncde_stream_kernel_name", "ncde_stream_step",
     "ncde_stream_hermite_workspace_bytes", "ncde_stream_hermite_kernel_name", "ncde_stream_step_hermite",
     "ncde_stream_stack_workspace_bytes", "ncde_stream_stack_kernel_name", "ncde_stream_stack_step",
+    "ncde_stream_field_workspace_bytes", "ncde_stream_field_kernel_name", "ncde_stream_step_field",
 )
 
 _LIB = None
@@ -234,6 +235,12 @@ def lib():
     h.ncde_stream_hermite_kernel_name.restype = ctypes.c_char_p
     h.ncde_stream_step_hermite.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
     h.ncde_stream_step_hermite.restype = ctypes.c_int
+    h.ncde_stream_field_workspace_bytes.argtypes = [P]
+    h.ncde_stream_field_workspace_bytes.restype = ctypes.c_int64
+    h.ncde_stream_field_kernel_name.argtypes = [P]
+    h.ncde_stream_field_kernel_name.restype = ctypes.c_char_p
+    h.ncde_stream_step_field.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
+    h.ncde_stream_step_field.restype = ctypes.c_int
     PP, SS = ctypes.POINTER(P), ctypes.POINTER(ctypes.POINTER(NcdeStream))      # one pointer per layer of the stack
     h.ncde_stream_stack_workspace_bytes.argtypes = [PP, ctypes.c_int]
     h.ncde_stream_stack_workspace_bytes.restype = ctypes.c_int64

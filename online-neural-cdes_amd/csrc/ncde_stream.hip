@@ -19,7 +19,8 @@
 // default_stage hands load_dx at the stream's own step index, (n + offset) - n in fp32.
 //
 // The phases are device functions of their own (stream_load_state .. stream_store_state); ncde_stream_stack_step runs them layer by
-// layer for a chain of linear CDEs in one launch (see StreamStackArgs).
+// layer for a chain of linear CDEs in one launch (see StreamStackArgs), and ncde_stream_step_field runs them around the stage of the
+// vector-field variants (the minimal-gated field, the evaluate / derivative inputs; see above that kernel).
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -27,6 +28,8 @@
 #include "ncde_common.h"
 #include "ncde_generic_stage.h"
 #include "ncde_host.h"
+#include "ncde_timeloop.h"
+#include "ncde_variant_stage.h"
 
 struct StreamArgs {
     int m, rect, ti, n_out;
@@ -115,12 +118,15 @@ __device__ __forceinline__ void stream_load_state(const KArgs& a, const StreamAr
 // 2. fill row r, 3. the pieces' dX/dt; then the row's bookkeeping.  from: the row as a [c][s] image in LDS (the layer below of a
 // stack: its Y0 after its step for this row), NULL: row r of q.x.  Returns whether any stream of the tile steps (uniform: every
 // thread reads the same 16 flags).  Ends behind a barrier.
+// starts != NULL (the field step's evaluate input): two further [c][s] images, the START ROWS of the two pieces -- starts[..] the
+// stream's last row before this fill, starts[CS + ..] the lagged row -- written in all 16 Cp entries like the dX/dt images (zero
+// for a stream that does not step).
 __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, const float* from,
-                                               int r, int b0, int tid) {
+                                               int r, int b0, int tid, float* starts = nullptr) {
     const int C = a.C, Cp = ru4(C);
     for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
         const int s = e / Cp, c = e - s * Cp, b = b0 + s;
-        float dl = 0.0f, da = 0.0f, db = 0.0f;
+        float dl = 0.0f, da = 0.0f, db = 0.0f, xa = 0.0f, xb = 0.0f;
         if (c < C && b < a.B && (!q.active || q.active[(long long)r * a.B + b])) {
             const int cnt = t.CNT[s];
             const float xv = from ? from[c * 16 + s] : q.x[(long long)r * q.xs_m + (long long)b * q.xs_b + c];
@@ -132,12 +138,18 @@ __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs&
                 db = fill - mid;
                 dl = cnt == 1 ? da : t.PDX[c * 16 + s];
                 t.PDX[c * 16 + s] = q.rect ? db : da;
+                xa = last;
+                xb = mid;
             }
             t.LAST[c * 16 + s] = fill;
         }
         w.DXL[c * 16 + s] = dl;
         w.DXA[c * 16 + s] = da;
         w.DXB[c * 16 + s] = db;
+        if (starts) {
+            starts[c * 16 + s] = xa;
+            starts[Cp * 16 + c * 16 + s] = xb;
+        }
     }
     __syncthreads();
     if (tid < 16) {
@@ -154,7 +166,20 @@ __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs&
     return any_step;
 }
 
-// 4. the Butcher stages, one step per piece
+// 4. the Butcher stages, one step per piece.  stream_combine: the bookkeeping of stage j for the streams that step (the caller's
+// barrier follows)
+__device__ __forceinline__ void stream_combine(const KArgs& a, const StreamScratch& w, const StreamState& t, int j, int HS, int tid) {
+    for (int e = tid; e < HS; e += GEN_THREADS) {
+        if (!w.STEP[e & 15]) continue;
+        float y0 = t.Y0[e], k1 = w.K1[e], k2 = w.K2[e];
+        bool last;
+        const float ys = StageCombine::apply(a.method, j, w.KO[e], 1.0f, y0, k1, k2, last);
+        w.YS[e] = ys;
+        w.K1[e] = k1;
+        w.K2[e] = k2;
+        if (last) t.Y0[e] = y0;
+    }
+}
 template <bool HERMITE>
 __device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid) {
     const int Hp = ru16(a.H), Cp = ru4(a.C), HS = Hp * 16, CS = Cp * 16;
@@ -164,16 +189,7 @@ __device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratc
         const float* dx_left = pc == 0 ? w.DXL : w.DXA;
         for (int j = 0; j < S; ++j) {
             gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, j == 0 ? dx_left : dx_own, w.KO, Hp, Cp, tid);
-            for (int e = tid; e < HS; e += GEN_THREADS) {
-                if (!w.STEP[e & 15]) continue;
-                float y0 = t.Y0[e], k1 = w.K1[e], k2 = w.K2[e];
-                bool last;
-                const float ys = StageCombine::apply(a.method, j, w.KO[e], 1.0f, y0, k1, k2, last);
-                w.YS[e] = ys;
-                w.K1[e] = k1;
-                w.K2[e] = k2;
-                if (last) t.Y0[e] = y0;
-            }
+            stream_combine(a, w, t, j, HS, tid);
             if constexpr (HERMITE) {
                 if (j + 1 < S) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
                     for (int e = tid; e < CS; e += GEN_THREADS) {
@@ -313,6 +329,103 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_stack_step
     for (int l = 0; l < L; ++l) stream_store_state(k.a[l], k.q[l], w, stream_stack_state(k, states, l), b0, tid);
 }
 
+// The field step (ncde_stream_step_field): the same phases around the stage of the vector-field VARIANTS (vr_stage_forward,
+// ncde_variant_stage.h) -- the minimal-gated field, and the evaluate / derivative inputs of the original and the minimal-gated field.
+//
+// The field input U [d0][16] takes the place of YS: rows < H are the stage state, rows H .. H + C - 1 (direct inputs: d0 = H + C)
+// the control input, rewritten before EVERY stage from the images of the fill phase:
+//   matmul / derivative  the dX/dt image of the left-piece rule above (stage 1: DXL, or DXA for the second rectilinear piece; later
+//                        stages the piece's own); matmul hands it to the contraction, derivative copies it into U.
+//   evaluate             X at the stage time.  Stage 1 sits on the piece's first knot and reads that knot's ROW itself: the stream's
+//                        last row before this fill (first piece) or the lagged row (second rectilinear piece), the two images
+//                        stream_fill_row leaves in XS.  Stage j > 0 reads start + frac_j * own, frac_j per stream the frac
+//                        default_stage hands the batch loaders at the stream's own step index n = count - 1 (linear), 2 (count - 1)
+//                        and 2 (count - 1) + 1 (rectilinear): (n + offset_j) - n in fp32.  (The batch kernel forms the knot row as
+//                        prev + 1 (next - prev) on the left piece: equal up to one rounding.  The torch-op step reads the row, too.)
+// Every weight is streamed (wres = -1): one step per launch does not repay filling resident copies, so the sums run in the order of
+// a batch ncde_fwd_variant solve WITHOUT residency.
+//
+// LDS, in floats (HS = ru16(H) 16, DS = 16 max(ru16(d0), ru16(layer widths), ru16(H)), CS = ru4(C) 16):
+//   U, ACT0, ACT1 3 DS | K1, K2, KO 3 HS | DXL, DXA, DXB 3 CS | XS 2 CS | STEP, EVER 32 | state HS + 2 CS + 16     = 3 DS + 4 HS + 7 CS + 48
+// What is read is inside what the launch cleared or a phase wrote, area by area:
+//   U rows < Hp       from Y0 at load and by every combine; rows H .. Hp - 1 receive y0 + dt k of pad rows = 0 there (Y0's pad rows are
+//                     zero from the clear, KO's are written as 0 by the heads), pad samples >= B never step and stay 0.
+//   U rows H .. d0-1  all 16 samples before every stage (after the combine, which may have zeroed rows < Hp among them); samples >= B
+//                     and channels of a stream that does not step read the images' zeros.  Rows d0 .. ru16(d0) - 1 stay zero: no
+//                     phase but the combine (rows < Hp, zeros) writes them.  The first layer reads rows < ru4(d0).
+//   ACT0 / ACT1       rows < ru16(dout) by vr_dense (rows >= dout as 0) before the next layer or the heads read rows < ru4(dout).
+//   KO rows < Hp      by every stage; K1 / K2 by stage 1 / 2 of a step before stage 2 / 3 reads them.
+//   DXL, DXA, DXB, XS all 16 Cp entries by every fill, zeros where c >= C, the sample is beyond B or the stream does not step.
+// Every barrier sits in uniform control flow: the branches around stages are the tile-wide any_step and the launch-wide field input.
+// the evaluate input of stage j of piece pc: X at the stage time -> UC [c][s], c < C (see above)
+__device__ void stream_field_value(const KArgs& a, float* UC, const float* start, const float* own, const int* STEP, int j, int n_pieces, int pc, int tid) {
+    const float off = stage_offset(a.method, j);
+    for (int e = tid; e < a.C * 16; e += GEN_THREADS) {
+        float v = start[e];
+        if (j > 0) {
+            const int n = (STEP[e & 15] - 1) * n_pieces + pc;
+            const float frac = default_stage(a.method, (float)n + off, 0x7fffffff).frac;
+            v = v + frac * own[e];
+        }
+        UC[e] = v;
+    }
+}
+
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const TileDims td = tile_dims(a, a.d0);
+    const int H = a.H, C = a.C, Hp = td.Hp, Cp = td.Cp, HS = td.HS, DS = td.DS, CS = Cp * 16;
+    const bool matmul = a.field_input == NCDE_INPUT_MATMUL, evaluate = a.field_input == NCDE_INPUT_EVALUATE;
+    StreamScratch w;
+    w.YS = lds;      // U
+    w.ACT0 = w.YS + DS;
+    w.ACT1 = w.ACT0 + DS;
+    w.K1 = w.ACT1 + DS;
+    w.K2 = w.K1 + HS;
+    w.KO = w.K2 + HS;
+    w.DXL = w.KO + HS;
+    w.DXA = w.DXL + CS;
+    w.DXB = w.DXA + CS;
+    float* XS = w.DXB + CS;      // the pieces' start rows (evaluate)
+    w.STEP = (int*)(XS + 2 * CS);
+    w.EVER = w.STEP + 16;
+    const StreamState t = stream_carve_state((float*)(w.EVER + 16), a);
+    float* U = w.YS;
+    const int total = 3 * DS + 4 * HS + 7 * CS + 48;
+    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
+    __syncthreads();
+    stream_load_state(a, q, t, U, b0, tid);
+    __syncthreads();
+    const int S = n_stages(a.method), n_pieces = q.rect ? 2 : 1;
+    for (int r = 0; r < q.m; ++r) {
+        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid, evaluate ? XS : nullptr)) {
+            for (int pc = 0; pc < n_pieces; ++pc) {
+                const float* dx_own = pc != 0 ? w.DXB : w.DXA;
+                const float* dx_left = pc == 0 ? w.DXL : w.DXA;
+                const float* start = XS + pc * CS;
+                for (int j = 0; j < S; ++j) {
+                    const float* img = j == 0 ? dx_left : dx_own;
+                    if (!matmul) {
+                        if (evaluate) stream_field_value(a, U + H * 16, start, dx_own, w.STEP, j, n_pieces, pc, tid);
+                        else
+                            for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = img[e];
+                        __syncthreads();
+                    }
+                    // (RU, RG, XB: the gru field's, which the host refuses -- valid addresses all the same, never touched)
+                    vr_stage_forward(a, U, w.ACT0, w.ACT0, w.ACT0, w.ACT0, img, w.KO, nullptr, nullptr, nullptr, lds, Hp, Cp, DS, tid);
+                    stream_combine(a, w, t, j, HS, tid);
+                    __syncthreads();
+                }
+            }
+        }
+        stream_readout(a, q, t, r, b0, tid);
+    }
+    __syncthreads();
+    stream_store_state(a, q, w, t, b0, tid);
+}
+
 namespace {
 
 int sfail(int code, const char* fmt, ...) {
@@ -327,7 +440,8 @@ int sfail(int code, const char* fmt, ...) {
 // The problem as the stream step reads it: batch, channels, hidden, method, flags and the field.  coeffs, z0, n_knots, output and the
 // time plan are NOT read (the rows arrive through NcdeStream, the state lives in its buffers).
 // hermite: the Hermite step's problem says interp = NCDE_INTERP_CUBIC; the LDS plan is the same (the stage image takes the DXB slot).
-int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
+// stream_problem_head: the copy and the checks every step shares, up to the range of the field's two enums.
+int stream_problem_head(const NcdeProblem* in, NcdeProblem* p, bool hermite) {
     if (!in) return sfail(NCDE_ERR_INVALID, "problem is NULL");
     if (in->abi_version < 1 || in->abi_version > NCDE_ABI_VERSION)
         return sfail(NCDE_ERR_INVALID, "abi_version %d not in [1, %d]", in->abi_version, NCDE_ABI_VERSION);
@@ -348,6 +462,12 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
     if (p->field_kind < NCDE_FIELD_ORIGINAL || p->field_kind > NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_INVALID, "unknown field_kind %d", p->field_kind);
     if (p->field_input < NCDE_INPUT_MATMUL || p->field_input > NCDE_INPUT_DERIVATIVE)
         return sfail(NCDE_ERR_INVALID, "vector_field_type string not recognised (field_input %d)", p->field_input);
+    return NCDE_OK;
+}
+
+int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
+    const int rc = stream_problem_head(in, p, hermite);
+    if (rc != NCDE_OK) return rc;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL)
         return sfail(NCDE_ERR_UNSUPPORTED, "online step: the original field with the matmul input only (field_kind %d, field_input %d)", p->field_kind,
                      p->field_input);
@@ -366,6 +486,33 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
     return NCDE_OK;
 }
 
+// The problem as the field step reads it: what stream_problem reads, plus the gate head of a gated field, and a layer chain that
+// starts at the width of the field input, d0 = hidden (matmul) or hidden + channels.
+int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
+    const int rc = stream_problem_head(in, p, false);
+    if (rc != NCDE_OK) return rc;
+    if (p->field_kind == NCDE_FIELD_GRU)
+        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the GRU-gated field is not covered (its stage runs the inner net twice plus a reset gate)");
+    if (p->field_kind == NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the low-rank field is not covered");
+    if (p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL)
+        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is ncde_stream_step's");
+    if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return sfail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
+    int d = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;      // d0
+    for (int l = 0; l < p->n_layers; ++l) {
+        if (p->layer_in[l] != d) return sfail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
+        if (p->layer_out[l] < 1) return sfail(NCDE_ERR_INVALID, "layer %d: out=%d", l, p->layer_out[l]);
+        if (!p->layer_W[l] || !p->layer_b[l]) return sfail(NCDE_ERR_INVALID, "layer %d: NULL weight/bias", l);
+        d = p->layer_out[l];
+    }
+    if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
+    *y = make_layout(p);
+    *lds = sizeof(float) * (size_t)(3 * y->DS + 4 * y->HS + 7 * y->Cp * 16 + 48);
+    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online field step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
+    return NCDE_OK;
+}
+
+enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2 };
+
 }  // namespace
 
 extern "C" int64_t ncde_stream_workspace_bytes(const NcdeProblem* p) {
@@ -383,11 +530,12 @@ extern "C" const char* ncde_stream_kernel_name(const NcdeProblem* p) {
     return stream_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step" : nullptr;
 }
 
-static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, bool hermite) {
+static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, int kind) {
     NcdeProblem q;
     Layout y;
     size_t lds;
-    const int rc = stream_problem(p, &q, &y, &lds, hermite);
+    const bool hermite = kind == kStepHermite;
+    const int rc = kind == kStepField ? stream_field_problem(p, &q, &y, &lds) : stream_problem(p, &q, &y, &lds, hermite);
     if (rc != NCDE_OK) return rc;
     if (!s) return sfail(NCDE_ERR_INVALID, "stream is NULL");
     if (s->n_rows < 1) return sfail(NCDE_ERR_INVALID, "n_rows %d: at least one new row", s->n_rows);
@@ -406,14 +554,38 @@ static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream
     k.z = s->z; k.last = s->last_row; k.pdx = s->prev_dx; k.count = s->count;
     k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
     void (*kernel)(KArgs, StreamArgs) = hermite ? ncde_stream_step_hermite_kernel : ncde_stream_step_kernel;
+    const char* name = hermite ? "ncde_stream_step_hermite" : "ncde_stream_step";
+    if (kind == kStepField) {      // every weight streamed
+        for (int l = 0; l < NCDE_MAX_LAYERS; ++l) a.wres[l] = -1;
+        a.wres_o = a.wres_g = a.wres_r = -1;
+        kernel = ncde_stream_step_field_kernel;
+        name = "ncde_stream_step_field";
+    }
     if (ncde_lds_optin((const void*)kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
     hipLaunchKernelGGL(kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "%s launch failed: %s", hermite ? "ncde_stream_step_hermite" : "ncde_stream_step", hipGetErrorString(e));
+    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "%s launch failed: %s", name, hipGetErrorString(e));
     return NCDE_OK;
 }
 
-extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, false); }
+extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepLinear); }
+
+extern "C" int64_t ncde_stream_field_workspace_bytes(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    const int rc = stream_field_problem(p, &q, &y, &lds);
+    return rc == NCDE_OK ? 0 : rc;
+}
+
+extern "C" const char* ncde_stream_field_kernel_name(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    return stream_field_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step_field" : nullptr;
+}
+
+extern "C" int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepField); }
 
 extern "C" int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p) {
     NcdeProblem q;
@@ -430,7 +602,7 @@ extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) {
     return stream_problem(p, &q, &y, &lds, true) == NCDE_OK ? "ncde_stream_step_hermite" : nullptr;
 }
 
-extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, true); }
+extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepHermite); }
 
 // ---- the stacked step ------------------------------------------------------------------------------------------------------------
 namespace {

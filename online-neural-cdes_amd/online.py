@@ -3,9 +3,11 @@
 ``NeuralCDE.online(batch_size)`` returns an ``OnlineNeuralCDE`` over the module's own parameters.  ``step(x_new)`` fills the new
 observation row(s) causally, appends the one (linear, Hermite cubic) or two (rectilinear) pieces they add to the control path, takes
 one solver step per piece and returns the readout -- what ``NeuralCDE(return_sequences=True)`` on the whole prefix gives at the same
-knot, at the cost of the new pieces only.  On the GPU (fp32, original field, matmul input) a call is ONE launch of
-``ncde_stream_step`` / ``ncde_stream_step_hermite`` (csrc/ncde_stream.hip); anything else takes the torch-op step below behind the
-once-only "unfused" warning.
+knot, at the cost of the new pieces only.  On the GPU (fp32) a call is ONE launch (csrc/ncde_stream.hip): ``ncde_stream_step`` /
+``ncde_stream_step_hermite`` for the original field with the matmul input, ``ncde_stream_step_field`` for the minimal-gated field
+and for the evaluate / derivative inputs of those two fields on a linear or rectilinear path.  Anything else -- the GRU-gated and
+the low-rank field, a gated field or a direct input on the Hermite path, a shape whose LDS plan the kernel's query refuses -- takes
+the torch-op step below behind the once-only "unfused" warning.
 
 ``interpolation="cubic_hermite"`` is the smooth path that is causal: the Hermite cubic with backward differences
 (``hermite_cubic_coefficients_with_backward_differences(x, initial_value_if_nan=v, forward_fill=True)``), whose piece reads the new
@@ -230,11 +232,25 @@ class OnlineNeuralCDE:
             p.layer_W[i], p.layer_b[i] = w.data_ptr(), b.data_ptr()
         p.Wo, p.bo = spec.Wo.data_ptr(), spec.bo.data_ptr()
         p.field_kind, p.field_input = _lib.FIELD_KIND[spec.kind], _lib.FIELD_INPUT[spec.mode]
+        if spec.kind != "original":      # the second head, as solver.build_problem fills it
+            p.Wg, p.bg = spec.Wg.data_ptr(), spec.bg.data_ptr()
         return p
 
+    def _kernel_entry(self, spec):
+        """(query, entry) of the step kernel that covers this field on this path, or None: the original field with the matmul input has
+        ncde_stream_step / ncde_stream_step_hermite; the minimal-gated field and the evaluate / derivative inputs of the two have
+        ncde_stream_step_field on a linear or rectilinear path."""
+        if spec.kind == "original" and spec.mode == "matmul":
+            if self.hermite:
+                return "ncde_stream_hermite_workspace_bytes", "ncde_stream_step_hermite"
+            return "ncde_stream_workspace_bytes", "ncde_stream_step"
+        if spec.kind in ("original", "minimal") and not self.hermite:
+            return "ncde_stream_field_workspace_bytes", "ncde_stream_step_field"
+        return None
+
     def _use_kernel(self, x):
-        """The route, in the house style: CUDA fp32, the original field with the matmul input and a shape the query accepts take the
-        kernel; anything else the torch-op step, behind the once-only warning."""
+        """The route, in the house style: CUDA fp32, a field one of the three step kernels covers (_kernel_entry) and a shape its query
+        accepts take that kernel; anything else the torch-op step, behind the once-only warning.  Nothing here reads the device."""
         key = (x.device.type, x.dtype)
         if key in self._route:      # (the shapes of a module do not change: one query per device / dtype)
             return self._route[key]
@@ -244,11 +260,11 @@ class OnlineNeuralCDE:
         elif not x.is_cuda or x.dtype != torch.float32:
             reason = "online step: tensors are not fp32 on the GPU"
         else:
-            spec = self.model.func.fused_spec()
-            if spec.kind != "original" or spec.mode != "matmul":
+            pick = self._kernel_entry(self.model.func.fused_spec())
+            if pick is None:
                 reason = "online step: a gated or low-rank vector field or the evaluate / derivative input"
             else:
-                query = "ncde_stream_hermite_workspace_bytes" if self.hermite else "ncde_stream_workspace_bytes"
+                query = pick[0]
                 rc = getattr(_lib.lib(), query)(ctypes.byref(self._problem()))
                 if rc == -2:
                     reason = "online step: " + (_lib.lib().ncde_last_error_string() or b"").decode()
@@ -288,7 +304,7 @@ class OnlineNeuralCDE:
         s, out, keep = self._stream_args(x, act, x.size(0))
         with torch.cuda.device(x.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-            entry = "ncde_stream_step_hermite" if self.hermite else "ncde_stream_step"
+            entry = self._kernel_entry(self.model.func.fused_spec())[1]
             _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(p), ctypes.byref(s), stream), entry)
         return out
 

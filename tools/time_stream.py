@@ -3,11 +3,16 @@
     python tools/time_stream.py [--out profiles/online_step_latency.json]      # ROUNDS=5 STEPS=200 REPS=10
     python tools/time_stream.py --interpolation linear,cubic_hermite           # the Hermite step (ncde_stream_step_hermite) next to the
                                                                                # linear step at the same shape: legs alternate in ONE process
+    python tools/time_stream.py --vector-field minimal --batches 16,4096 --prefixes ""      # the field step (ncde_stream_step_field) next
+    python tools/time_stream.py --vector-field-type evaluate --batches 16,4096 --prefixes ""  # to the torch-op step on the same weights
 
 Legs, per batch size B in {1, 16, 256, 4096}:
   online step      handle.step(x_k) of NeuralCDE.online, one new observation per call (one launch of ncde_stream_step)
   prefix k         what a server has without it: one NeuralCDE(return_sequences=False) call on the prefix of k observations
                    (k in {10, 100, 399}; the prefix's coefficients are built BEFORE the clock starts, which flatters this leg)
+  torch-op step    with --vector-field / --vector-field-type other than original / matmul: a second handle over the same weights held
+                   on the torch-op step (online.py::_advance_torch) -- the route such a handle took before ncde_stream_step_field, and
+                   the yardstick of that kernel
 Every call is followed by a device synchronise inside the timed window -- a server reads the prediction before the next observation
 arrives -- and the clock is the host's.  Every leg is warmed up, then the legs are timed ALTERNATING for ROUNDS rounds (STEPS online
 steps / REPS prefix calls per round); one line per (leg, round) so that the spread is visible, then median, min and max per leg.
@@ -34,26 +39,33 @@ def main():
     ap.add_argument("--prefixes", default="10,100,399")
     ap.add_argument("--interpolation", default="rectilinear", help="the causal control path: rectilinear, linear or cubic_hermite; a comma "
                     "list times one online leg per path (the prefix legs run on the first)")
+    ap.add_argument("--vector-field", default="original", help="original or minimal (the fields with a step kernel)")
+    ap.add_argument("--vector-field-type", default="matmul", help="matmul, evaluate or derivative")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a timing needs the GPU"
     ROUNDS, STEPS, REPS = (int(os.environ.get(k, d)) for k, d in (("ROUNDS", 5), ("STEPS", 200), ("REPS", 10)))
     c = dict(bench.CONFIGS["cfg2"])
-    prefixes = [int(k) for k in args.prefixes.split(",")]
+    prefixes = [int(k) for k in args.prefixes.split(",") if k]
+    field = dict(vector_field=args.vector_field, vector_field_type=args.vector_field_type)
+    variant = (args.vector_field, args.vector_field_type) != ("original", "matmul")
     L = max(prefixes + [STEPS]) + 1
     paths = args.interpolation.split(",")
     assert all(p in ("rectilinear", "linear", "cubic_hermite") for p in paths), paths
     path = paths[0]
-    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "interpolation": paths, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
+    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "interpolation": paths, "field": field, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
     for B in (int(b) for b in args.batches.split(",")):
         torch.manual_seed(0)
-        model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=path, solver="rk4").cuda()
+        model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=path, solver="rk4", **field).cuda()
         x = torch.from_numpy(ncde_amd.data.synthetic_series(B, L, c["C"] - 1, missing=c["missing"], seed=1234)).cuda()
         rows = x.transpose(0, 1).contiguous()
         handles = {path: model.online(B)}
         for q in paths[1:]:      # the same weights on the other paths
-            other = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=q, solver="rk4").cuda()
+            other = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=q, solver="rk4", **field).cuda()
             other.load_state_dict(model.state_dict())
             handles[q] = other.online(B)
+        if variant:      # the same handle class, held on the torch-op step (its once-only warning is not the subject here)
+            handles["torch-op"] = model.online(B)
+            handles["torch-op"]._route[("cuda", torch.float32)] = False
         if path == "rectilinear":
             coeffs = {k: ncde_amd.linear_interpolation_coeffs(x[:, :k].contiguous(), rectilinear=0, initial_value_if_nan=0.0) for k in prefixes}
         else:
@@ -80,8 +92,8 @@ def main():
                 torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
-        legs = [("online step" if q == path else "online " + q, lambda q=q: online(STEPS, q)) for q in paths] + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
-        for q in paths:
+        legs = [("online step" if q == path else "online " + q, lambda q=q: online(STEPS, q)) for q in paths] + ([("torch-op step", lambda: online(STEPS, "torch-op"))] if variant else []) + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
+        for q in handles:
             online(20, q)
         for k in prefixes:
             prefix(k, 2)
