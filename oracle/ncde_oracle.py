@@ -739,7 +739,10 @@ class Dopri5:
     ``func(t, y, perturb)``: t a 0-dim tensor ALREADY in the state dtype; perturb in {0: none, -1: just before t}."""
 
     def __init__(self, func, y0, rtol, atol, norm=_rms, min_step=0.0, max_step=float("inf"), first_step=None, safety=0.9,
-                 ifactor=10.0, dfactor=0.2, max_num_steps=2 ** 31 - 1):
+                 ifactor=10.0, dfactor=0.2, max_num_steps=2 ** 31 - 1, replay=None):
+        """replay (verification, the mirror of the library's options["_replay"] / dp_control_body): rows of (dt, accepted).  Attempt i
+        takes dt = replay[i][0] -- the first attempt too, after the initial-step rule or first_step has run -- and is accepted iff
+        replay[i][1] != 0; the controller's own decision and next dt are ignored while rows remain, attempts beyond the list run free."""
         f64 = torch.float64
         self.func, self.y0, self.norm = func, y0, norm
         self.rtol, self.atol = torch.as_tensor(rtol, dtype=f64), torch.as_tensor(atol, dtype=f64)
@@ -747,6 +750,7 @@ class Dopri5:
         self.first_step = None if first_step is None else torch.as_tensor(first_step, dtype=f64)
         self.safety, self.ifactor, self.dfactor = (torch.as_tensor(v, dtype=f64) for v in (safety, ifactor, dfactor))
         self.max_num_steps = max_num_steps
+        self.replay = [] if replay is None else [(float(r[0]), float(r[1]) != 0.0) for r in replay]
         dt_ = y0.dtype
         self.alpha = _DP_ALPHA.to(dt_)
         self.beta = [b.to(dt_) for b in _DP_BETA]
@@ -824,6 +828,8 @@ class Dopri5:
             accept = False
         if dt <= self.min_step:
             accept = True
+        if len(self.trace) < len(self.replay):
+            accept = self.replay[len(self.trace)][1]
         self.trace.append((float(t0), float(dt), accept, float(error_ratio)))
         if accept:
             self.n_accept += 1
@@ -841,6 +847,8 @@ class Dopri5:
             self.n_reject += 1
             t_next, y_next, f_next = t0, y0, f0
         dt_next = self._optimal_step_size(dt, error_ratio).clamp(self.min_step, self.max_step)
+        if len(self.trace) < len(self.replay):      # (the trace already counts this attempt)
+            dt_next = torch.as_tensor(self.replay[len(self.trace)][0], dtype=torch.float64)
         return (y_next, f_next, t0, t_next, dt_next, interp)
 
     def integrate(self, t):
@@ -848,6 +856,8 @@ class Dopri5:
         sol = [self.y0]
         f0 = self._f(t[0], self.y0)
         first = self._select_initial_step(t[0], f0) if self.first_step is None else self.first_step
+        if self.replay:
+            first = torch.as_tensor(self.replay[0][0], dtype=torch.float64)
         st = (self.y0, f0, t[0], t[0], first, [self.y0] * 5)
         for i in range(1, len(t)):
             n = 0
@@ -887,6 +897,8 @@ def dopri5_forward(control, field, z0, t, rtol, atol, options=None, stats=None):
 def dopri5_adjoint(control, field, t, z_out, grad_out, rtol, atol, options=None, stats=None, vjp="hand"):
     """Continuous adjoint with the adaptive solver (adjoint.py:37-145): per output interval a fresh dopri5 solve of the
     flat augmented state [vjp_t, y, a, g_theta...] in negated time, mixed norm max(|t|, rms(y), rms(a), max_p rms(g_p)).
+    options["replay"]: ONE list for the whole call -- the attempt index runs on across the per-interval solves, as the library's
+    NcdeAdaptiveOptions.replay does.
 
     vjp = "hand": the hand-written VJPs used everywhere else in this oracle.  vjp = "autograd": the stage VJP through
     torch.autograd.grad as adjoint.py:95-98 does -- same values up to summation order, but an ADAPTIVE solve amplifies
@@ -952,9 +964,11 @@ def dopri5_adjoint(control, field, t, z_out, grad_out, rtol, atol, options=None,
     a = grad_out[:, -1].clone()
     g = [torch.zeros_like(p) for p in params]
     vt = torch.zeros(1, dtype=y.dtype)       # vjp_t: carried across the output intervals like a and g (adjoint.py:131)
+    options = dict(options or {})
+    replay = options.pop("replay", None)
     for i in range(len(t) - 1, 0, -1):
         v0 = torch.cat([vt, y.reshape(-1), a.reshape(-1)] + [q.reshape(-1) for q in g])
-        sv = Dopri5(func, v0, rtol, atol, norm=norm, **(options or {}))
+        sv = Dopri5(func, v0, rtol, atol, norm=norm, replay=None if replay is None else list(replay)[len(acc["trace"]):], **options)
         v1 = sv.integrate(-t[i - 1:i + 1].flip(0))[1]
         acc["accepted"] += sv.n_accept
         acc["rejected"] += sv.n_reject
