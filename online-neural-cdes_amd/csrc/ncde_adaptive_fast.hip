@@ -20,6 +20,7 @@
 #include "ncde_adaptive_fast.h"
 #include "ncde_bf3.h"
 #include "ncde_dp_defs.h"
+#include "ncde_dp_fused_stage.h"
 #include "ncde_fastdefs.h"
 #include "ncde_host.h"
 
@@ -191,18 +192,10 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_fwd(DpArgs d) {
     for (int q = 0; q < EPQ; ++q) {
         const int e = tid + q * NT;
         const int j = e / (16 * CP), rem = e - j * (16 * CP), es = rem / CP, cc = rem - es * CP;
-        float v = 0.0f;
+        float v = 0.0f, v2;
         if (e < nst * 16 * CP && cc < Cr && b0 + es < a.B) {
             const StageDesc sd = c->st[phase == DP_STEP ? j + 1 : 0];
-            const float* p = a.coeffs + (long long)(b0 + es) * a.cs_b + (long long)sd.idx * a.cs_t;
-            if (a.interp == NCDE_INTERP_LINEAR) {
-                v = p[a.cs_t + cc] - p[cc];
-                if (sd.kdt != 1.0f) v = v / sd.kdt;
-            } else {
-                const float bb = p[Cr + cc], c2 = p[2 * Cr + cc], dd = p[3 * Cr + cc];
-                const float inner = c2 + dd * sd.frac;
-                v = bb + inner * sd.frac;
-            }
+            dp_control_derivative<false>(a, sd, a.interp == NCDE_INTERP_LINEAR, b0 + es, cc, v, v2);
         }
         qn[q] = v;
     }
@@ -439,19 +432,6 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_fwd(DpArgs d) {
 //     DP_STEP, and DP_FIN after an accepted attempt that reached the end of the output interval: the same seven evaluations with the
 //     weights of the 4th-order dense output at the interval end (interp.py:4-61, linear in the k_j), which also resets (y, a) to the
 //     stored solution / adds the next output's cotangent (adjoint.py:116-133).
-template <int H, int HH, int C, int NL>
-struct DpaPack {
-    static constexpr int NW = 4, CP = (C + 3) & ~3, CQ = CP / 4, HB = H / 4, HT = HH / 16, KH = HH / 4, NB = HB / NW, NTILE = NB * CQ;
-    // per wave and lane (registers): the A operands of the wave's own output tiles, the hidden-layer biases
-    static constexpr int O_WO = 0, LANE = NB * CQ * KH, LANE4 = (LANE + 3) / 4;
-    static constexpr int WAVE = LANE4 * 256;                    // floats per wave: [chunk of 4][lane][4]
-    // shared operand images (LDS): [tile][chunk of 4 k-steps][lane][4] -- one ds_read_b128 feeds four MFMAs
-    static constexpr int WOT = NW * NTILE * HT * 256, BOL = NW * NTILE * 16;
-    static constexpr int I_W0 = 0, I_W1 = I_W0 + HT * (HB / 4) * 256, I_W1T = I_W1 + HT * (KH / 4) * 256, I_W0T = I_W1T + HT * (KH / 4) * 256,
-                         I_WOT = I_W0T + NW * (KH / 4) * 256, I_BOL = I_WOT + WOT, I_B0 = I_BOL + BOL, I_B1 = I_B0 + HT * 16,
-                         IMGS = I_B1 + HT * 16;      // I_B0 / I_B1: hidden-layer biases [t][g][r] (the accumulator a lane starts a tile with)
-    static constexpr int TOTAL = NW * WAVE + IMGS;
-};
 
 template <int H, int HH, int C, int NL>
 __global__ __launch_bounds__(256) void ncde_dpa_pack(DpArgs d) {
@@ -521,25 +501,18 @@ __global__ __launch_bounds__(256) void ncde_dpa_pack(DpArgs d) {
 // there).  The wave-private [unit][sample] images keep only the rows the wave's own weight-gradient tiles read.  (Two earlier
 // versions: both sums updated by VALU fma spilled 258 dwords per lane, 30 us per stage; the second sum read-modify-written in LDS
 // with Wo^T streamed from L2 one tile ahead spilled 152 and waited on L2, 25 us per stage.)
+// (The body and its pointers stay inline here, not on DpaStage::eval: at 256 + 256 registers every form of the shared body tried spilled
+// more than this text does -- DESIGN.md 5.6a.  Layout, weight prologue, dX/dt loader, exchange and the hidden-layer write-out are shared.)
 template <int H, int HH, int C, int NL>
 __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
-    typedef DpaPack<H, HH, C, NL> PK;
-    constexpr int NW = 4, NT = 256;
-    constexpr int CP = PK::CP, CQ = PK::CQ, HB = PK::HB, HT = PK::HT, KH = PK::KH, NB = PK::NB, NTILE = PK::NTILE;
-    constexpr int HT0 = H / 16;
-    constexpr int XS = 20;
-    constexpr int R_Z = 0, R_X = 16, R_XL = R_X + 16 * (NL - 1), R_DP = R_XL + HH, PRIV = (R_DP + HH) * XS;      // image rows of a wave
-    constexpr int EPT = (16 * CP + NT - 1) / NT;
-    static_assert(H % (4 * NW) == 0 && HH % 16 == 0 && H % 16 == 0 && NB <= 4 && NTILE <= 16 && KH <= 16, "shape not tileable");
-    static_assert(HT * HT == NW && HT * HT0 == NW, "one dW1 tile and one dW0 tile per wave");
+    typedef DpaStage<H, HH, C, NL> ST;
+    typedef typename ST::PK PK;
+    constexpr int NW = ST::NW, CQ = ST::CQ, HB = ST::HB, HT = ST::HT, KH = ST::KH, NB = ST::NB, NTILE = ST::NTILE;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* zx = lds;                              // [2][H*16]   stage-state exchange
-    float* dxs = zx + 2 * H * 16;                 // [2][16*CP]  dX/dt of the stage, by stage parity
-    float* d2s = dxs + 2 * 16 * CP;               // [2][16*CP]  d2X/dt2 (cubic control: the vjp_t component)
-    float* red = d2s + 2 * 16 * CP;               // [NW][HH*16] dL/dx_L partials
-    float* simg = red + NW * HH * 16;             // operand images (DpaPack::I_*)
-    float* privbase = simg + PK::IMGS;            // [NW][PRIV]
-    double* sh = reinterpret_cast<double*>(privbase + NW * PRIV);      // [4][NW] partial sums
+    typedef DpaLayout<H, HH, C, NL> L;
+    constexpr int CP = L::CP, HT0 = H / 16, XS = L::XS, R_Z = L::R_Z, R_X = L::R_X, R_XL = L::R_XL, R_DP = L::R_DP, PRIV = L::PRIV, EPT = L::EPT;
+    float *dxs = lds + L::O_DXS, *d2s = lds + L::O_D2S, *red = lds + L::O_RED, *simg = lds + L::O_IMG, *privbase = lds + L::O_PRIV;
+    double* sh = reinterpret_cast<double*>(lds + L::O_SH);
     __shared__ StageDesc sds[8];
 
     DpCtrl* c = d.ctrl;
@@ -549,13 +522,14 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
     unsigned long long acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = wall_clock64();
 #endif
     const KArgs& a = d.a;
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int s = lane & 15, g = lane >> 4;
     const int b0 = blockIdx.x * NCDE_TILE;
     const int bs = b0 + s;
     const bool valid = bs < a.B;
-    const int Hr = a.H, HHr = a.dout[0], Cr = a.C;
+    const int Hr = a.H, Cr = a.C;
     const int cur = c->cur;
     const float* Ycur = cur ? d.YC : d.Y0;
     float* Ynxt = cur ? d.Y0 : d.YC;
@@ -580,76 +554,16 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
     const float* w0ti = simg + PK::I_W0T + (wave * (KH / 4) * 64 + lane) * 4;
     const float* woTw = simg + PK::I_WOT + wave * NTILE * HT * 256;
     const float* boLw = simg + PK::I_BOL + wave * NTILE * 16;
-    if (tid < 7) sds[tid] = step ? (tid == 0 ? c->st_k1 : c->st[tid]) : c->st[0];
-
-    // ---- weights: the wave's Wo rows and the biases -> registers, operand images -> LDS ----------------------------------------------
-    float wo[NB][CQ][KH];
     const float* b0i = simg + PK::I_B0 + g * 4;
     const float* b1i = simg + PK::I_B1 + g * 4;
-    {
-        const float* wp = d.WP + (long long)wave * PK::WAVE + lane * 4;
-        float wreg[PK::LANE4 * 4];
-#pragma unroll
-        for (int i4 = 0; i4 < PK::LANE4; ++i4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(wp + i4 * 256);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wreg[4 * i4 + q] = v[q];
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int cq = 0; cq < CQ; ++cq)
-#pragma unroll
-                for (int ks = 0; ks < KH; ++ks) wo[nb][cq][ks] = wreg[PK::O_WO + (nb * CQ + cq) * KH + ks];
-        const f32x4* src = reinterpret_cast<const f32x4*>(d.WP + (long long)NW * PK::WAVE);
-        f32x4* dst = reinterpret_cast<f32x4*>(simg);
-        constexpr int NV = PK::IMGS / 4;
-        int e = tid;
-        for (; e + 7 * NT < NV; e += 8 * NT) {      // eight 16-byte loads in flight per thread
-            f32x4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = src[e + u * NT];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) dst[e + u * NT] = v[u];
-        }
-        for (; e < NV; e += NT) dst[e] = src[e];
-    }
+    const ST S(lds, tid);
+    if (tid < 7) sds[tid] = step ? (tid == 0 ? c->st_k1 : c->st[tid]) : c->st[0];
 
-    // ---- dX/dt (and d2X/dt2) of a stage: loaded into registers early, stored to the parity slot before the stage's last barrier -------
+    float wo[NB][CQ][KH];
+    S.load_weights(d.WP, wo);
     float dxv[EPT], d2v[EPT];
-    auto stage_load = [&](int j) {
-        const StageDesc sd = sds[j];
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + q * NT;
-            const int es = e / CP, cc = e - es * CP;
-            float v = 0.0f, v2 = 0.0f;
-            if (e < 16 * CP && cc < Cr && b0 + es < a.B) {
-                const float* p = a.coeffs + (long long)(b0 + es) * a.cs_b + (long long)sd.idx * a.cs_t;
-                if (!cubic) {
-                    v = p[a.cs_t + cc] - p[cc];
-                    if (sd.kdt != 1.0f) v = v / sd.kdt;
-                } else {
-                    const float bb = p[Cr + cc], c2 = p[2 * Cr + cc], dd = p[3 * Cr + cc];
-                    const float inner = c2 + dd * sd.frac;
-                    v = bb + inner * sd.frac;
-                    v2 = inner + dd * sd.frac;
-                }
-            }
-            dxv[q] = v;
-            d2v[q] = v2;
-        }
-    };
-    auto stage_store = [&](int j) {
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + q * NT;
-            if (e < 16 * CP) {
-                dxs[(j & 1) * 16 * CP + e] = dxv[q];
-                d2s[(j & 1) * 16 * CP + e] = d2v[q];
-            }
-        }
-    };
+    auto stage_load = [&](int j) { S.stage_load(a, sds[j], cubic, b0, dxv, d2v); };
+    auto stage_store = [&](int j) { S.stage_store(j, dxv, d2v); };
 
     // ---- owned state entries -----------------------------------------------------------------------------------------------------
     float y0[NB], a0[NB], ky[7][NB], ka[7][NB], ys[NB], as_[NB], y1[NB], a1[NB];
@@ -706,15 +620,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
     }
     float zreg[HB];
     int zpar = 0;
-    auto exchange = [&]() {      // owned stage inputs -> the layer-0 B operand of every wave (publishes the dX slot stored before it, too)
-        float* zw = zx + zpar * H * 16;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) zw[(4 * (wave * NB + nb) + g) * 16 + s] = ys[nb];
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < HB; ++ks) zreg[ks] = zw[(4 * ks + g) * 16 + s];
-        zpar ^= 1;
-    };
+    auto exchange = [&]() { S.exchange(zpar, ys, zreg); };
     exchange();
     DPA_TICK(0)
 
@@ -1037,18 +943,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
                     if (hh < Hr && cc < Cr && s == tau) gp[a.gbo_off + hh * Cr + cc] = gbo[q][r];
                 }
             }
-        if (NL > 1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (16 * tr1 + 4 * g + r < HHr && 16 * tc1 + s < HHr) gp[a.gW_off[1] + (16 * tr1 + 4 * g + r) * HHr + 16 * tc1 + s] = gW1[q][r];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (16 * tr0 + 4 * g + r < HHr && 16 * tc0 + s < Hr) gp[a.gW_off[0] + (16 * tr0 + 4 * g + r) * Hr + 16 * tc0 + s] = gW0[q][r];
-        if (wave == 0 && s < KH && 4 * s + g < HHr) {      // the lane with s == ks holds the bias sums of unit 4 ks + g
-            if (NL > 1) gp[a.gb_off[1] + 4 * s + g] = gb1[q];
-            gp[a.gb_off[0] + 4 * s + g] = gb0[q];
-        }
+        S.store_hidden_grads(a, gp, gW1[q], gW0[q], gb1[q], gb0[q]);
         // the time component vjp_t (cubic control; zero for a linear one): workgroup sum of the per-lane partials
         float v = row16_sum(gvt[q]);
         v += __shfl_xor(v, 16, 64);
@@ -1073,7 +968,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// reverse sweep of a TAPED solve (adjoint=False) on the same stage machinery: ncde_dp_tape_backward (ncde_adaptive.hip) restated
+// reverse sweep of a TAPED solve (adjoint=False) on the stage machinery of ncde_dp_fused_stage.h (the algorithm of ncde_dp_tape_backward)
 // ------------------------------------------------------------------------------------------------------------------
 // Persistent, one workgroup per 16-sample tile, over the accepted steps m = M-1 .. 0.  Per step: the seven stage derivatives are
 // recomputed from the recorded start state (forward part of the stage body only), the cotangents of the step's outputs are set up
@@ -1083,316 +978,41 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_adj(DpArgs d) {
 // as the attempt kernels do.  Hand-over to ncde_dp_tape_finish (DZ0, F0B, SCB, PN2, the parameter partial) as the per-launch kernel.
 template <int H, int HH, int C, int NL>
 __global__ __launch_bounds__(256, 1) void ncde_dpf_tape(DpArgs d) {
-    typedef DpaPack<H, HH, C, NL> PK;
-    constexpr int NW = 4, NT = 256;
-    constexpr int CP = PK::CP, CQ = PK::CQ, HB = PK::HB, HT = PK::HT, KH = PK::KH, NB = PK::NB, NTILE = PK::NTILE;
-    constexpr int HT0 = H / 16;
-    constexpr int XS = 20;
-    constexpr int R_Z = 0, R_X = 16, R_XL = R_X + 16 * (NL - 1), R_DP = R_XL + HH, PRIV = (R_DP + HH) * XS;
-    constexpr int EPT = (16 * CP + NT - 1) / NT;
-    static_assert(HT * HT == NW && HT * HT0 == NW, "one dW1 tile and one dW0 tile per wave");
+    typedef DpaStage<H, HH, C, NL> ST;
+    constexpr int NW = ST::NW, CQ = ST::CQ, HB = ST::HB, HT = ST::HT, KH = ST::KH, NB = ST::NB, NTILE = ST::NTILE;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* zx = lds;
-    float* dxs = zx + 2 * H * 16;
-    float* d2s = dxs + 2 * 16 * CP;
-    float* red = d2s + 2 * 16 * CP;
-    float* simg = red + NW * HH * 16;
-    float* privbase = simg + PK::IMGS;
-    double* sh = reinterpret_cast<double*>(privbase + NW * PRIV);      // [2][NW]
     __shared__ StageDesc sds[8];
     __shared__ double sh_dt;
     __shared__ int sh_jb, sh_je;
 
     const KArgs& a = d.a;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int s = lane & 15, g = lane >> 4;
+    const int tid = threadIdx.x;
+    const ST S(lds, tid);
+    const int lane = S.lane, wave = S.wave, s = S.s, g = S.g;
     const int b0 = blockIdx.x * NCDE_TILE;
     const int bs = b0 + s;
     const bool valid = bs < a.B;
     const int Hr = a.H, HHr = a.dout[0], Cr = a.C;
     const long long BH = (long long)a.B * Hr;
     const bool cubic = a.interp == NCDE_INTERP_CUBIC;
-    float* priv = privbase + wave * PRIV;
-    float* zimg = priv + R_Z * XS;
-    float* xLimg = priv + R_XL * XS;
-    float* dpimg = priv + R_DP * XS;
-    float* dptile = dpimg;
-    const int tr1 = wave / HT, tc1 = wave - tr1 * HT;
-    const int tr0 = wave / HT0, tc0 = wave - tr0 * HT0;
-    const float* w0i = simg + PK::I_W0 + lane * 4;
-    const float* w1i = simg + PK::I_W1 + lane * 4;
-    const float* w1ti = simg + PK::I_W1T + lane * 4;
-    const float* w0ti = simg + PK::I_W0T + (wave * (KH / 4) * 64 + lane) * 4;
-    const float* woTw = simg + PK::I_WOT + wave * NTILE * HT * 256;
-    const float* boLw = simg + PK::I_BOL + wave * NTILE * 16;
-    const float* b0i = simg + PK::I_B0 + g * 4;
-    const float* b1i = simg + PK::I_B1 + g * 4;
 
     float wo[NB][CQ][KH];
-    {
-        const float* wp = d.WP + (long long)wave * PK::WAVE + lane * 4;
-        float wreg[PK::LANE4 * 4];
-#pragma unroll
-        for (int i4 = 0; i4 < PK::LANE4; ++i4) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(wp + i4 * 256);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) wreg[4 * i4 + q] = v[q];
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int cq = 0; cq < CQ; ++cq)
-#pragma unroll
-                for (int ks = 0; ks < KH; ++ks) wo[nb][cq][ks] = wreg[PK::O_WO + (nb * CQ + cq) * KH + ks];
-        const f32x4* src = reinterpret_cast<const f32x4*>(d.WP + (long long)NW * PK::WAVE);
-        f32x4* dst = reinterpret_cast<f32x4*>(simg);
-        for (int e = tid; e < PK::IMGS / 4; e += NT) dst[e] = src[e];
-    }
-    float dxv[EPT], d2v[EPT];
-    auto stage_load = [&](int j) {
-        const StageDesc sd = sds[j];
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + q * NT;
-            const int es = e / CP, cc = e - es * CP;
-            float v = 0.0f, v2 = 0.0f;
-            if (e < 16 * CP && cc < Cr && b0 + es < a.B) {
-                const float* p = a.coeffs + (long long)(b0 + es) * a.cs_b + (long long)sd.idx * a.cs_t;
-                if (!cubic) {
-                    v = p[a.cs_t + cc] - p[cc];
-                    if (sd.kdt != 1.0f) v = v / sd.kdt;
-                } else {
-                    const float bb = p[Cr + cc], c2 = p[2 * Cr + cc], dd = p[3 * Cr + cc];
-                    const float inner = c2 + dd * sd.frac;
-                    v = bb + inner * sd.frac;
-                    v2 = inner + dd * sd.frac;
-                }
-            }
-            dxv[q] = v;
-            d2v[q] = v2;
-        }
-    };
-    auto stage_store = [&](int slot) {
-#pragma unroll
-        for (int q = 0; q < EPT; ++q) {
-            const int e = tid + q * NT;
-            if (e < 16 * CP) {
-                dxs[(slot & 1) * 16 * CP + e] = dxv[q];
-                d2s[(slot & 1) * 16 * CP + e] = d2v[q];
-            }
-        }
-    };
+    S.load_weights(d.WP, wo);
+    float dxv[ST::EPT], d2v[ST::EPT];
+    auto stage_load = [&](int j) { S.stage_load(a, sds[j], cubic, b0, dxv, d2v); };
+    auto stage_store = [&](int slot) { S.stage_store(slot, dxv, d2v); };
 
-    // ---- gradient accumulators (one sum, weight 1) ---------------------------------------------------------------------------------
-    f32x4 gWo[NTILE][HT], gW1, gW0, gbo;
-    float gb1 = 0.0f, gb0 = 0.0f;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    gW1 = gW0 = gbo = zero4;
-#pragma unroll
-    for (int i = 0; i < NTILE; ++i)
-#pragma unroll
-        for (int t = 0; t < HT; ++t) gWo[i][t] = zero4;
-
+    DpaGradOne<NTILE, HT> G;      // one gradient sum, weight 1
+    G.clear();
     float zreg[HB], ys[NB], as_[NB];
     int zpar = 0, dpar = 0;
-    auto exchange = [&]() {
-        float* zw = zx + zpar * H * 16;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) zw[(4 * (wave * NB + nb) + g) * 16 + s] = ys[nb];
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < HB; ++ks) zreg[ks] = zw[(4 * ks + g) * 16 + s];
-        zpar ^= 1;
-    };
-    // One stage evaluation at the stage input now in zreg, with dX/dt in parity slot `dslot`: kout = f dX/dt for the owned entries; with
-    // `vjp`: also vy = as_^T df/dy, the parameter gradients (+= as_^T df/dtheta) and vt = as_^T (d/dt of f dX/dt) per lane.
+    auto exchange = [&]() { S.exchange(zpar, ys, zreg); };
+    // One stage evaluation at the stage input now in zreg, with dX/dt in parity slot `dslot`: forward-only (kout), or with the VJP of
+    // the cotangent as_ (vy, vt, G)
     float kout[NB], vt;
     f32x4 vy;
-    auto stage = [&](int dslot, bool vjp) {
-        const float* dxp = dxs + (dslot & 1) * 16 * CP + s * CP;
-        const float* d2p = d2s + (dslot & 1) * 16 * CP + s * CP;
-        float xc[KH];
-        unsigned relu_mask = 0;
-        {
-            f32x4 acc[HT];
-#pragma unroll
-            for (int tt = 0; tt < HT; ++tt) acc[tt] = *reinterpret_cast<const f32x4*>(b0i + tt * 16);
-#pragma unroll
-            for (int q4 = 0; q4 < HB / 4; ++q4) {
-                f32x4 a4[HT];
-#pragma unroll
-                for (int tt = 0; tt < HT; ++tt) a4[tt] = *reinterpret_cast<const f32x4*>(w0i + (tt * (HB / 4) + q4) * 256);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int tt = 0; tt < HT; ++tt) acc[tt] = mfma16(a4[tt][i], zreg[4 * q4 + i], acc[tt]);
-            }
-#pragma unroll
-            for (int tt = 0; tt < HT; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xc[4 * tt + r] = relu_dev(acc[tt][r]);
-#pragma unroll
-            for (int l = 1; l < NL; ++l) {
-                if (vjp) {
-#pragma unroll
-                    for (int q4 = 0; q4 < KH / 4; ++q4)
-                        if (q4 == tc1) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) priv[((R_X + 16 * (l - 1)) + 4 * i + g) * XS + s] = xc[4 * q4 + i];
-                        }
-                }
-#pragma unroll
-                for (int ks = 0; ks < KH; ++ks) relu_mask |= (xc[ks] > 0.0f ? 1u : 0u) << (8 * (l - 1) + ks);
-#pragma unroll
-                for (int tt = 0; tt < HT; ++tt) acc[tt] = *reinterpret_cast<const f32x4*>(b1i + tt * 16);
-#pragma unroll
-                for (int q4 = 0; q4 < KH / 4; ++q4) {
-                    f32x4 a4[HT];
-#pragma unroll
-                    for (int tt = 0; tt < HT; ++tt) a4[tt] = *reinterpret_cast<const f32x4*>(w1i + (tt * (KH / 4) + q4) * 256);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int tt = 0; tt < HT; ++tt) acc[tt] = mfma16(a4[tt][i], xc[4 * q4 + i], acc[tt]);
-                }
-#pragma unroll
-                for (int tt = 0; tt < HT; ++tt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) xc[4 * tt + r] = relu_dev(acc[tt][r]);
-            }
-        }
-        f32x4 xB[HT];
-        if (vjp) {
-#pragma unroll
-            for (int q4 = 0; q4 < HB / 4; ++q4)
-                if (q4 == tc0) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) zimg[(4 * i + g) * XS + s] = zreg[4 * q4 + i];
-                }
-#pragma unroll
-            for (int ks = 0; ks < KH; ++ks) xLimg[(4 * ks + g) * XS + s] = xc[ks];
-            wave_lds_order();
-#pragma unroll
-            for (int tt = 0; tt < HT; ++tt) xB[tt] = *reinterpret_cast<const f32x4*>(xLimg + (16 * tt + s) * XS + 4 * g);
-        }
-        f32x4 accJ[HT];
-#pragma unroll
-        for (int tt = 0; tt < HT; ++tt) accJ[tt] = zero4;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) kout[nb] = 0.0f;
-        vt = 0.0f;
-#pragma unroll
-        for (int cq = 0; cq < CQ; ++cq) {
-            f32x4 o[NB];
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) o[nb] = *reinterpret_cast<const f32x4*>(boLw + ((nb * CQ + cq) * 4 + g) * 4);
-#pragma unroll
-            for (int ks = 0; ks < KH; ++ks)
-#pragma unroll
-                for (int nb = 0; nb < NB; ++nb) o[nb] = mfma16(wo[nb][cq][ks], xc[ks], o[nb]);
-            const f32x4 dx = *reinterpret_cast<const f32x4*>(dxp + 4 * cq);
-            const f32x4 d2 = *reinterpret_cast<const f32x4*>(d2p + 4 * cq);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int tau = nb * CQ + cq;
-                f32x4 dP;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float m = tanh_prescaled(o[nb][r]);
-                    kout[nb] = fmaf(m, dx[r], kout[nb]);
-                    dP[r] = (as_[nb] * dx[r]) * (1.0f - m * m);
-                    vt = fmaf(as_[nb] * m, d2[r], vt);
-                }
-                if (vjp) {
-#pragma unroll
-                    for (int tt = 0; tt < HT; ++tt) {
-                        const f32x4 av = *reinterpret_cast<const f32x4*>(woTw + ((tau * HT + tt) * 64 + lane) * 4);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) accJ[tt] = mfma16(av[r], dP[r], accJ[tt]);
-                    }
-                    f32x4 sm;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        sm[r] = row16_sum(dP[r]);
-                        dptile[(4 * g + r) * XS + s] = dP[r];
-                    }
-                    if (s == tau) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) gbo[r] += sm[r];
-                    }
-                    wave_lds_order();
-                    const f32x4 av = *reinterpret_cast<const f32x4*>(dptile + s * XS + 4 * g);
-                    wave_lds_order();
-#pragma unroll
-                    for (int tt = 0; tt < HT; ++tt)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) gWo[tau][tt] = mfma16(av[q], xB[tt][q], gWo[tau][tt]);
-                }
-            }
-        }
-        vy = zero4;
-        if (!vjp) return;
-        float gpre[KH];
-#pragma unroll
-        for (int tt = 0; tt < HT; ++tt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[wave * HH * 16 + (4 * (4 * tt + r) + g) * 16 + s] = accJ[tt][r];
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < KH; ++ks) {
-            float v = red[(4 * ks + g) * 16 + s];
-#pragma unroll
-            for (int wv = 1; wv < NW; ++wv) v += red[wv * HH * 16 + (4 * ks + g) * 16 + s];
-            gpre[ks] = xc[ks] > 0.0f ? v : 0.0f;
-        }
-        auto bias_sum = [&](float& gb) {
-#pragma unroll
-            for (int ks = 0; ks < KH; ++ks) {
-                const float sm = row16_sum(gpre[ks]);
-                if (s == ks) gb += sm;
-                dpimg[(4 * ks + g) * XS + s] = gpre[ks];
-            }
-            wave_lds_order();
-        };
-        auto grad_tile = [&](f32x4& gw, int tr, const float* bimg) {
-            const f32x4 av = *reinterpret_cast<const f32x4*>(dpimg + (16 * tr + s) * XS + 4 * g);
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(bimg + s * XS + 4 * g);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) gw = mfma16(av[q], bv[q], gw);
-            wave_lds_order();
-        };
-#pragma unroll
-        for (int l = NL - 1; l >= 1; --l) {
-            bias_sum(gb1);
-            grad_tile(gW1, tr1, priv + (R_X + 16 * (l - 1)) * XS);
-            f32x4 acc[HT];
-#pragma unroll
-            for (int tt = 0; tt < HT; ++tt) acc[tt] = zero4;
-#pragma unroll
-            for (int q4 = 0; q4 < KH / 4; ++q4) {
-                f32x4 a4[HT];
-#pragma unroll
-                for (int tt = 0; tt < HT; ++tt) a4[tt] = *reinterpret_cast<const f32x4*>(w1ti + (tt * (KH / 4) + q4) * 256);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int tt = 0; tt < HT; ++tt) acc[tt] = mfma16(a4[tt][i], gpre[4 * q4 + i], acc[tt]);
-            }
-#pragma unroll
-            for (int tt = 0; tt < HT; ++tt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gpre[4 * tt + r] = ((relu_mask >> (8 * (l - 1) + 4 * tt + r)) & 1u) ? acc[tt][r] : 0.0f;
-        }
-        bias_sum(gb0);
-        grad_tile(gW0, tr0, zimg);
-#pragma unroll
-        for (int q4 = 0; q4 < KH / 4; ++q4) {
-            const f32x4 a4 = *reinterpret_cast<const f32x4*>(w0ti + q4 * 256);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) vy = mfma16(a4[i], gpre[4 * q4 + i], vy);
-        }
-    };
+    auto stage_forward = [&](int dslot) { S.template eval<false>(dslot, wo, zreg, as_, G, kout, vy, vt); };
+    auto stage_vjp = [&](int dslot) { S.template eval<true>(dslot, wo, zreg, as_, G, kout, vy, vt); };
 
     // ---- per-lane state of the sweep ---------------------------------------------------------------------------------------------------
     float y0[NB], kf[7][NB], kb[7][NB], yb0[NB], yb1[NB], YB1[NB], KBN[NB];
@@ -1449,7 +1069,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_tape(DpArgs d) {
 #pragma unroll 1
         for (int i = 0; i < n_eval; ++i) {
             if (i + 1 < n_eval) stage_load(i + 1);
-            stage(dpar, false);
+            stage_forward(dpar);
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
@@ -1538,7 +1158,7 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_tape(DpArgs d) {
             dpar ^= 1;
             stage_store(dpar);
             exchange();
-            stage(dpar, true);
+            stage_vjp(dpar);
             if (cubic) {      // dL/d(t_i): t_i = t0 + alpha_i dt, t0 = t[0] + dt_1 + constants
                 if (m >= 1) Tpart += (double)vt;
                 else D1part += (double)kAlpha[i - 1] * (double)vt;
@@ -1575,11 +1195,11 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_tape(DpArgs d) {
     }
     const double Tw = wave_sum_d(Tpart), Dw = wave_sum_d(D1part);
     __syncthreads();
-    if (lane == 0) { sh[wave] = Tw; sh[NW + wave] = Dw; }
+    if (lane == 0) { S.sh[wave] = Tw; S.sh[NW + wave] = Dw; }
     __syncthreads();
     if (tid == 0) {
-        d.PN2[(long long)blockIdx.x * 4 + 0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-        d.PN2[(long long)blockIdx.x * 4 + 1] = (sh[NW] + sh[NW + 1]) + (sh[NW + 2] + sh[NW + 3]);
+        d.PN2[(long long)blockIdx.x * 4 + 0] = (S.sh[0] + S.sh[1]) + (S.sh[2] + S.sh[3]);
+        d.PN2[(long long)blockIdx.x * 4 + 1] = (S.sh[NW] + S.sh[NW + 1]) + (S.sh[NW + 2] + S.sh[NW + 3]);
         d.PN2[(long long)blockIdx.x * 4 + 2] = 0.0;
         d.PN2[(long long)blockIdx.x * 4 + 3] = 0.0;
     }
@@ -1597,23 +1217,12 @@ __global__ __launch_bounds__(256, 1) void ncde_dpf_tape(DpArgs d) {
                 if (hh < Hr && cc < Cr) {
 #pragma unroll
                     for (int tt = 0; tt < HT; ++tt)
-                        if (16 * tt + s < HHr) gp[a.gWo_off + (long long)(hh * Cr + cc) * HHr + 16 * tt + s] = gWo[tau][tt][r];
-                    if (s == tau) gp[a.gbo_off + hh * Cr + cc] = gbo[r];
+                        if (16 * tt + s < HHr) gp[a.gWo_off + (long long)(hh * Cr + cc) * HHr + 16 * tt + s] = G.gWo[tau][tt][r];
+                    if (s == tau) gp[a.gbo_off + hh * Cr + cc] = G.gbo[r];
                 }
             }
         }
-    if (NL > 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (16 * tr1 + 4 * g + r < HHr && 16 * tc1 + s < HHr) gp[a.gW_off[1] + (16 * tr1 + 4 * g + r) * HHr + 16 * tc1 + s] = gW1[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        if (16 * tr0 + 4 * g + r < HHr && 16 * tc0 + s < Hr) gp[a.gW_off[0] + (16 * tr0 + 4 * g + r) * Hr + 16 * tc0 + s] = gW0[r];
-    if (wave == 0 && s < KH && 4 * s + g < HHr) {
-        if (NL > 1) gp[a.gb_off[1] + 4 * s + g] = gb1;
-        gp[a.gb_off[0] + 4 * s + g] = gb0;
-    }
+    S.store_hidden_grads(a, gp, G.gW1, G.gW0, G.gb1, G.gb0);
     if (tid == 0) gp[a.theta_size] = 0.0f;
 }
 
@@ -1753,10 +1362,14 @@ int dpf_shape(const NcdeProblem* p) {      // 0: none, 1: <32, 32, 20>, 2: <64, 
 
 namespace {
 typedef DpaPack<32, 32, 20, 3> Dpa32;      // (the pack layout does not depend on NL)
-size_t dpa_lds_bytes(int nl) {
-    const size_t priv = (size_t)(16 + 16 * (nl - 1) + 32 + 32) * 20;
-    return 4 * (size_t)(2 * 32 * 16 + 4 * 16 * 20 + 4 * 32 * 16 + Dpa32::IMGS + 4 * priv) + 16 * sizeof(double);
+template <int NL>
+constexpr size_t dpa_lds() {      // the kernels' own layout; the assertion: the formula this function held before the layout was stated once
+    typedef DpaLayout<32, 32, 20, NL> L;
+    static_assert(L::BYTES == 4 * (size_t)(2 * 32 * 16 + 4 * 16 * 20 + 4 * 32 * 16 + Dpa32::IMGS + 4 * (16 + 16 * (NL - 1) + 32 + 32) * 20) + 16 * sizeof(double),
+                  "dynamic LDS of the fused adjoint / sweep moved: the 160 KB gate and the dispatch table move with it");
+    return L::BYTES;
 }
+size_t dpa_lds_bytes(int nl) { return nl == 1 ? dpa_lds<1>() : (nl == 2 ? dpa_lds<2>() : dpa_lds<3>()); }      // nl <= 3: every caller asks ncde_dpf_supported first
 template <int NL>
 DpfKernel dpa_kernel() { return (DpfKernel)ncde_dpf_adj<32, 32, 20, NL>; }
 DpfKernel dpa_pick(int nl) { return nl == 1 ? dpa_kernel<1>() : (nl == 2 ? dpa_kernel<2>() : (nl == 3 ? dpa_kernel<3>() : nullptr)); }      // (NL = 4 does not fit the 160 KB of LDS)

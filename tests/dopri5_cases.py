@@ -21,6 +21,7 @@ seed pair on which the fp32 oracle, plain and from three shaken z0, stays within
 Measured on an MI355X, worst over the variants and batches of a shape and axis, z / adjoint=True gradients / adjoint=False gradients:
     h32          A 2.3e-06/2.9e-06/1.7e-06   B 2.9e-06/2.8e-06/5.1e-06   Cl 4.2e-06/2.7e-06/1.8e-06   Cc 2.7e-06/2.8e-06/2.3e-06
     h32_pad_nl1  A 2.0e-06/2.1e-06/9.1e-07   B 1.7e-06/2.1e-06/2.2e-06   Cl 2.7e-06/2.6e-06/8.8e-07   Cc 2.2e-06/2.3e-06/1.1e-06
+    h32_nl2      A 2.4e-06/3.4e-06/8.9e-07   B 2.3e-06/2.6e-06/2.7e-06   Cl 2.3e-06/2.3e-06/1.1e-06   Cc 2.8e-06/2.1e-06/1.1e-06
     h32_nl4      A 2.3e-06/2.1e-06/7.9e-07   B 2.8e-06/3.2e-06/3.0e-06   Cl 2.5e-06/3.2e-06/2.0e-06   Cc 2.5e-06/6.0e-06/2.1e-06
     h64          A 2.7e-06/3.0e-06/7.2e-07   B 2.6e-06/3.0e-06/1.3e-06   Cl 2.9e-06/4.9e-06/9.1e-07   Cc 4.4e-06/3.7e-06/1.4e-06
     h64_pad      A 3.1e-06/2.3e-06/4.5e-07   B 3.1e-06/3.1e-06/1.4e-06   Cl 2.4e-06/3.2e-06/6.7e-07   Cc 3.0e-06/3.1e-06/7.3e-07
@@ -47,6 +48,7 @@ _LAUNCH = ("ncde_dp_stage", "ncde_dp_tape_backward")
 SHAPES = {
     "h32": ((20, 32, 32, 3), 0, ("ncde_dpf_fwd<H32",) + _FUSED),
     "h32_pad_nl1": ((5, 16, 24, 1), 0, ("ncde_dpf_fwd<H32",) + _FUSED),
+    "h32_nl2": ((6, 24, 32, 2), 0, ("ncde_dpf_fwd<H32",) + _FUSED),      # the NL = 2 instantiations of the fused adjoint and sweep
     "h32_nl4": ((20, 32, 32, 4), 0, ("ncde_dpf_fwd<H32",) + _LAUNCH),
     "h64": ((4, 64, 64, 3), 0, ("ncde_dpf_fwd<H64",) + _LAUNCH),
     "h64_pad": ((3, 48, 64, 2), 0, ("ncde_dpf_fwd<H64",) + _LAUNCH),
@@ -251,7 +253,8 @@ SEEDS = {
     "h32-A-end-B50": (95, 11), "h32-B-end-B21": (97, 9), "h32-B-early-B21": (97, 9), "h32-B-end-B50": (97, 9), "h32-Cl-end-B21": (95, 11),
     "h32-Cl-early-B21": (95, 11), "h32-Cl-inside-B21": (97, 10), "h32-Cl-end-B50": (97, 12), "h32-Cc-end-B21": (97, 10),
     "h32-Cc-early-B21": (97, 10), "h32-Cc-end-B50": (97, 11), "h32_pad_nl1-B-end-B21": (97, 9), "h32_pad_nl1-B-early-B21": (97, 9),
-    "h32_pad_nl1-Cl-inside-B21": (97, 9), "h32_nl4-A-end-B21": (95, 10), "h32_nl4-B-end-B21": (97, 9), "h32_nl4-B-early-B21": (97, 9),
+    "h32_pad_nl1-Cl-inside-B21": (97, 9), "h32_nl2-Cl-inside-B21": (97, 9), "h32_nl2-Cc-early-B21": (95, 10),
+    "h32_nl4-A-end-B21": (95, 10), "h32_nl4-B-end-B21": (97, 9), "h32_nl4-B-early-B21": (97, 9),
     "h32_nl4-Cl-end-B21": (97, 9), "h32_nl4-Cl-early-B21": (97, 9), "h32_nl4-Cl-inside-B21": (97, 10), "h64-A-end-B21": (97, 14),
     "h64-A-early-B21": (97, 10), "h64-B-end-B21": (97, 10), "h64-B-early-B21": (97, 9), "h64-Cl-end-B21": (97, 9), "h64-Cl-early-B21": (97, 9),
     "h64-Cl-inside-B21": (95, 10), "h64-Cc-end-B21": (97, 10), "h64-Cc-early-B21": (97, 10), "h64_pad-A-end-B21": (97, 9),

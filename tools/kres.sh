@@ -14,7 +14,7 @@ if [ "$1" != "--check" ]; then table $1; exit 0; fi
 # mangled-name fragments: template arguments as ILi<v>E...
 #   cfg2 / cfg3: ncde_fwd_fast_bf3<32,32,20,NW4,linear,rk4,PROF0,NLT3,fp16x2,PLAN0>, ncde_adj_fast3<NL3,C20,linear,rk4,PROF0,DISC0,HP2,PLAN0>
 #   cfg4:        ncde_fwd_fast_bf3<64,64,4,NW4,cubic,midpoint,0,3,fp16x2,0>,       ncde_adj_h64<midpoint,NS1,HPF1,DISC0,PLAN0>
-#   dopri5:      ncde_dpf_fwd<32,32,20>, ncde_dpf_tape<32,32,20,3>   (ncde_dpf_adj keeps 128 B: DESIGN.md 5.5e)
+#   dopri5:      ncde_dpf_fwd<32,32,20>, ncde_dpf_tape<32,32,20,3>   (ncde_dpf_adj<..,2> / <..,3> keep 72 B / 120 B: DESIGN.md 5.6a)
 rc=0
 check() {  # file, name fragment
   line=$(grep -F "$2" /tmp/kres_$1.txt | head -1)
