@@ -731,6 +731,13 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_dp_tape_finish(Dp
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
+// in a function with `err` / `errn`: a failed HIP call becomes its text and NCDE_ERR_HIP
+#define DP_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) { snprintf(err, errn, "%s failed: %s", #expr, hipGetErrorString(e_)); return NCDE_ERR_HIP; } \
+    } while (0)
+
 namespace {
 
 struct DpPlan {
@@ -833,6 +840,70 @@ TapeWs tape_ws(const NcdeProblem* p, const Layout& y) {
     w.total = o;
     return w;
 }
+
+// Dynamic LDS of a pass.  `base`: what the gates compare with the 160 KB and name in their refusals -- the arrays plus, for the two
+// gradient passes, 4 x 256 doubles for the kernels' block reductions (static __shared__ there, so not part of `launch`).  The gradient
+// accumulator of theta1 floats joins the arrays (`gacc`) where that still fits.
+enum DpPass { kDpForwardStage, kDpAdjointStage, kDpTapeSweep };
+struct DpLds {
+    size_t base, launch;
+    bool gacc;
+};
+DpLds dp_lds(const Layout& y, DpPass pass, int theta1) {
+    DpLds l{};
+    if (pass == kDpForwardStage) {
+        l.base = l.launch = sizeof(float) * (size_t)(2 * y.HS + 2 * y.DS + y.Cp * 16);
+        return l;
+    }
+    const size_t arrays = sizeof(float) * (size_t)((pass == kDpTapeSweep ? 7 : 4) * y.HS + ((y.L > 0 ? y.L : 1) + 4) * y.DS + 2 * y.Cp * 16 + 4 * 16 * 17);
+    l.base = arrays + 4 * 256 * sizeof(double);
+    l.gacc = l.base + sizeof(float) * (size_t)theta1 <= (size_t)kLdsLimit;
+    l.launch = arrays + (l.gacc ? sizeof(float) * (size_t)theta1 : 0);
+    return l;
+}
+
+// the record's arrays, as the recording forward and the reverse sweep see them
+void dp_bind_record(DpArgs& d, void* record, const TapeLayout& tl) {
+    char* rb = (char*)record;
+    d.tape = (DpTapeHeader*)rb;
+    d.tape_steps = (DpStepRec*)(rb + tl.off_steps);
+    d.tape_x = (float*)(rb + tl.off_x);
+    d.tape_y = (float*)(rb + tl.off_y);
+    d.tape_cap = tl.cap;
+}
+
+// a user knot grid as floats at `dst` (device); synchronises: the staging copy is a local
+hipError_t dp_upload_knots(const NcdeProblem* p, const NcdeTimeSpec* ts, void* dst, hipStream_t st) {
+    if (!ts->knots) return hipSuccess;
+    std::vector<float> kf(p->n_knots);
+    for (int i = 0; i < p->n_knots; ++i) kf[i] = (float)ts->knots[i];
+    const hipError_t e = hipMemcpyAsync(dst, kf.data(), sizeof(float) * p->n_knots, hipMemcpyHostToDevice, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+
+// Runs a solve to its end: enqueue(rounds) launches that many attempts (those of a finished solve exit at once), then the controller is
+// read back.  Per-launch kernels: 16 attempts per poll.  Fused attempt kernels (ncde_adaptive_fast.hip, ONE launch per attempt): how many
+// are enqueued before the next look follows the progress so far (attempts per unit of solver time), so a solve is polled a handful of
+// times, not once per 16 attempts.
+template <class Enqueue>
+int dp_poll(const DpArgs& d, const NcdeTimeSpec* ts, hipStream_t st, DpCtrl* hc, char* err, size_t errn, Enqueue enqueue) {
+    const double t_lo = ts->t[0], t_hi = ts->t[d.n_t - 1];
+    int rounds = d.fused ? 48 : 16;
+    for (long long guard = 0; guard < (1LL << 40); ++guard) {
+        const int rc = enqueue(rounds);
+        if (rc != NCDE_OK) return rc;
+        DP_TRY(hipMemcpyAsync(hc, d.ctrl, sizeof(DpCtrl), hipMemcpyDeviceToHost, st));
+        DP_TRY(hipStreamSynchronize(st));
+        if (hc->error != 0 || hc->phase == DP_DONE) break;
+        if (!d.fused) continue;
+        const double done = d.adj ? (hc->t0 + t_hi) / (t_hi - t_lo) : (hc->t0 - t_lo) / (t_hi - t_lo);
+        const double launched = (double)hc->n_attempts + 2.0;
+        double remaining = done > 1e-3 ? launched * (1.0 - done) / done : 4.0 * launched;
+        remaining = remaining * 1.05 + 6.0 + (d.adj ? 3.0 * (hc->interval - 1) : 0.0);
+        rounds = (int)std::min(std::min(1024.0, 2.0 * rounds), std::max(8.0, remaining));      // (early estimates overshoot: first steps are short)
+    }
+    return NCDE_OK;
+}
 }  // namespace
 
 int64_t ncde_dp_workspace_bytes(const NcdeProblem* p, int n_t, int adj) {
@@ -850,7 +921,7 @@ bool ncde_dp_supported(const NcdeProblem* p, int adj, char* why, size_t n) {
     if (y.variant) { snprintf(why, n, "dopri5 runs the original field with the matmul input only"); return false; }
     if (!adj && y.lds_fwd > (size_t)kLdsLimit) { snprintf(why, n, "dopri5 forward needs %zu B of LDS", y.lds_fwd); return false; }
     if (adj) {
-        const size_t base = sizeof(float) * (size_t)(4 * y.HS + ((y.L > 0 ? y.L : 1) + 4) * y.DS + 2 * y.Cp * 16 + 4 * 16 * 17) + 4 * 256 * sizeof(double);
+        const size_t base = dp_lds(y, kDpAdjointStage, y.theta_size + 1).base;
         if (base > (size_t)kLdsLimit) { snprintf(why, n, "dopri5 adjoint needs %zu B of LDS", base); return false; }
         if (y.dlast > 128) { snprintf(why, n, "dopri5 adjoint supports a last hidden width <= 128 (got %d)", y.dlast); return false; }
     }
@@ -865,7 +936,7 @@ bool ncde_dp_tape_supported(const NcdeProblem* p, char* why, size_t n) {
     const Layout y = make_layout(p);
     if (y.Hp > 16 * DP_NE) { snprintf(why, n, "dopri5 with adjoint=False supports hidden <= %d (got %d)", 16 * DP_NE, p->hidden); return false; }
     if (y.dlast > 128) { snprintf(why, n, "dopri5 with adjoint=False supports a last hidden width <= 128 (got %d)", y.dlast); return false; }
-    const size_t lds = sizeof(float) * (size_t)(7 * y.HS + ((y.L > 0 ? y.L : 1) + 4) * y.DS + 2 * y.Cp * 16 + 4 * 16 * 17) + 4 * 256 * sizeof(double);
+    const size_t lds = dp_lds(y, kDpTapeSweep, y.theta_size + 1).base;
     if (lds > (size_t)kLdsLimit) { snprintf(why, n, "dopri5 with adjoint=False needs %zu B of LDS for its reverse sweep (> %d)", lds, kLdsLimit); return false; }
     return true;
 }
@@ -906,17 +977,11 @@ int ncde_dp_solve(const NcdeProblem* p, const NcdeTimeSpec* ts, const NcdeAdapti
         if (adj) { snprintf(err, errn, "a record is kept by the forward solve only"); return NCDE_ERR_INVALID; }
         const int cap = tape_cap_of(p, n_t, record_bytes);
         if (cap < 1) { snprintf(err, errn, "record of %zu B holds no step (ncde_dopri5_record_bytes)", record_bytes); return NCDE_ERR_WORKSPACE; }
-        const TapeLayout tl = tape_layout(p, n_t, cap);
-        char* rb = (char*)record;
-        d.tape = (DpTapeHeader*)rb;
-        d.tape_steps = (DpStepRec*)(rb + tl.off_steps);
-        d.tape_x = (float*)(rb + tl.off_x);
-        d.tape_y = (float*)(rb + tl.off_y);
-        d.tape_cap = cap;
+        dp_bind_record(d, record, tape_layout(p, n_t, cap));
         DpTapeHeader hh;
         memset(&hh, 0, sizeof(hh));
         hh.magic = DP_TAPE_MAGIC; hh.cap = cap; hh.n_t = n_t;
-        hipError_t e0 = hipMemcpyAsync(rb, &hh, sizeof(hh), hipMemcpyHostToDevice, st);
+        hipError_t e0 = hipMemcpyAsync(record, &hh, sizeof(hh), hipMemcpyHostToDevice, st);
         if (e0 == hipSuccess) e0 = hipStreamSynchronize(st);      // hh is a local
         if (e0 != hipSuccess) { snprintf(err, errn, "record header upload failed: %s", hipGetErrorString(e0)); return NCDE_ERR_HIP; }
     }
@@ -926,38 +991,16 @@ int ncde_dp_solve(const NcdeProblem* p, const NcdeTimeSpec* ts, const NcdeAdapti
     d.ifactor = op->ifactor > 0.0 ? op->ifactor : 10.0;
     d.dfactor = op->dfactor > 0.0 ? op->dfactor : 0.2;
     d.max_num_steps = op->max_num_steps > 0 ? op->max_num_steps : 2147483647;
-    // parameter tensors = segments of the flat gradient layout (one rms each in the mixed norm)
-    {
-        int n = 0;
-        for (int l = 0; l < p->n_layers; ++l) {
-            bool firstW = true, firstB = true;
-            for (int q = 0; q < l; ++q) {
-                if (p->layer_W[q] == p->layer_W[l]) firstW = false;
-                if (p->layer_b[q] == p->layer_b[l]) firstB = false;
-            }
-            // a NULL destination = the tensor is not among the adjoint's parameters (requires_grad False, or left out of
-            // adjoint_params): the reference's augmented state does not contain it (adjoint.py:176-189), so it has no say in
-            // the mixed error norm either
-            if (firstW && (!adj || g->grad_layer_W[l])) { d.seg_off[n] = y.gW_off[l]; d.seg_len[n] = p->layer_out[l] * p->layer_in[l]; ++n; }
-            if (firstB && (!adj || g->grad_layer_b[l])) { d.seg_off[n] = y.gb_off[l]; d.seg_len[n] = p->layer_out[l]; ++n; }
-        }
-        if (!adj || g->grad_Wo) { d.seg_off[n] = y.gWo_off; d.seg_len[n] = y.rows * y.dlast; ++n; }
-        if (!adj || g->grad_bo) { d.seg_off[n] = y.gbo_off; d.seg_len[n] = y.rows; ++n; }
-        d.nseg = n;
-    }
-    // LDS plans
-    const size_t lds_fwd = sizeof(float) * (size_t)(2 * y.HS + 2 * y.DS + y.Cp * 16);
-    size_t lds_adj = sizeof(float) * (size_t)(4 * y.HS + ((y.L > 0 ? y.L : 1) + 4) * y.DS + 2 * y.Cp * 16 + 4 * 16 * 17);
-    const size_t red_bytes = 4 * 256 * sizeof(double);
-    d.gacc_in_lds = adj && lds_adj + sizeof(float) * (size_t)w.theta1 + red_bytes <= (size_t)kLdsLimit;
-    if (d.gacc_in_lds) lds_adj += sizeof(float) * (size_t)w.theta1;
-    const size_t lds = adj ? lds_adj : lds_fwd;
-
-#define DP_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) { snprintf(err, errn, "%s failed: %s", #expr, hipGetErrorString(e_)); return NCDE_ERR_HIP; } \
-    } while (0)
+    // parameter tensors = segments of the flat gradient layout: one rms each in the mixed error norm, and the final scatter's list.
+    // A NULL destination = the tensor is not among the adjoint's parameters (requires_grad False, or left out of adjoint_params): the
+    // reference's augmented state does not contain it (adjoint.py:176-189), so it has no say in the norm either.
+    ReduceSegs segs{};
+    build_segs(p, y, g, adj ? kSegsSkipNull : kSegsNoDst, &segs);
+    d.nseg = segs.n;
+    std::copy(segs.off, segs.off + segs.n, d.seg_off);
+    std::copy(segs.len, segs.len + segs.n, d.seg_len);
+    const DpLds lds = dp_lds(y, adj ? kDpAdjointStage : kDpForwardStage, w.theta1);
+    d.gacc_in_lds = lds.gacc;
 
     DP_TRY(hipMemcpyAsync(base + w.off_t, ts->t, sizeof(double) * n_t, hipMemcpyHostToDevice, st));
     if (replay && replay_n > 0) {
@@ -968,57 +1011,39 @@ int ncde_dp_solve(const NcdeProblem* p, const NcdeTimeSpec* ts, const NcdeAdapti
         d.replay = rdev;
         d.replay_n = replay_n;
     }
-    std::vector<float> kf;
-    if (ts->knots) {
-        kf.resize(p->n_knots);
-        for (int i = 0; i < p->n_knots; ++i) kf[i] = (float)ts->knots[i];
-        DP_TRY(hipMemcpyAsync(base + w.off_knots, kf.data(), sizeof(float) * p->n_knots, hipMemcpyHostToDevice, st));
-        DP_TRY(hipStreamSynchronize(st));      // kf is a local: the copy must have left it before we go on
-    }
+    DP_TRY(dp_upload_knots(p, ts, base + w.off_knots, st));
     const long long BH = (long long)p->batch * p->hidden;
     const int egrid = (int)((BH + 255) / 256);
     const int tgrid = (w.theta1 + 255) / 256;
-    DP_TRY(ncde_lds_optin((const void*)ncde_dp_stage, lds));
+    DP_TRY(ncde_lds_optin((const void*)ncde_dp_stage, lds.launch));
     hipLaunchKernelGGL(ncde_dp_init, dim3(egrid), dim3(256), 0, st, d);
     DP_TRY(hipGetLastError());
     DpCtrl hc;
-    const int rounds_per_sync = 16;
-    // Fused attempt kernels (ncde_adaptive_fast.hip): ONE launch per attempt.  The host still only counts launches; how many it enqueues
-    // before it looks at the controller again follows the progress so far (attempts per unit of solver time), so a solve is polled a
-    // handful of times, not once per 16 attempts.
     d.fused = ncde_dpf_supported(p, adj) ? 1 : 0;
+    int rc;
     if (d.fused) {
-        const int rcp = ncde_dpf_prepare(p, &d, sizeof(d), adj, st);
-        if (rcp != NCDE_OK) { snprintf(err, errn, "fused dopri5: weight image failed (%d)", rcp); return rcp; }
-        const double t_lo = ts->t[0], t_hi = ts->t[n_t - 1];
-        int rounds = 48;
-        for (long long guard = 0; guard < (1LL << 40); ++guard) {
-            const int rc = ncde_dpf_launch(p, &d, sizeof(d), adj, rounds, st);
-            if (rc != NCDE_OK) { snprintf(err, errn, "fused dopri5 launch failed (%d)", rc); return rc; }
-            DP_TRY(hipMemcpyAsync(&hc, d.ctrl, sizeof(DpCtrl), hipMemcpyDeviceToHost, st));
-            DP_TRY(hipStreamSynchronize(st));
-            if (hc.error != 0 || hc.phase == DP_DONE) break;
-            const double done = adj ? (hc.t0 + t_hi) / (t_hi - t_lo) : (hc.t0 - t_lo) / (t_hi - t_lo);
-            const double launched = (double)hc.n_attempts + 2.0;
-            double remaining = done > 1e-3 ? launched * (1.0 - done) / done : 4.0 * launched;
-            remaining = remaining * 1.05 + 6.0 + (adj ? 3.0 * (hc.interval - 1) : 0.0);
-            rounds = (int)std::min(std::min(1024.0, 2.0 * rounds), std::max(8.0, remaining));      // (early estimates overshoot: first steps are short)
-        }
-    }
-    for (long long guard = 0; !d.fused && guard < (1LL << 40); ++guard) {
-        for (int r = 0; r < rounds_per_sync; ++r) {
-            for (int slot = 1; slot <= 6; ++slot) {
-                hipLaunchKernelGGL(ncde_dp_stage, dim3(w.n_wg), dim3(GEN_THREADS), lds, st, d, slot);
-                if (adj) hipLaunchKernelGGL(ncde_dp_reduce_theta, dim3(tgrid), dim3(256), 0, st, d, slot);
+        rc = ncde_dpf_prepare(p, d, adj, st);
+        if (rc != NCDE_OK) { snprintf(err, errn, "fused dopri5: weight image failed (%d)", rc); return rc; }
+        rc = dp_poll(d, ts, st, &hc, err, errn, [&](int rounds) {
+            const int rl = ncde_dpf_launch(p, d, adj, rounds, st);
+            if (rl != NCDE_OK) snprintf(err, errn, "fused dopri5 launch failed (%d)", rl);
+            return rl;
+        });
+    } else {
+        rc = dp_poll(d, ts, st, &hc, err, errn, [&](int rounds) -> int {
+            for (int r = 0; r < rounds; ++r) {
+                for (int slot = 1; slot <= 6; ++slot) {
+                    hipLaunchKernelGGL(ncde_dp_stage, dim3(w.n_wg), dim3(GEN_THREADS), lds.launch, st, d, slot);
+                    if (adj) hipLaunchKernelGGL(ncde_dp_reduce_theta, dim3(tgrid), dim3(256), 0, st, d, slot);
+                }
+                hipLaunchKernelGGL(ncde_dp_control, dim3(1), dim3(256), 0, st, d);
+                hipLaunchKernelGGL(ncde_dp_commit, dim3(egrid), dim3(256), 0, st, d);
             }
-            hipLaunchKernelGGL(ncde_dp_control, dim3(1), dim3(256), 0, st, d);
-            hipLaunchKernelGGL(ncde_dp_commit, dim3(egrid), dim3(256), 0, st, d);
-        }
-        DP_TRY(hipGetLastError());
-        DP_TRY(hipMemcpyAsync(&hc, d.ctrl, sizeof(DpCtrl), hipMemcpyDeviceToHost, st));
-        DP_TRY(hipStreamSynchronize(st));
-        if (hc.error != 0 || hc.phase == DP_DONE) break;
+            DP_TRY(hipGetLastError());
+            return NCDE_OK;
+        });
     }
+    if (rc != NCDE_OK) return rc;
     if (d.trace_cap > 0) {
         const int rows = std::min(d.trace_cap, hc.n_attempts);
         if (rows > 0) DP_TRY(hipMemcpy(op->trace, d.TR, sizeof(double) * 4 * rows, hipMemcpyDeviceToHost));
@@ -1035,28 +1060,13 @@ int ncde_dp_solve(const NcdeProblem* p, const NcdeTimeSpec* ts, const NcdeAdapti
         const float* a_end = (d.fused && hc.cur) ? d.AC : d.A0;        // fused attempt kernels: the state is double-buffered
         const float* g_end = (d.fused && hc.cur) ? d.GCT : d.G0T;
         DP_TRY(hipMemcpyAsync(g->grad_z0, a_end, sizeof(float) * BH, hipMemcpyDeviceToDevice, st));
-        // one "partial" of theta_size floats: a pure scatter into the destinations that exist
-        ReduceSegs segs{};
-        int n = 0;
-        for (int l = 0; l < p->n_layers; ++l) {
-            bool firstW = true, firstB = true;
-            for (int q = 0; q < l; ++q) {
-                if (p->layer_W[q] == p->layer_W[l]) firstW = false;
-                if (p->layer_b[q] == p->layer_b[l]) firstB = false;
-            }
-            if (firstW && g->grad_layer_W[l]) { segs.off[n] = y.gW_off[l]; segs.len[n] = p->layer_out[l] * p->layer_in[l]; segs.dst[n] = g->grad_layer_W[l]; ++n; }
-            if (firstB && g->grad_layer_b[l]) { segs.off[n] = y.gb_off[l]; segs.len[n] = p->layer_out[l]; segs.dst[n] = g->grad_layer_b[l]; ++n; }
-        }
-        if (g->grad_Wo) { segs.off[n] = y.gWo_off; segs.len[n] = y.rows * y.dlast; segs.dst[n] = g->grad_Wo; ++n; }
-        if (g->grad_bo) { segs.off[n] = y.gbo_off; segs.len[n] = y.rows; segs.dst[n] = g->grad_bo; ++n; }
-        segs.n = n;
-        if (n > 0) {
+        // one "partial" of theta_size floats: a pure scatter into the destinations that exist (the norm's segments)
+        if (segs.n > 0) {
             hipLaunchKernelGGL(ncde_reduce_partials, dim3((y.theta_size + 255) / 256), dim3(256), 0, st, g_end, 1, y.theta_size, segs);
             DP_TRY(hipGetLastError());
         }
     }
     return NCDE_OK;
-#undef DP_TRY
 }
 
 // Reverse sweep of a taped solve: dL/dz0 and dL/dtheta from the record of ncde_dp_solve(..., record).  Synchronises the stream
@@ -1070,53 +1080,35 @@ int ncde_dp_tape_backward_run(const NcdeProblem* p, const NcdeTimeSpec* ts, cons
     if (ws_bytes < w.total) { snprintf(err, errn, "workspace %zu B < %zu B", ws_bytes, w.total); return NCDE_ERR_WORKSPACE; }
     const int cap = tape_cap_of(p, n_t, record_bytes);
     if (cap < 1) { snprintf(err, errn, "record of %zu B holds no step", record_bytes); return NCDE_ERR_WORKSPACE; }
-    const TapeLayout tl = tape_layout(p, n_t, cap);
     char* base = (char*)ws;
-    char* rb = (char*)const_cast<void*>(record);
     DpArgs d;
     memset(&d, 0, sizeof(d));
     fill_kargs(p, y, &d.a);
     d.a.n_out = n_t;
     d.n_wg = y.n_wg; d.n_t = n_t; d.n_knots = p->n_knots; d.theta1 = y.theta_size + 1;
-    d.tape = (DpTapeHeader*)rb;
-    d.tape_steps = (DpStepRec*)(rb + tl.off_steps);
-    d.tape_x = (float*)(rb + tl.off_x);
-    d.tape_y = (float*)(rb + tl.off_y);
-    d.tape_cap = cap;
+    dp_bind_record(d, const_cast<void*>(record), tape_layout(p, n_t, cap));
     d.knots = ts->knots ? (const float*)(base + w.off_knots) : nullptr;
     d.KF = (float*)(base + w.off_kf); d.KBR = (float*)(base + w.off_kb);
     d.DZ0 = (float*)(base + w.off_dz0); d.F0B = (float*)(base + w.off_f0b); d.SCB = (float*)(base + w.off_scb);
     d.GP = (float*)(base + w.off_gp); d.PN2 = (double*)(base + w.off_pn2);
     d.grad_out = grad_out; d.gz0 = g->grad_z0;
     d.rtol = op->rtol; d.atol = op->atol;
-#define DP_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) { snprintf(err, errn, "%s failed: %s", #expr, hipGetErrorString(e_)); return NCDE_ERR_HIP; } \
-    } while (0)
-    std::vector<float> kf;
-    if (ts->knots) {
-        kf.resize(p->n_knots);
-        for (int i = 0; i < p->n_knots; ++i) kf[i] = (float)ts->knots[i];
-        DP_TRY(hipMemcpyAsync(base + w.off_knots, kf.data(), sizeof(float) * p->n_knots, hipMemcpyHostToDevice, st));
-        DP_TRY(hipStreamSynchronize(st));
-    }
+    DP_TRY(dp_upload_knots(p, ts, base + w.off_knots, st));
     DpTapeHeader hh;
-    DP_TRY(hipMemcpyAsync(&hh, rb, sizeof(hh), hipMemcpyDeviceToHost, st));
+    DP_TRY(hipMemcpyAsync(&hh, record, sizeof(hh), hipMemcpyDeviceToHost, st));
     DP_TRY(hipStreamSynchronize(st));
     if (hh.magic != DP_TAPE_MAGIC || hh.n_t != n_t || hh.n_steps < 1 || hh.n_steps > cap || hh.overflow) {
         snprintf(err, errn, "not the record of a finished taped solve of this problem (magic %x, n_t %d, steps %d / %d)", hh.magic, hh.n_t, hh.n_steps, cap);
         return NCDE_ERR_INVALID;
     }
-    size_t lds = sizeof(float) * (size_t)(7 * y.HS + ((y.L > 0 ? y.L : 1) + 4) * y.DS + 2 * y.Cp * 16 + 4 * 16 * 17);
-    const size_t red_bytes = 4 * 256 * sizeof(double);
-    d.gacc_in_lds = lds + sizeof(float) * (size_t)d.theta1 + red_bytes <= (size_t)kLdsLimit;
-    if (d.gacc_in_lds) lds += sizeof(float) * (size_t)d.theta1;
+    const DpLds sweep = dp_lds(y, kDpTapeSweep, d.theta1);
+    const size_t lds = sweep.launch;
+    d.gacc_in_lds = sweep.gacc;
     DP_TRY(ncde_lds_optin((const void*)ncde_dp_tape_backward, lds));
     DP_TRY(ncde_lds_optin((const void*)ncde_dp_tape_finish, lds));
     if (ncde_dpf_tape_supported(p)) {      // the sweep on the fused stage machinery (ncde_adaptive_fast.hip); same hand-over to the finish launches
         d.WP = (float*)(base + w.off_wp);
-        const int rc = ncde_dpf_tape_launch(p, &d, sizeof(d), st);
+        const int rc = ncde_dpf_tape_launch(p, d, st);
         if (rc != NCDE_OK) { snprintf(err, errn, "fused taped sweep failed (%d)", rc); return rc; }
     } else {
         hipLaunchKernelGGL(ncde_dp_tape_backward, dim3(y.n_wg), dim3(GEN_THREADS), lds, st, d);
@@ -1125,26 +1117,9 @@ int ncde_dp_tape_backward_run(const NcdeProblem* p, const NcdeTimeSpec* ts, cons
     hipLaunchKernelGGL(ncde_dp_tape_finish, dim3(y.n_wg), dim3(GEN_THREADS), lds, st, d, 2);
     DP_TRY(hipGetLastError());
     // per-workgroup partials have stride theta_size + 1 (the time slot): compact sum via the common reduction on a strided view
-    {
-        ReduceSegs segs{};
-        int n = 0;
-        for (int l = 0; l < p->n_layers; ++l) {
-            bool firstW = true, firstB = true;
-            for (int q = 0; q < l; ++q) {
-                if (p->layer_W[q] == p->layer_W[l]) firstW = false;
-                if (p->layer_b[q] == p->layer_b[l]) firstB = false;
-            }
-            if (firstW) { segs.off[n] = y.gW_off[l]; segs.len[n] = p->layer_out[l] * p->layer_in[l]; segs.dst[n] = g->grad_layer_W[l]; ++n; }
-            if (firstB) { segs.off[n] = y.gb_off[l]; segs.len[n] = p->layer_out[l]; segs.dst[n] = g->grad_layer_b[l]; ++n; }
-        }
-        segs.off[n] = y.gWo_off; segs.len[n] = y.rows * y.dlast; segs.dst[n] = g->grad_Wo; ++n;
-        segs.off[n] = y.gbo_off; segs.len[n] = y.rows; segs.dst[n] = g->grad_bo; ++n;
-        segs.n = n;
-        for (int i = 0; i < n; ++i)
-            if (!segs.dst[i]) { snprintf(err, errn, "NcdeGrads: NULL destination for a parameter gradient"); return NCDE_ERR_INVALID; }
-        hipLaunchKernelGGL(ncde_reduce_partials, dim3((d.theta1 + 255) / 256), dim3(256), 0, st, d.GP, y.n_wg, d.theta1, segs);
-        DP_TRY(hipGetLastError());
-    }
+    ReduceSegs segs{};
+    if (!build_segs(p, y, g, kSegsRefuseNull, &segs)) { snprintf(err, errn, "NcdeGrads: NULL destination for a parameter gradient"); return NCDE_ERR_INVALID; }
+    hipLaunchKernelGGL(ncde_reduce_partials, dim3((d.theta1 + 255) / 256), dim3(256), 0, st, d.GP, y.n_wg, d.theta1, segs);
+    DP_TRY(hipGetLastError());
     return NCDE_OK;
-#undef DP_TRY
 }

@@ -1369,17 +1369,19 @@ constexpr size_t dpa_lds() {      // the kernels' own layout; the assertion: the
                   "dynamic LDS of the fused adjoint / sweep moved: the 160 KB gate and the dispatch table move with it");
     return L::BYTES;
 }
-size_t dpa_lds_bytes(int nl) { return nl == 1 ? dpa_lds<1>() : (nl == 2 ? dpa_lds<2>() : dpa_lds<3>()); }      // nl <= 3: every caller asks ncde_dpf_supported first
-template <int NL>
-DpfKernel dpa_kernel() { return (DpfKernel)ncde_dpf_adj<32, 32, 20, NL>; }
-DpfKernel dpa_pick(int nl) { return nl == 1 ? dpa_kernel<1>() : (nl == 2 ? dpa_kernel<2>() : (nl == 3 ? dpa_kernel<3>() : nullptr)); }      // (NL = 4 does not fit the 160 KB of LDS)
+// The (32, 32, 20) adjoint and taped sweep by layer count, [NL - 1]; 1 <= NL <= kDpaMaxNL: every caller asks ncde_dpf_supported first
+// (NL = 4 does not fit the 160 KB of LDS).  Columns, and kDpaTape further down, not one table of rows: the kernels lie in the code object
+// in the order this file first names them, and their pc-relative addresses of the tableau move with it.
+constexpr int kDpaMaxNL = 3;
+const size_t kDpaLds[kDpaMaxNL] = {dpa_lds<1>(), dpa_lds<2>(), dpa_lds<3>()};      // dynamic LDS of both kernels
+const DpfKernel kDpaAdj[kDpaMaxNL] = {(DpfKernel)ncde_dpf_adj<32, 32, 20, 1>, (DpfKernel)ncde_dpf_adj<32, 32, 20, 2>, (DpfKernel)ncde_dpf_adj<32, 32, 20, 3>};
 }  // namespace
 
 bool ncde_dpf_supported(const NcdeProblem* p, int adj) {
     if (p->flags & NCDE_FLAG_FORCE_GENERIC) return false;
     const int sh = dpf_shape(p);
     if (adj == 0) return sh != 0;
-    if (adj == 1) return sh == 1 && p->n_layers <= 3 && dpa_lds_bytes(p->n_layers) + 512 <= 160 * 1024;      // (32, 32, 20) set, <= 3 layers (include/ncde_hip.h); 512 B: static LDS
+    if (adj == 1) return sh == 1 && p->n_layers <= kDpaMaxNL && kDpaLds[p->n_layers - 1] + 512 <= 160 * 1024;      // (32, 32, 20) set, <= 3 layers (include/ncde_hip.h); 512 B: static LDS
     return false;
 }
 
@@ -1400,14 +1402,11 @@ size_t ncde_dpf_pack_floats(const NcdeProblem* p, int adj) {
 }
 
 // once per solve, before the first attempt: the per-lane weight image
-int ncde_dpf_prepare(const NcdeProblem* p, const void* dp_args, size_t dp_args_bytes, int adj, hipStream_t st) {
-    if (dp_args_bytes != sizeof(DpArgs) || !ncde_dpf_supported(p, adj)) return NCDE_ERR_UNSUPPORTED;
-    DpArgs d;
-    memcpy(&d, dp_args, sizeof(d));
+int ncde_dpf_prepare(const NcdeProblem* p, const DpArgs& d, int adj, hipStream_t st) {
+    if (!ncde_dpf_supported(p, adj)) return NCDE_ERR_UNSUPPORTED;
     if (adj) {
         hipLaunchKernelGGL((ncde_dpa_pack<32, 32, 20, 3>), dim3(1), dim3(256), 0, st, d);
-        const size_t lds = dpa_lds_bytes(p->n_layers);
-        if (hipFuncSetAttribute((const void*)dpa_pick(p->n_layers), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return NCDE_ERR_HIP;
+        if (ncde_lds_optin((const void*)kDpaAdj[p->n_layers - 1], kDpaLds[p->n_layers - 1]) != hipSuccess) return NCDE_ERR_HIP;
     } else if (dpf_shape(p) == 1) {
         hipLaunchKernelGGL((ncde_dpf_pack<32, 32, 20>), dim3(1), dim3(256), 0, st, d);
     } else {
@@ -1416,30 +1415,28 @@ int ncde_dpf_prepare(const NcdeProblem* p, const void* dp_args, size_t dp_args_b
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
+namespace {
+const DpfKernel kDpaTape[kDpaMaxNL] = {(DpfKernel)ncde_dpf_tape<32, 32, 20, 1>, (DpfKernel)ncde_dpf_tape<32, 32, 20, 2>, (DpfKernel)ncde_dpf_tape<32, 32, 20, 3>};
+}  // namespace
+
 // reverse sweep of a taped solve: weight image + the persistent sweep (the caller launches ncde_dp_tape_finish afterwards, as before)
 bool ncde_dpf_tape_supported(const NcdeProblem* p) { return ncde_dpf_supported(p, 1); }
 const char* ncde_dpf_tape_kernel_name(const NcdeProblem* p) { return ncde_dpf_tape_supported(p) ? "ncde_dpf_tape<H32,HH32,C20,fp32 MFMA>" : nullptr; }
-int ncde_dpf_tape_launch(const NcdeProblem* p, const void* dp_args, size_t dp_args_bytes, hipStream_t st) {
-    if (dp_args_bytes != sizeof(DpArgs) || !ncde_dpf_tape_supported(p)) return NCDE_ERR_UNSUPPORTED;
-    DpArgs d;
-    memcpy(&d, dp_args, sizeof(d));
-    const int nl = p->n_layers;
-    const DpfKernel k = nl == 1 ? (DpfKernel)ncde_dpf_tape<32, 32, 20, 1> : (nl == 2 ? (DpfKernel)ncde_dpf_tape<32, 32, 20, 2>
-                                                                             : (DpfKernel)ncde_dpf_tape<32, 32, 20, 3>);      // nl <= 3 (ncde_dpf_supported)
-    const size_t lds = dpa_lds_bytes(nl);
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return NCDE_ERR_HIP;
+int ncde_dpf_tape_launch(const NcdeProblem* p, const DpArgs& d, hipStream_t st) {
+    if (!ncde_dpf_tape_supported(p)) return NCDE_ERR_UNSUPPORTED;
+    const DpfKernel k = kDpaTape[p->n_layers - 1];
+    const size_t lds = kDpaLds[p->n_layers - 1];
+    if (ncde_lds_optin((const void*)k, lds) != hipSuccess) return NCDE_ERR_HIP;
     hipLaunchKernelGGL((ncde_dpa_pack<32, 32, 20, 3>), dim3(1), dim3(256), 0, st, d);
     hipLaunchKernelGGL(k, dim3(d.n_wg), dim3(256), lds, st, d);
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }
 
-int ncde_dpf_launch(const NcdeProblem* p, const void* dp_args, size_t dp_args_bytes, int adj, int rounds, hipStream_t st) {
-    if (dp_args_bytes != sizeof(DpArgs) || !ncde_dpf_supported(p, adj)) return NCDE_ERR_UNSUPPORTED;
-    DpArgs d;
-    memcpy(&d, dp_args, sizeof(d));
+int ncde_dpf_launch(const NcdeProblem* p, const DpArgs& d, int adj, int rounds, hipStream_t st) {
+    if (!ncde_dpf_supported(p, adj)) return NCDE_ERR_UNSUPPORTED;
     if (adj) {
-        const DpfKernel k = dpa_pick(p->n_layers);
-        const size_t lds = dpa_lds_bytes(p->n_layers);
+        const DpfKernel k = kDpaAdj[p->n_layers - 1];
+        const size_t lds = kDpaLds[p->n_layers - 1];
         for (int r = 0; r < rounds; ++r) {
             hipLaunchKernelGGL(k, dim3(d.n_wg), dim3(256), lds, st, d);
             hipLaunchKernelGGL(ncde_dpf_reduce, dim3(d.n_rblk), dim3(256), 0, st, d);      // n_rblk = ceil(partial length / 64)

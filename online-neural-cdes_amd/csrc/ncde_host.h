@@ -170,33 +170,52 @@ inline void fill_kargs(const NcdeProblem* p, const Layout& y, KArgs* a) {
     a->Cc = p->reserved_ ? (p->reserved_ & 0xFFF) : p->channels;
 }
 
-// K4: sum the per-workgroup partials and scatter into the caller's buffers. 0 = ok, else NcdeStatus.
-inline int launch_reduce_partials(const NcdeProblem* p, const Layout& y, const NcdeGrads* g, const float* gpart, int n_part,
-                                  hipStream_t st) {
-    ReduceSegs segs{};
+// The parameter tensors of a problem as segments of the flat gradient layout, in the layout's order: per layer W then b (a tensor tied
+// to an earlier layer only at its first occurrence), Wo, bo, then Wg, bg (every field but the original) and Wr, br (GRU).  The one
+// list behind the partials reduce (K4) and the dopri5 adjoint's mixed error norm, which sums its segments in this order.
+enum SegPolicy {
+    kSegsNoDst,       // every segment, no destinations; `g` may be NULL (dopri5 forward: its norm has no parameter part to scatter)
+    kSegsSkipNull,    // a NULL destination = the tensor is not among the adjoint's parameters: it gets no segment
+    kSegsRefuseNull,  // a NULL destination is an error: the list is not built
+};
+inline bool build_segs(const NcdeProblem* p, const Layout& y, const NcdeGrads* g, SegPolicy policy, ReduceSegs* s) {
+    const NcdeGrads none{};
+    if (policy == kSegsNoDst) g = &none;
+    bool ok = true;
     int n = 0;
+    auto add = [&](int off, int len, float* dst) {
+        if (!dst && policy == kSegsRefuseNull) ok = false;
+        if (!dst && policy != kSegsNoDst) return;
+        s->off[n] = off; s->len[n] = len; s->dst[n] = dst; ++n;
+    };
     for (int l = 0; l < p->n_layers; ++l) {
         bool firstW = true, firstB = true;
         for (int q = 0; q < l; ++q) {
             if (p->layer_W[q] == p->layer_W[l]) firstW = false;
             if (p->layer_b[q] == p->layer_b[l]) firstB = false;
         }
-        if (firstW) { segs.off[n] = y.gW_off[l]; segs.len[n] = p->layer_out[l] * p->layer_in[l]; segs.dst[n] = g->grad_layer_W[l]; ++n; }
-        if (firstB) { segs.off[n] = y.gb_off[l]; segs.len[n] = p->layer_out[l]; segs.dst[n] = g->grad_layer_b[l]; ++n; }
+        if (firstW) add(y.gW_off[l], p->layer_out[l] * p->layer_in[l], g->grad_layer_W[l]);
+        if (firstB) add(y.gb_off[l], p->layer_out[l], g->grad_layer_b[l]);
     }
-    segs.off[n] = y.gWo_off; segs.len[n] = y.rows * y.dlast; segs.dst[n] = g->grad_Wo; ++n;
-    segs.off[n] = y.gbo_off; segs.len[n] = y.rows; segs.dst[n] = g->grad_bo; ++n;
+    add(y.gWo_off, y.rows * y.dlast, g->grad_Wo);
+    add(y.gbo_off, y.rows, g->grad_bo);
     if (p->field_kind != NCDE_FIELD_ORIGINAL) {
-        segs.off[n] = y.gWg_off; segs.len[n] = y.rows_g * y.dlast; segs.dst[n] = g->grad_Wg; ++n;
-        segs.off[n] = y.gbg_off; segs.len[n] = y.rows_g; segs.dst[n] = g->grad_bg; ++n;
+        add(y.gWg_off, y.rows_g * y.dlast, g->grad_Wg);
+        add(y.gbg_off, y.rows_g, g->grad_bg);
     }
     if (p->field_kind == NCDE_FIELD_GRU) {
-        segs.off[n] = y.gWr_off; segs.len[n] = y.d0 * y.d0; segs.dst[n] = g->grad_Wr; ++n;
-        segs.off[n] = y.gbr_off; segs.len[n] = y.d0; segs.dst[n] = g->grad_br; ++n;
+        add(y.gWr_off, y.d0 * y.d0, g->grad_Wr);
+        add(y.gbr_off, y.d0, g->grad_br);
     }
-    segs.n = n;
-    for (int i = 0; i < n; ++i)
-        if (!segs.dst[i]) return NCDE_ERR_INVALID;
+    s->n = n;
+    return ok;
+}
+
+// K4: sum the per-workgroup partials and scatter into the caller's buffers (every tensor needs one). 0 = ok, else NcdeStatus.
+inline int launch_reduce_partials(const NcdeProblem* p, const Layout& y, const NcdeGrads* g, const float* gpart, int n_part,
+                                  hipStream_t st) {
+    ReduceSegs segs{};
+    if (!build_segs(p, y, g, kSegsRefuseNull, &segs)) return NCDE_ERR_INVALID;
     hipLaunchKernelGGL(ncde_reduce_partials, dim3((y.theta_size + 255) / 256), dim3(256), 0, st, gpart, n_part, y.theta_size, segs);
     return hipGetLastError() == hipSuccess ? NCDE_OK : NCDE_ERR_HIP;
 }

@@ -532,6 +532,26 @@ def test_dispatch_table_matches_the_recorded_one():
         assert dt.query(h, case) == row[nk:], case
 
 
+def test_dopri5_dispatch_table_matches_the_recorded_one():
+    """tests/golden/dispatch_table_dopri5.json: the whole dopri5 grid of tools/dispatch_table.py (--dopri5), recorded from the library as it
+    was before the adaptive solver's host code was rebuilt on one segment list and one LDS rule.  ncde_dopri5_kernel_name and
+    ncde_dopri5_workspace_bytes of the passes 0 / 1 / 2, ncde_dopri5_record_bytes over four option sets, and the error text of each failing
+    query: every field of every row, and the grid is the one the tool walks today."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("dispatch_table", os.path.join(ROOT, "tools", "dispatch_table.py"))
+    dt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(dt)
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "dispatch_table_dopri5.json")))
+    assert tuple(fx["keys"]) == dt.DP_KEYS and tuple(fx["fields"]) == dt.DP_FIELDS
+    nk = len(fx["keys"])
+    assert [row[:nk] for row in fx["rows"]] == [[c[k] for k in dt.DP_KEYS] for c in dt.dp_cases()]
+    h = dt.dp_load(_lib.LIB_PATH)
+    for row in fx["rows"]:
+        case = dict(zip(fx["keys"], row[:nk]))
+        assert dt.dp_query(h, case) == row[nk:], case
+
+
 def _grad_slots(g, nl):
     """Every destination of an NcdeGrads as {name: address or None}."""
     d = {"z0": g.grad_z0}

@@ -10,6 +10,10 @@ ncde_last_error_string() of each query that fails.  Two libraries dispatch ident
 `--fixture FILE` writes the reduced table tests/test_host_cpu.py replays (tests/golden/dispatch_table.json): for every distinct
 (kernel name, error texts) of the full grid its first occurrences.  Generate it from the library the change is measured
 AGAINST, never from the code under test.
+
+`--dopri5` walks the adaptive solver's queries instead (DP_POINTS x interpolation x knot grid x n_t x batch): ncde_dopri5_kernel_name and
+ncde_dopri5_workspace_bytes of the passes 0 / 1 / 2 and ncde_dopri5_record_bytes over DP_RECORD_OPTIONS, each with its status / error
+text.  That grid is small: its fixture (tests/golden/dispatch_table_dopri5.json) is the whole table.
 """
 import argparse
 import ctypes
@@ -74,6 +78,102 @@ def build_problem(c):
     return p
 
 
+# ---- the adaptive solver's queries ----------------------------------------------------------------------------------------------------
+DP_KEYS = ("point", "C", "H", "HH", "nl", "tie", "field", "input", "flags", "interp", "user_knots", "n_t", "B")
+DP_FIELDS = tuple("%s%d%s" % (q, k, e) for q in ("name", "workspace_bytes") for k in (0, 1, 2) for e in ("", "_error")) + \
+    tuple("record_bytes_%d%s" % (i, e) for i in range(4) for e in ("", "_error"))
+DP_RECORD_OPTIONS = [(0.0, 0), (0.125, 0), (0.0, 50), (0.125, 50)]      # (min_step, max_num_steps)
+DP_KNOTS = 9
+DP_USER_KNOTS = (0.25, 0.75, 2.0, 2.75, 4.75, 5.25, 6.0, 7.25, 9.25)
+# tie: "inner" = one matrix for every layer but the first (the reference's stack), "none" = all distinct, "1=2" / "1=0" = only that pair
+DP_POINTS = [      # (name, C, H, HH, nl, tie, field kind, field input, flags)
+    ("h32_nl1", 20, 32, 32, 1, "inner", 0, 0, 0), ("h32_nl2", 20, 32, 32, 2, "inner", 0, 0, 0), ("h32_nl3", 20, 32, 32, 3, "inner", 0, 0, 0),
+    ("h32_nl4", 20, 32, 32, 4, "inner", 0, 0, 0), ("h32_pad_nl1", 5, 16, 24, 1, "inner", 0, 0, 0), ("h32_pad_nl2", 6, 24, 32, 2, "inner", 0, 0, 0),
+    ("h64", 4, 64, 64, 3, "inner", 0, 0, 0), ("h64_pad", 3, 48, 64, 2, "inner", 0, 0, 0), ("h40", 7, 40, 40, 2, "inner", 0, 0, 0),
+    ("h32_generic", 20, 32, 32, 3, "inner", 0, 0, _lib.FLAG_FORCE_GENERIC),
+    ("adjoint_lds", 80, 128, 512, 2, "inner", 0, 0, 0),       # beyond the adjoint's LDS
+    ("hidden_144", 4, 144, 64, 2, "inner", 0, 0, 0),          # hidden > 128: refused by the taped sweep
+    ("last_160", 4, 32, 160, 2, "inner", 0, 0, 0),            # last width > 128
+    ("gated", 20, 32, 32, 3, "inner", 1, 0, 0), ("evaluate", 20, 32, 32, 3, "inner", 0, 1, 0),      # both refused
+    ("tie_1=2", 20, 32, 32, 4, "1=2", 0, 0, 0), ("tie_1=0", 20, 32, 32, 3, "1=0", 0, 0, 0), ("tie_none", 20, 32, 32, 3, "none", 0, 0, 0),
+]
+
+
+def dp_cases():
+    for pt, interp, user, n_t, B in itertools.product(DP_POINTS, (0, 1), (0, 1), (2, 5), (1, 21, 4096)):
+        yield dict(zip(DP_KEYS, pt + (interp, user, n_t, B)))
+
+
+def dp_problem(c):
+    p = _lib.NcdeProblem()
+    p.abi_version = _lib.NCDE_ABI_VERSION
+    p.batch, p.n_knots, p.channels, p.hidden = c["B"], DP_KNOTS, c["C"], c["H"]
+    p.interp, p.method, p.output, p.flags = c["interp"], 0, _lib.OUT_INTERVAL, c["flags"]
+    p.n_layers = c["nl"]
+    slots = {"inner": lambda l: min(l, 1), "none": lambda l: l, "1=2": lambda l: 1 if l == 2 else l, "1=0": lambda l: 0 if l == 1 else l}[c["tie"]]
+    for l in range(c["nl"]):
+        d_in = (c["H"] + c["C"] if c["input"] == 1 else c["H"]) if l == 0 else c["HH"]
+        p.layer_in[l], p.layer_out[l] = d_in, c["HH"]
+        p.layer_W[l], p.layer_b[l] = 0x10000 * (slots(l) + 1), 0x10000 * (slots(l) + 1) + 0x8000
+    p.Wo, p.bo, p.coeffs, p.z0 = 0x300000, 0x310000, 0x400000, 0x500000
+    parts = 1 if c["interp"] == 0 else 4
+    p.coeffs_stride_b, p.coeffs_stride_t = DP_KNOTS * parts * c["C"], parts * c["C"]
+    p.field_kind, p.field_input = c["field"], c["input"]
+    if c["field"] == 1:
+        p.Wg, p.bg = 0x600000, 0x610000
+    return p
+
+
+def dp_load(path):
+    h = load(path)
+    P, TS, AO = ctypes.POINTER(_lib.NcdeProblem), ctypes.POINTER(_lib.NcdeTimeSpec), ctypes.POINTER(_lib.NcdeAdaptiveOptions)
+    h.ncde_dopri5_kernel_name.argtypes, h.ncde_dopri5_kernel_name.restype = [P, ctypes.c_int], ctypes.c_char_p
+    h.ncde_dopri5_workspace_bytes.argtypes, h.ncde_dopri5_workspace_bytes.restype = [P, TS, ctypes.c_int], ctypes.c_int64
+    h.ncde_dopri5_record_bytes.argtypes, h.ncde_dopri5_record_bytes.restype = [P, TS, AO], ctypes.c_int64
+    return h
+
+
+def dp_query(h, c):
+    """The values of DP_FIELDS: per query its result (None / a negative status where it fails) and, where it fails, the error text."""
+    p = ctypes.byref(dp_problem(c))
+    kn = DP_USER_KNOTS if c["user_knots"] else tuple(float(k) for k in range(DP_KNOTS))
+    n_t = c["n_t"]
+    t = (ctypes.c_double * n_t)(*[kn[0] + (kn[-1] - kn[0]) * i / (n_t - 1) for i in range(n_t)])
+    knots = (ctypes.c_double * DP_KNOTS)(*kn)
+    ts = _lib.NcdeTimeSpec()
+    ts.n_t, ts.time_is_f64, ts.t = n_t, 1, t
+    if c["user_knots"]:
+        ts.knots = knots
+    calls = [lambda k=k: h.ncde_dopri5_kernel_name(p, k) for k in (0, 1, 2)]
+    calls += [lambda k=k: h.ncde_dopri5_workspace_bytes(p, ctypes.byref(ts), k) for k in (0, 1, 2)]
+    for min_step, max_num_steps in DP_RECORD_OPTIONS:
+        o = _lib.NcdeAdaptiveOptions()
+        o.rtol, o.atol, o.min_step, o.max_num_steps = 1e-3, 1e-5, min_step, max_num_steps
+        calls.append(lambda o=o: h.ncde_dopri5_record_bytes(p, ctypes.byref(ts), ctypes.byref(o)))
+    out = []
+    for fn in calls:
+        h.ncde_num_outputs(None)      # a known error text in front of every query (see query)
+        r = fn()
+        failed = r is None or (not isinstance(r, bytes) and r < 0)
+        out += [r.decode() if isinstance(r, bytes) else r, h.ncde_last_error_string().decode() if failed else ""]
+    return out
+
+
+def dp_main(a):
+    h = dp_load(a.lib)
+    rows = [[c[k] for k in DP_KEYS] + dp_query(h, c) for c in dp_cases()]
+    text = "".join(" ".join("%s=%s" % kv for kv in zip(DP_KEYS, r)) + " | " + " | ".join(str(x) for x in r[len(DP_KEYS):]) + "\n" for r in rows)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
+    if a.fixture:
+        with open(a.fixture, "w") as f:
+            f.write('{"keys": %s,\n "fields": %s,\n "rows": [\n' % (json.dumps(list(DP_KEYS)), json.dumps(list(DP_FIELDS))))
+            f.write(",\n".join(json.dumps(r, separators=(",", ":")) for r in rows))
+            f.write("\n]}\n")
+    print(json.dumps({"lines": len(rows), "sha256": hashlib.sha256(text.encode()).hexdigest(), "fixture_rows": len(rows) if a.fixture else 0}))
+
+
 def load(path):
     h = ctypes.CDLL(path)
     P = ctypes.POINTER(_lib.NcdeProblem)
@@ -103,7 +203,10 @@ def main():
     ap.add_argument("--out", help="write the full table here (default: only its line count and SHA-256 are printed)")
     ap.add_argument("--fixture", help="write the reduced table (JSON) here")
     ap.add_argument("--per-key", type=int, default=2, help="occurrences kept per distinct (name, error texts) in the fixture")
+    ap.add_argument("--dopri5", action="store_true", help="the adaptive solver's queries instead (see above)")
     a = ap.parse_args()
+    if a.dopri5:
+        return dp_main(a)
     h = load(a.lib)
     out = open(a.out, "w") if a.out else None
     sha, n, seen, rows = hashlib.sha256(), 0, {}, []

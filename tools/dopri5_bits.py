@@ -13,7 +13,12 @@ Every case is driven by its replay lists, so the step sequence is the same whate
 adaptive adjoint's dz0 and parameter gradients, the taped backward's dz0 and parameter gradients.  NOT covered: NcdeGrads has no field for
 the adjoint's time component (vt -> gvt -> the partial's last entry; it only enters the error norm, which a replayed sequence ignores)
 nor for the sweep's Tpart / D1part (with `first_step` given, as here, they reach no output): that arithmetic is compared by the code
-objects' resource records and by reading, not by these bits."""
+objects' resource records and by reading, not by these bits.
+
+--shapes all: also h32_nl4, h64, h64_pad, h40 and h32_generic (`end` on the four axes, B = 21) -- the per-launch stage kernels and the
+un-fused taped sweep, i.e. every route of the host code.  PARTIAL: on h32-Cl-end-B21 and h32_generic-Cl-end-B21 the adaptive adjoint once
+more with adjoint_params = (Wo, bo): the layer tensors get no destination, so they leave the error norm's segments and the final
+scatter's alike (stored: dz0, dWo, dbo)."""
 import argparse
 import json
 import os
@@ -26,20 +31,24 @@ for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 
 SHAPES = ("h32", "h32_nl2", "h32_pad_nl1")
+MORE_SHAPES = ("h32_nl4", "h64", "h64_pad", "h40", "h32_generic")
+PARTIAL = ("h32-Cl-end-B21", "h32_generic-Cl-end-B21")
 
 
-def case_ids():
+def case_ids(shapes=SHAPES):
     import dopri5_cases as dc
     ids = []
-    for sh in SHAPES:
+    for sh in shapes:
         for ax in dc.AXES:
             ids.append("%s-%s-end-B%d" % (sh, ax, dc.BATCH))
-            ids += ["%s-%s-end-B%d" % (sh, ax, b) for b in dc.BATCH_EXTRA.get(sh, ())]
-        ids.append("%s-Cl-inside-B%d" % (sh, dc.BATCH))
+            if sh in SHAPES:
+                ids += ["%s-%s-end-B%d" % (sh, ax, b) for b in dc.BATCH_EXTRA.get(sh, ())]
+        if sh in SHAPES:
+            ids.append("%s-Cl-inside-B%d" % (sh, dc.BATCH))
     return ids
 
 
-def run_grid(out_path):
+def run_grid(out_path, shapes=SHAPES):
     import ctypes
     import torch
     import dopri5_cases as dc
@@ -47,7 +56,7 @@ def run_grid(out_path):
     import ncde_amd
     from ncde_amd import _lib, solver
     store, names = {}, {}
-    for cid in case_ids():
+    for cid in case_ids(shapes):
         a = dc.arrays(cid)
         coeffs = torch.from_numpy(a["coeffs"]).cuda()
         kn = None if a["knots"] is None else torch.from_numpy(a["knots"]).cuda()
@@ -56,18 +65,21 @@ def run_grid(out_path):
         prob = solver.build_problem(coeffs, a["interp"], torch.from_numpy(a["z0"]).cuda(), func.fused_spec(), "rk4", _lib.OUT_INTERVAL, a["flags"])
         names[cid] = [(_lib.lib().ncde_dopri5_kernel_name(ctypes.byref(prob), k) or b"?").decode() for k in (0, 1, 2)]
         assert all(k.startswith(w) for k, w in zip(names[cid], a["route"])), (cid, names[cid])
-        for mode, adjoint in (("adjoint", True), ("taped", False)):
+        for mode, adjoint in (("adjoint", True), ("taped", False)) + ((("partial", True),) if cid in PARTIAL else ()):
             func = gpu_util.CaseField(a["params"], a["layers"], "cuda")
             z0 = torch.from_numpy(a["z0"]).cuda().requires_grad_(True)
+            kept = ["Wo", "bo"] if mode == "partial" else a["names"]
+            more = {"adjoint_params": tuple(func.p[n] for n in kept)} if mode == "partial" else {}
             out = ncde_amd.cdeint(X, func, z0, torch.from_numpy(a["t"]).cuda(), adjoint=adjoint, method="dopri5", rtol=dc.RTOL, atol=dc.ATOL,
                                   kernel_flags=a["flags"], options={"first_step": a["fwd"][0][0], "_replay": a["fwd"]},
-                                  adjoint_options={"first_step": a["bwd"][0][0], "_replay": a["bwd"]})
+                                  adjoint_options={"first_step": a["bwd"][0][0], "_replay": a["bwd"]}, **more)
             (out * torch.from_numpy(a["grad_out"]).cuda()).sum().backward()
             torch.cuda.synchronize()
             store["%s/%s/z" % (cid, mode)] = out.detach().cpu().numpy()
             store["%s/%s/dz0" % (cid, mode)] = z0.grad.cpu().numpy()
-            for n in a["names"]:
+            for n in kept:
                 store["%s/%s/d%s" % (cid, mode, n)] = func.p[n].grad.cpu().numpy()
+            assert all(func.p[n].grad is None for n in a["names"] if n not in kept), (cid, mode)
         print(cid, names[cid], flush=True)
     store["kernel_names"] = np.array(json.dumps(names, sort_keys=True))
     np.savez(out_path, **store)
@@ -80,6 +92,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--compare", nargs=2, metavar=("A.npz", "B.npz"))
     ap.add_argument("--summary", help="--compare: also write the summary here")
+    ap.add_argument("--shapes", nargs="+", default=list(SHAPES), help="shapes of tests/dopri5_cases.py to run, or `all` (default: the three fused ones)")
     a = ap.parse_args()
     if a.compare:
         import family_bits
@@ -88,7 +101,7 @@ def main():
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
     assert a.out, "--out FILE.npz"
-    return run_grid(a.out)
+    return run_grid(a.out, SHAPES + MORE_SHAPES if a.shapes == ["all"] else tuple(a.shapes))
 
 
 if __name__ == "__main__":
