@@ -536,6 +536,39 @@ int64_t ncde_stream_field_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0:
 const char* ncde_stream_field_kernel_name(const NcdeProblem* p);   /* NULL on error */
 int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream);
 
+/* The field step on the Hermite cubic with backward differences: the five pairs of ncde_stream_step_field on the path of
+ * ncde_stream_step_hermite (same structs, same state; the problem says interp = NCDE_INTERP_CUBIC, s->rectilinear must be 0).
+ * With dn, b, two_c and three_d as stated for ncde_stream_step_hermite and s_j the stage's offset in the piece, per stage j:
+ *   matmul, derivative   stage 1 reads b, stage j > 1 reads b + (two_c + three_d * s_j) * s_j.
+ *   evaluate             stage 1 reads the row at the knot itself (the stream's last row before this fill), stage j > 1 reads
+ *                        that row + (b + (0.5 * two_c + three_d * s_j / 3) * s_j) * s_j -- the cubic branch of the batch kernels.
+ * The LDS plan is that of ncde_stream_step_field (the stage image takes the slot of the second rectilinear piece), so the query
+ * accepts exactly the shapes ncde_stream_field_workspace_bytes accepts; every weight is streamed.  NCDE_ERR_UNSUPPORTED: the GRU-gated
+ * field, the low-rank field, the original field with the matmul input (the message points to ncde_stream_step_hermite) and a plan
+ * above 160 KiB (the message carries the bytes).  NCDE_ERR_INVALID: what ncde_stream_step_field answers it for, interp other than
+ * NCDE_INTERP_CUBIC, s->rectilinear != 0.  A refusal launches nothing and leaves every state buffer untouched.  The kernel name is
+ * "ncde_stream_step_field_hermite". */
+int64_t ncde_stream_field_hermite_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_field_hermite_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_field_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream);
+
+/* The low-rank step: the same step, same structs and same state for NCDE_FIELD_LOWRANK (matmul input) with euler, midpoint or rk4.
+ * The problem carries the rank in flags (NCDE_FLAG_FIELD_RANK(R), 1 <= R <= channels), Wo / bo = M_h [H*R, last width],
+ * Wg / bg = M_o [R*C, last width] and at least one inner layer whose chain starts at hidden.  p->interp says the path:
+ *   NCDE_INTERP_LINEAR   a linear or rectilinear stream (s->rectilinear), the pieces and the left-piece rule of ncde_stream_step;
+ *   NCDE_INTERP_CUBIC    the Hermite cubic of ncde_stream_step_hermite (s->rectilinear must be 0): stage 1 reads b, stage j > 1
+ *                        b + (two_c + three_d * s_j) * s_j.
+ * The stage is that of the batch kernel ncde_fwd_lowrank with the heads streamed from L2 (the same sums in the same order).  ONE
+ * launch, one workgroup per 16 streams, no workspace.  NCDE_ERR_UNSUPPORTED, each with a message: any other field kind, an input
+ * other than matmul, and a shape whose LDS plan, 4 (5 HS + 2 DS + 5 CS + 48 + 16 ru16((hidden + channels) R)) bytes with
+ * HS = 16 ru16(hidden), DS = 16 max(ru16(hidden), ru16(layer widths)), CS = 16 ru4(channels), exceeds 160 KiB (the message carries
+ * the bytes).  NCDE_ERR_INVALID: a rank outside [1, channels], n_layers == 0, a layer chain that does not start at hidden or does
+ * not chain, a NULL Wo / bo / Wg / bg, and what ncde_stream_step answers it for about NcdeStream.  A refusal launches nothing and
+ * leaves every state buffer untouched.  The kernel name is "ncde_stream_step_lowrank" or "ncde_stream_step_lowrank_hermite". */
+int64_t ncde_stream_lowrank_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_lowrank_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_lowrank(const NcdeProblem* p, const NcdeStream* s, void* stream);
+
 /* The stacked step: n_stack chained linear CDE layers (StackedNeuralCDE: layer i + 1 reads layer i's hidden sequence as the linear
  * coefficients of its control) advance by s[0]->n_rows rows in ONE launch, one workgroup per 16 streams walking the layers of a row.
  *   layer 0    fills its row from s[0]->x exactly as ncde_stream_step does.

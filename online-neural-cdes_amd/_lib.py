@@ -156,6 +156,8 @@ EXPORTS = (
     "ncde_stream_hermite_workspace_bytes", "ncde_stream_hermite_kernel_name", "ncde_stream_step_hermite",
     "ncde_stream_stack_workspace_bytes", "ncde_stream_stack_kernel_name", "ncde_stream_stack_step",
     "ncde_stream_field_workspace_bytes", "ncde_stream_field_kernel_name", "ncde_stream_step_field",
+    "ncde_stream_field_hermite_workspace_bytes", "ncde_stream_field_hermite_kernel_name", "ncde_stream_step_field_hermite",
+    "ncde_stream_lowrank_workspace_bytes", "ncde_stream_lowrank_kernel_name", "ncde_stream_step_lowrank",
 )
 
 _LIB = None
@@ -241,6 +243,13 @@ def lib():
     h.ncde_stream_field_kernel_name.restype = ctypes.c_char_p
     h.ncde_stream_step_field.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
     h.ncde_stream_step_field.restype = ctypes.c_int
+    for family in ("field_hermite", "lowrank"):
+        getattr(h, "ncde_stream_%s_workspace_bytes" % family).argtypes = [P]
+        getattr(h, "ncde_stream_%s_workspace_bytes" % family).restype = ctypes.c_int64
+        getattr(h, "ncde_stream_%s_kernel_name" % family).argtypes = [P]
+        getattr(h, "ncde_stream_%s_kernel_name" % family).restype = ctypes.c_char_p
+        getattr(h, "ncde_stream_step_%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream), vp]
+        getattr(h, "ncde_stream_step_%s" % family).restype = ctypes.c_int
     PP, SS = ctypes.POINTER(P), ctypes.POINTER(ctypes.POINTER(NcdeStream))      # one pointer per layer of the stack
     h.ncde_stream_stack_workspace_bytes.argtypes = [PP, ctypes.c_int]
     h.ncde_stream_stack_workspace_bytes.restype = ctypes.c_int64

@@ -19,8 +19,9 @@
 // default_stage hands load_dx at the stream's own step index, (n + offset) - n in fp32.
 //
 // The phases are device functions of their own (stream_load_state .. stream_store_state); ncde_stream_stack_step runs them layer by
-// layer for a chain of linear CDEs in one launch (see StreamStackArgs), and ncde_stream_step_field runs them around the stage of the
-// vector-field variants (the minimal-gated field, the evaluate / derivative inputs; see above that kernel).
+// layer for a chain of linear CDEs in one launch (see StreamStackArgs), ncde_stream_step_field / ncde_stream_step_field_hermite run
+// them around the stage of the vector-field variants (the minimal-gated field, the evaluate / derivative inputs; see above that
+// kernel), and ncde_stream_step_lowrank around the stage of the low-rank field, on all three paths (see above that kernel).
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "ncde_common.h"
 #include "ncde_generic_stage.h"
 #include "ncde_host.h"
+#include "ncde_lowrank_stage.h"
 #include "ncde_timeloop.h"
 #include "ncde_variant_stage.h"
 
@@ -180,32 +182,51 @@ __device__ __forceinline__ void stream_combine(const KArgs& a, const StreamScrat
         if (last) t.Y0[e] = y0;
     }
 }
-template <bool HERMITE>
-__device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid) {
-    const int Hp = ru16(a.H), Cp = ru4(a.C), HS = Hp * 16, CS = Cp * 16;
+// HERMITE: the image stage j > 0 of the step reads, rebuilt into the DXB slot from b = DXL and dn = DXA at the stream's own frac.
+// start == NULL: the slope b + (2c + 3d s) s.  start != NULL (the field step's evaluate input; the streams' last rows before the
+// fill): the value start + (b + (2c / 2 + 3d s / 3) s) s, in the operation order of the batch loaders (vr_load_cin).
+__device__ __forceinline__ void stream_hermite_image(const KArgs& a, const StreamScratch& w, int j, int CS, int tid, const float* start = nullptr) {
+    for (int e = tid; e < CS; e += GEN_THREADS) {
+        const float frac = default_stage(a.method, (float)(w.STEP[e & 15] - 1) + stage_offset(a.method, j), 0x7fffffff).frac;
+        const float bb = w.DXL[e], dn = w.DXA[e];
+        const float two_c = 2.0f * (3.0f * (dn - bb) - dn + bb);
+        const float three_d = (dn - bb) - two_c;
+        if (start) {
+            float inner = 0.5f * two_c + (three_d * frac) / 3.0f;
+            inner = bb + inner * frac;
+            w.DXB[e] = start[e] + inner * frac;
+        } else {
+            const float inner = two_c + three_d * frac;
+            w.DXB[e] = bb + inner * frac;
+        }
+    }
+}
+// stage(dx): one evaluation of the field at YS with the dX/dt image dx into KO, ending behind a barrier (gen_stage_forward, or
+// the low-rank stage)
+template <bool HERMITE, class Stage>
+__device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid, Stage stage) {
+    const int HS = ru16(a.H) * 16, CS = ru4(a.C) * 16;
     const int S = n_stages(a.method);
     for (int pc = 0; pc < n_pieces; ++pc) {
         const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
         const float* dx_left = pc == 0 ? w.DXL : w.DXA;
         for (int j = 0; j < S; ++j) {
-            gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, j == 0 ? dx_left : dx_own, w.KO, Hp, Cp, tid);
+            stage(j == 0 ? dx_left : dx_own);
             stream_combine(a, w, t, j, HS, tid);
-            if constexpr (HERMITE) {
-                if (j + 1 < S) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
-                    for (int e = tid; e < CS; e += GEN_THREADS) {
-                        const float frac = default_stage(a.method, (float)(w.STEP[e & 15] - 1) + stage_offset(a.method, j + 1), 0x7fffffff).frac;
-                        const float bb = w.DXL[e], dn = w.DXA[e];
-                        const float two_c = 2.0f * (3.0f * (dn - bb) - dn + bb);
-                        const float three_d = (dn - bb) - two_c;
-                        const float inner = two_c + three_d * frac;
-                        w.DXB[e] = bb + inner * frac;
-                    }
-                }
+            if constexpr (HERMITE) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
+                if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid);
             }
             __syncthreads();
         }
     }
 }
+// the original field's stage for stream_stages
+struct StreamGenStage {
+    const KArgs& a;
+    const StreamScratch& w;
+    int tid;
+    __device__ __forceinline__ void operator()(const float* dx) const { gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, dx, w.KO, ru16(a.H), ru4(a.C), tid); }
+};
 
 // 5. readout of every stream of the tile at row r (a stream without a row: of its unchanged z)
 __device__ __forceinline__ void stream_readout(const KArgs& a, const StreamArgs& q, const StreamState& t, int r, int b0, int tid) {
@@ -260,7 +281,7 @@ __device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArg
     stream_load_state(a, q, t, w.YS, b0, tid);
     __syncthreads();
     for (int r = 0; r < q.m; ++r) {
-        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid);
+        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamGenStage{a, w, tid});
         stream_readout(a, q, t, r, b0, tid);
     }
     __syncthreads();
@@ -320,7 +341,7 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_stack_step
             const StreamState t = stream_stack_state(k, states, l);
             // the stage input of this layer (the last readers of YS, the layer before, ended behind a barrier; readers start behind fill's)
             for (int e = tid; e < ru16(a.H) * 16; e += GEN_THREADS) w.YS[e] = t.Y0[e];
-            if (stream_fill_row(a, k.q[l], w, t, below, r, b0, tid)) stream_stages<false>(a, w, t, 1, tid);
+            if (stream_fill_row(a, k.q[l], w, t, below, r, b0, tid)) stream_stages<false>(a, w, t, 1, tid, StreamGenStage{a, w, tid});
             stream_readout(a, k.q[l], t, r, b0, tid);
             below = t.Y0;
         }
@@ -371,7 +392,14 @@ __device__ void stream_field_value(const KArgs& a, float* UC, const float* start
     }
 }
 
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) {
+// HERMITE (ncde_stream_step_field_hermite): the same five pairs on the Hermite cubic with backward differences, one piece per row.
+// The fill leaves b = DXL, dn = DXA and the stream's last row before the fill in XS, as above.  Stage 1 sits on the knot and reads b
+// (matmul / derivative) or the knot's row XS (evaluate).  The image of stage j > 1 -- the slope b + (2c + 3d s) s, or for evaluate
+// the value XS + (b + (2c / 2 + 3d s / 3) s) s -- is rebuilt into the DXB slot (free: no rectilinear form; all 16 Cp entries, zeros
+// where the fill left zeros) by the combine phase of the stage before it, under that phase's barrier, as in stream_stages<true>.
+// Same plan, same areas; the second half of XS is written by the fill and not read.
+template <bool HERMITE>
+__device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * NCDE_TILE;
@@ -402,20 +430,28 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field
     for (int r = 0; r < q.m; ++r) {
         if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid, evaluate ? XS : nullptr)) {
             for (int pc = 0; pc < n_pieces; ++pc) {
-                const float* dx_own = pc != 0 ? w.DXB : w.DXA;
+                const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
                 const float* dx_left = pc == 0 ? w.DXL : w.DXA;
                 const float* start = XS + pc * CS;
                 for (int j = 0; j < S; ++j) {
                     const float* img = j == 0 ? dx_left : dx_own;
                     if (!matmul) {
-                        if (evaluate) stream_field_value(a, U + H * 16, start, dx_own, w.STEP, j, n_pieces, pc, tid);
-                        else
-                            for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = img[e];
+                        if constexpr (HERMITE) {      // evaluate: the knot's row, then the value image
+                            const float* src = (evaluate && j == 0) ? start : img;
+                            for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = src[e];
+                        } else {
+                            if (evaluate) stream_field_value(a, U + H * 16, start, dx_own, w.STEP, j, n_pieces, pc, tid);
+                            else
+                                for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = img[e];
+                        }
                         __syncthreads();
                     }
                     // (RU, RG, XB: the gru field's, which the host refuses -- valid addresses all the same, never touched)
                     vr_stage_forward(a, U, w.ACT0, w.ACT0, w.ACT0, w.ACT0, img, w.KO, nullptr, nullptr, nullptr, lds, Hp, Cp, DS, tid);
                     stream_combine(a, w, t, j, HS, tid);
+                    if constexpr (HERMITE) {      // the next stage's image (its reader starts behind the barrier; the last reader of DXB is done)
+                        if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid, evaluate ? XS : nullptr);
+                    }
                     __syncthreads();
                 }
             }
@@ -425,6 +461,75 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field
     __syncthreads();
     stream_store_state(a, q, w, t, b0, tid);
 }
+
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) { stream_field_body<false>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hermite_kernel(KArgs a, StreamArgs q) { stream_field_body<true>(a, q); }
+
+// The low-rank step (ncde_stream_step_lowrank, ncde_stream_step_lowrank_hermite): the phases and the stage loop of stream_step_body
+// around the stage of ncde_fwd_lowrank (ncde_lowrank_stage.h) -- the inner layers on dense_relu, ping-pong in ACT0 / ACT1, then
+// lr_heads into PQ, a barrier, and lr_contract of PQ with the stage's dX/dt image into KO.  The image is the one stream_stages hands
+// the original field: the left-piece rule on a linear or rectilinear stream, b and the rebuilt slope image in the DXB slot on the
+// Hermite path.  The heads are streamed (wl = NULL, wres_o = -1: one step per launch does not repay a resident copy), so the sums
+// run in the order of a batch ncde_fwd_lowrank solve WITHOUT residency.
+//
+// LDS, in floats (HS = ru16(H) 16, DS = 16 max(ru16(H), ru16(layer widths)), CS = ru4(C) 16, NTp = ru16((H + C) R)):
+//   YS, K1, K2, KO 4 HS | ACT0, ACT1 2 DS | DXL, DXA, DXB 3 CS | STEP, EVER 32 | state HS + 2 CS + 16 | PQ 16 NTp     = 5 HS + 2 DS + 5 CS + 48 + 16 NTp
+// What is read is inside what the launch cleared or a phase wrote, area by area:
+//   YS rows < Hp      from Y0 at load and by every combine; rows H .. Hp - 1 stay zero (Y0's pad rows are zero from the clear, KO's
+//                     are written as 0 by lr_contract), pad samples >= B never step and stay 0.  The first layer reads rows < ru4(H).
+//   ACT0 / ACT1       rows < ru16(dout) by dense_relu (rows >= dout as 0) before the next layer or lr_heads reads rows < ru4(dout).
+//   PQ rows < NTp     by lr_heads in every stage (rows NT .. NTp - 1 as 0), all 16 samples, before lr_contract reads rows < NT.
+//   KO rows < Hp      by lr_contract in every stage; K1 / K2 by stage 1 / 2 of a step before stage 2 / 3 reads them.
+//   DXL, DXA, DXB     all 16 Cp entries by every fill, zeros where c >= C, the sample is beyond B or the stream does not step;
+//                     lr_contract reads channels < C.  Hermite: DXB all 16 Cp entries again by every rebuild.
+// Every barrier sits in uniform control flow: the only branch around stages is the tile-wide any_step.
+struct StreamLowrankStage {
+    const KArgs& a;
+    const StreamScratch& w;
+    const LrDims& d;
+    float* PQ;
+    int tid;
+    __device__ __forceinline__ void operator()(const float* dx) const {
+        const int lane = tid & 63, wave = tid >> 6;
+        const float* in = w.YS;
+        for (int l = 0; l < a.n_layers; ++l) {
+            float* outb = (l & 1) ? w.ACT1 : w.ACT0;
+            dense_relu(a.W[l], a.b[l], a.dout[l], a.din[l], in, outb, wave, lane);
+            __syncthreads();
+            in = outb;
+        }
+        lr_heads(a, d, in, PQ, wave, lane);
+        __syncthreads();
+        lr_contract(d, PQ, dx, w.KO, ru16(a.H) * 16, tid);
+        __syncthreads();
+    }
+};
+
+template <bool HERMITE>
+__device__ __forceinline__ void stream_lowrank_body(const KArgs& a, const StreamArgs& q) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * NCDE_TILE;
+    const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
+    const LrDims d = lr_dims(a, lds);      // (wres_o = -1: d.wl = NULL)
+    StreamScratch w;
+    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w), a);
+    float* PQ = (float*)(t.CNT + 16);      // [NTp][16]
+    const int total = stream_scratch_floats(HS, DS, CS) + stream_state_floats(a) + d.NTp * 16;
+    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
+    __syncthreads();
+    stream_load_state(a, q, t, w.YS, b0, tid);
+    __syncthreads();
+    for (int r = 0; r < q.m; ++r) {
+        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
+        stream_readout(a, q, t, r, b0, tid);
+    }
+    __syncthreads();
+    stream_store_state(a, q, w, t, b0, tid);
+}
+
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<false>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hermite_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<true>(a, q); }
 
 namespace {
 
@@ -487,15 +592,16 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
 }
 
 // The problem as the field step reads it: what stream_problem reads, plus the gate head of a gated field, and a layer chain that
-// starts at the width of the field input, d0 = hidden (matmul) or hidden + channels.
-int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
-    const int rc = stream_problem_head(in, p, false);
+// starts at the width of the field input, d0 = hidden (matmul) or hidden + channels.  hermite: interp = NCDE_INTERP_CUBIC, the same
+// plan (the stage image takes the DXB slot).
+int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
+    const int rc = stream_problem_head(in, p, hermite);
     if (rc != NCDE_OK) return rc;
     if (p->field_kind == NCDE_FIELD_GRU)
         return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the GRU-gated field is not covered (its stage runs the inner net twice plus a reset gate)");
     if (p->field_kind == NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the low-rank field is not covered");
     if (p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is ncde_stream_step's");
+        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is %s's", hermite ? "ncde_stream_step_hermite" : "ncde_stream_step");
     if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return sfail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
     int d = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;      // d0
     for (int l = 0; l < p->n_layers; ++l) {
@@ -511,7 +617,44 @@ int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_
     return NCDE_OK;
 }
 
-enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2 };
+// The problem as the low-rank step reads it: what stream_problem reads, the rank in the top byte of flags and the second head
+// (Wo / bo = M_h [H R, dlast], Wg / bg = M_o [R C, dlast]).  interp says the path: NCDE_INTERP_LINEAR or NCDE_INTERP_CUBIC (Hermite).
+int stream_lowrank_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
+    const int rc = stream_problem_head(in, p, in && in->interp == NCDE_INTERP_CUBIC);
+    if (rc != NCDE_OK) return rc;
+    if (p->field_kind != NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field only (field_kind %d)", p->field_kind);
+    if (p->field_input != NCDE_INPUT_MATMUL)
+        return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field takes the matmul input only (field_input %d)", p->field_input);
+    const int rank = ncde_field_rank(p);
+    if (rank < 1 || rank > p->channels)
+        return sfail(NCDE_ERR_INVALID, "low-rank field: rank %d (NCDE_FLAG_FIELD_RANK) outside [1, channels = %d]", rank, p->channels);
+    if (p->n_layers < 1) return sfail(NCDE_ERR_INVALID, "online low-rank step: the low-rank kernels need at least one inner layer");
+    int d = p->hidden;
+    for (int l = 0; l < p->n_layers; ++l) {
+        if (p->layer_in[l] != d) return sfail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
+        if (p->layer_out[l] < 1) return sfail(NCDE_ERR_INVALID, "layer %d: out=%d", l, p->layer_out[l]);
+        if (!p->layer_W[l] || !p->layer_b[l]) return sfail(NCDE_ERR_INVALID, "layer %d: NULL weight/bias", l);
+        d = p->layer_out[l];
+    }
+    if (!p->Wo || !p->bo || !p->Wg || !p->bg) return sfail(NCDE_ERR_INVALID, "low-rank field: NULL Wo/bo (M_h) or Wg/bg (M_o)");
+    *y = make_layout(p);
+    const size_t ntp = ((size_t)(p->hidden + p->channels) * (size_t)rank + 15) & ~(size_t)15;
+    *lds = sizeof(float) * ((size_t)5 * y->HS + (size_t)2 * y->DS + (size_t)5 * y->Cp * 16 + 48 + 16 * ntp);
+    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
+    return NCDE_OK;
+}
+
+enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2, kStepFieldHermite = 3, kStepLowrank = 4 };
+
+// every step's problem, by kind
+int stream_problem_of(int kind, const NcdeProblem* p, NcdeProblem* q, Layout* y, size_t* lds) {
+    switch (kind) {
+        case kStepField: return stream_field_problem(p, q, y, lds);
+        case kStepFieldHermite: return stream_field_problem(p, q, y, lds, true);
+        case kStepLowrank: return stream_lowrank_problem(p, q, y, lds);
+        default: return stream_problem(p, q, y, lds, kind == kStepHermite);
+    }
+}
 
 }  // namespace
 
@@ -534,9 +677,9 @@ static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream
     NcdeProblem q;
     Layout y;
     size_t lds;
-    const bool hermite = kind == kStepHermite;
-    const int rc = kind == kStepField ? stream_field_problem(p, &q, &y, &lds) : stream_problem(p, &q, &y, &lds, hermite);
+    const int rc = stream_problem_of(kind, p, &q, &y, &lds);
     if (rc != NCDE_OK) return rc;
+    const bool hermite = q.interp == NCDE_INTERP_CUBIC;
     if (!s) return sfail(NCDE_ERR_INVALID, "stream is NULL");
     if (s->n_rows < 1) return sfail(NCDE_ERR_INVALID, "n_rows %d: at least one new row", s->n_rows);
     if (!s->x || !s->z || !s->last_row || !s->prev_dx || !s->count) return sfail(NCDE_ERR_INVALID, "NULL x / z / last_row / prev_dx / count");
@@ -555,11 +698,16 @@ static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream
     k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
     void (*kernel)(KArgs, StreamArgs) = hermite ? ncde_stream_step_hermite_kernel : ncde_stream_step_kernel;
     const char* name = hermite ? "ncde_stream_step_hermite" : "ncde_stream_step";
-    if (kind == kStepField) {      // every weight streamed
+    if (kind == kStepField || kind == kStepFieldHermite) {      // every weight streamed
         for (int l = 0; l < NCDE_MAX_LAYERS; ++l) a.wres[l] = -1;
         a.wres_o = a.wres_g = a.wres_r = -1;
-        kernel = ncde_stream_step_field_kernel;
-        name = "ncde_stream_step_field";
+        kernel = hermite ? ncde_stream_step_field_hermite_kernel : ncde_stream_step_field_kernel;
+        name = hermite ? "ncde_stream_step_field_hermite" : "ncde_stream_step_field";
+    }
+    if (kind == kStepLowrank) {      // the heads streamed
+        a.wres_o = -1;
+        kernel = hermite ? ncde_stream_step_lowrank_hermite_kernel : ncde_stream_step_lowrank_kernel;
+        name = hermite ? "ncde_stream_step_lowrank_hermite" : "ncde_stream_step_lowrank";
     }
     if (ncde_lds_optin((const void*)kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
     hipLaunchKernelGGL(kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
@@ -586,6 +734,41 @@ extern "C" const char* ncde_stream_field_kernel_name(const NcdeProblem* p) {
 }
 
 extern "C" int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepField); }
+
+extern "C" int64_t ncde_stream_field_hermite_workspace_bytes(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    const int rc = stream_field_problem(p, &q, &y, &lds, true);
+    return rc == NCDE_OK ? 0 : rc;
+}
+
+extern "C" const char* ncde_stream_field_hermite_kernel_name(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    return stream_field_problem(p, &q, &y, &lds, true) == NCDE_OK ? "ncde_stream_step_field_hermite" : nullptr;
+}
+
+extern "C" int ncde_stream_step_field_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepFieldHermite); }
+
+extern "C" int64_t ncde_stream_lowrank_workspace_bytes(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    const int rc = stream_lowrank_problem(p, &q, &y, &lds);
+    return rc == NCDE_OK ? 0 : rc;
+}
+
+extern "C" const char* ncde_stream_lowrank_kernel_name(const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    if (stream_lowrank_problem(p, &q, &y, &lds) != NCDE_OK) return nullptr;
+    return q.interp == NCDE_INTERP_CUBIC ? "ncde_stream_step_lowrank_hermite" : "ncde_stream_step_lowrank";
+}
+
+extern "C" int ncde_stream_step_lowrank(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepLowrank); }
 
 extern "C" int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p) {
     NcdeProblem q;

@@ -4,10 +4,10 @@
 observation row(s) causally, appends the one (linear, Hermite cubic) or two (rectilinear) pieces they add to the control path, takes
 one solver step per piece and returns the readout -- what ``NeuralCDE(return_sequences=True)`` on the whole prefix gives at the same
 knot, at the cost of the new pieces only.  On the GPU (fp32) a call is ONE launch (csrc/ncde_stream.hip): ``ncde_stream_step`` /
-``ncde_stream_step_hermite`` for the original field with the matmul input, ``ncde_stream_step_field`` for the minimal-gated field
-and for the evaluate / derivative inputs of those two fields on a linear or rectilinear path.  Anything else -- the GRU-gated and
-the low-rank field, a gated field or a direct input on the Hermite path, a shape whose LDS plan the kernel's query refuses -- takes
-the torch-op step below behind the once-only "unfused" warning.
+``ncde_stream_step_hermite`` for the original field with the matmul input, ``ncde_stream_step_field`` /
+``ncde_stream_step_field_hermite`` for the minimal-gated field and for the evaluate / derivative inputs of those two fields, and
+``ncde_stream_step_lowrank`` for the low-rank field, each on a linear, rectilinear or Hermite path.  Anything else -- the GRU-gated
+field, a shape whose LDS plan the kernel's query refuses -- takes the torch-op step below behind the once-only "unfused" warning.
 
 ``interpolation="cubic_hermite"`` is the smooth path that is causal: the Hermite cubic with backward differences
 (``hermite_cubic_coefficients_with_backward_differences(x, initial_value_if_nan=v, forward_fill=True)``), whose piece reads the new
@@ -234,22 +234,31 @@ class OnlineNeuralCDE:
         p.field_kind, p.field_input = _lib.FIELD_KIND[spec.kind], _lib.FIELD_INPUT[spec.mode]
         if spec.kind != "original":      # the second head, as solver.build_problem fills it
             p.Wg, p.bg = spec.Wg.data_ptr(), spec.bg.data_ptr()
+        if spec.kind == "lowrank":      # the rank travels in the top byte of flags
+            if not 1 <= spec.rank <= 255:
+                raise ValueError("low-rank field: rank %d outside [1, 255]" % spec.rank)
+            p.flags = _lib.FLAG_FIELD_RANK(spec.rank)
         return p
 
     def _kernel_entry(self, spec):
-        """(query, entry) of the step kernel that covers this field on this path, or None: the original field with the matmul input has
-        ncde_stream_step / ncde_stream_step_hermite; the minimal-gated field and the evaluate / derivative inputs of the two have
-        ncde_stream_step_field on a linear or rectilinear path."""
+        """(query, entry) of the step kernel that covers this field on this path, or None (the GRU-gated field): the original field
+        with the matmul input has ncde_stream_step / ncde_stream_step_hermite; the minimal-gated field and the evaluate / derivative
+        inputs of the two have ncde_stream_step_field / ncde_stream_step_field_hermite; the low-rank field has
+        ncde_stream_step_lowrank on all three paths (the problem's interp says which)."""
         if spec.kind == "original" and spec.mode == "matmul":
             if self.hermite:
                 return "ncde_stream_hermite_workspace_bytes", "ncde_stream_step_hermite"
             return "ncde_stream_workspace_bytes", "ncde_stream_step"
-        if spec.kind in ("original", "minimal") and not self.hermite:
+        if spec.kind in ("original", "minimal"):
+            if self.hermite:
+                return "ncde_stream_field_hermite_workspace_bytes", "ncde_stream_step_field_hermite"
             return "ncde_stream_field_workspace_bytes", "ncde_stream_step_field"
+        if spec.kind == "lowrank":
+            return "ncde_stream_lowrank_workspace_bytes", "ncde_stream_step_lowrank"
         return None
 
     def _use_kernel(self, x):
-        """The route, in the house style: CUDA fp32, a field one of the three step kernels covers (_kernel_entry) and a shape its query
+        """The route, in the house style: CUDA fp32, a field one of the step kernels covers (_kernel_entry) and a shape its query
         accepts take that kernel; anything else the torch-op step, behind the once-only warning.  Nothing here reads the device."""
         key = (x.device.type, x.dtype)
         if key in self._route:      # (the shapes of a module do not change: one query per device / dtype)

@@ -5,13 +5,18 @@
                                                                                # linear step at the same shape: legs alternate in ONE process
     python tools/time_stream.py --vector-field minimal --batches 16,4096 --prefixes ""      # the field step (ncde_stream_step_field) next
     python tools/time_stream.py --vector-field-type evaluate --batches 16,4096 --prefixes ""  # to the torch-op step on the same weights
+    python tools/time_stream.py --vector-field low-rank --interpolation linear --batches 16,4096 --prefixes "" --append --out F
+                                                                               # the low-rank step (ncde_stream_step_lowrank), any path
+    python tools/time_stream.py --interpolation cubic_hermite --vector-field minimal --batches 16,4096 --prefixes "" --append --out F
+                                                                               # the field step on the Hermite path; --append collects
+                                                                               # the runs of several invocations in one file
 
 Legs, per batch size B in {1, 16, 256, 4096}:
   online step      handle.step(x_k) of NeuralCDE.online, one new observation per call (one launch of ncde_stream_step)
   prefix k         what a server has without it: one NeuralCDE(return_sequences=False) call on the prefix of k observations
                    (k in {10, 100, 399}; the prefix's coefficients are built BEFORE the clock starts, which flatters this leg)
   torch-op step    with --vector-field / --vector-field-type other than original / matmul: a second handle over the same weights held
-                   on the torch-op step (online.py::_advance_torch) -- the route such a handle took before ncde_stream_step_field, and
+                   on the torch-op step (online.py::_advance_torch) -- the route such a handle took before its step kernel existed, and
                    the yardstick of that kernel
 Every call is followed by a device synchronise inside the timed window -- a server reads the prediction before the next observation
 arrives -- and the clock is the host's.  Every leg is warmed up, then the legs are timed ALTERNATING for ROUNDS rounds (STEPS online
@@ -39,7 +44,9 @@ def main():
     ap.add_argument("--prefixes", default="10,100,399")
     ap.add_argument("--interpolation", default="rectilinear", help="the causal control path: rectilinear, linear or cubic_hermite; a comma "
                     "list times one online leg per path (the prefix legs run on the first)")
-    ap.add_argument("--vector-field", default="original", help="original or minimal (the fields with a step kernel)")
+    ap.add_argument("--vector-field", default="original", help="original, minimal or low-rank (the fields with a step kernel)")
+    ap.add_argument("--sparsity", type=float, default=0.5, help="low-rank: rank = ceil(C (1 - sparsity))")
+    ap.add_argument("--append", action="store_true", help="--out holds {\"runs\": [...]}: add this run to it instead of overwriting")
     ap.add_argument("--vector-field-type", default="matmul", help="matmul, evaluate or derivative")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a timing needs the GPU"
@@ -47,6 +54,8 @@ def main():
     c = dict(bench.CONFIGS["cfg2"])
     prefixes = [int(k) for k in args.prefixes.split(",") if k]
     field = dict(vector_field=args.vector_field, vector_field_type=args.vector_field_type)
+    if args.vector_field == "low-rank":
+        field["sparsity"] = args.sparsity
     variant = (args.vector_field, args.vector_field_type) != ("original", "matmul")
     L = max(prefixes + [STEPS]) + 1
     paths = args.interpolation.split(",")
@@ -110,6 +119,12 @@ def main():
             print("B %5d median   %-20s %10.1f us/call  (min %.1f, max %.1f over %d rounds)" % (B, name, rec["median_us"], rec["min_us"], rec["max_us"], ROUNDS),
                   flush=True)
     if args.out:
+        if args.append:
+            runs = []
+            if os.path.exists(args.out):
+                with open(args.out) as fh:
+                    runs = json.load(fh)["runs"]
+            report = {"runs": runs + [report]}
         with open(args.out, "w") as fh:
             json.dump(report, fh, indent=1)
             fh.write("\n")
