@@ -569,6 +569,37 @@ int64_t ncde_stream_lowrank_workspace_bytes(const NcdeProblem* p);   /* 0, or < 
 const char* ncde_stream_lowrank_kernel_name(const NcdeProblem* p);   /* NULL on error */
 int ncde_stream_step_lowrank(const NcdeProblem* p, const NcdeStream* s, void* stream);
 
+/* The hybrid steps: the online half of the linear / rectilinear hybrid scheme (ncde_prepare_hybrid_*).  The same structs and the
+ * same state; the extra argument rectilinear_mask is a DEVICE pointer to uint8 [channels], 1 = the channel steps rectilinearly (the
+ * sparse channels R), 0 = it is interpolated linearly.  Time is channel 0 and rectilinear_mask[0] is 0.  The host never reads the
+ * mask.  A new row of a stream with count >= 1 is filled as for ncde_stream_step (every channel) and adds, in this order,
+ *   piece A   time and the linear channels move: da[c] = fill[c] - last[c] for c not in R, 0 for c in R.  Stage 1 reads prev_dx (da
+ *             itself at count == 1), every later stage da.
+ *   piece B   the sparse channels move: db[c] = fill[c] - last[c] for c in R, 0 elsewhere.  Stage 1 reads da, every later stage db.
+ *             Taken by a stream if and only if db[c] != 0 for some c -- the builder's kept knot; a re-observed unchanged value adds
+ *             no piece -- and skipped by the whole workgroup where none of its 16 streams takes it.
+ *   then      prev_dx = db where piece B was taken, da otherwise; last_row = fill, count += 1.
+ * Precondition, not checked (as "time is never NaN" is not): a stream's time strictly increases, so piece A always exists.
+ *   ncde_stream_step_hybrid          the fields of ncde_stream_step (the original field, matmul input)
+ *   ncde_stream_step_field_hybrid    those of ncde_stream_step_field with the matmul or derivative input
+ *   ncde_stream_step_lowrank_hybrid  that of ncde_stream_step_lowrank
+ * LDS plans in bytes, with the HS / DS / CS of the plain steps: 4 (5 HS + 2 DS + 5 CS + 64), 4 (3 DS + 4 HS + 5 CS + 64) and
+ * 4 (5 HS + 2 DS + 5 CS + 64 + 16 ru16((hidden + channels) R)).  NCDE_ERR_UNSUPPORTED, each with a message: what the plain step of
+ * the same family refuses, the evaluate input (its stage offset is the stream's knot index, which the state does not carry),
+ * interp = NCDE_INTERP_CUBIC (the Hermite path has no hybrid form) and a plan above 160 KiB.  NCDE_ERR_INVALID: what the plain step
+ * answers it for, a NULL rectilinear_mask, s->rectilinear != 0 (the mask replaces it) and s->time_index != 0.  There is no hybrid
+ * form of the stacked step.  A refusal launches nothing and leaves every state buffer untouched.  The kernel names are those of the
+ * entry points. */
+int64_t ncde_stream_hybrid_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_hybrid_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream);
+int64_t ncde_stream_field_hybrid_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_field_hybrid_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_field_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream);
+int64_t ncde_stream_lowrank_hybrid_workspace_bytes(const NcdeProblem* p);   /* 0, or < 0: status code */
+const char* ncde_stream_lowrank_hybrid_kernel_name(const NcdeProblem* p);   /* NULL on error */
+int ncde_stream_step_lowrank_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream);
+
 /* The stacked step: n_stack chained linear CDE layers (StackedNeuralCDE: layer i + 1 reads layer i's hidden sequence as the linear
  * coefficients of its control) advance by s[0]->n_rows rows in ONE launch, one workgroup per 16 streams walking the layers of a row.
  *   layer 0    fills its row from s[0]->x exactly as ncde_stream_step does.

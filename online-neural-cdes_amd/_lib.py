@@ -158,6 +158,9 @@ EXPORTS = (
     "ncde_stream_field_workspace_bytes", "ncde_stream_field_kernel_name", "ncde_stream_step_field",
     "ncde_stream_field_hermite_workspace_bytes", "ncde_stream_field_hermite_kernel_name", "ncde_stream_step_field_hermite",
     "ncde_stream_lowrank_workspace_bytes", "ncde_stream_lowrank_kernel_name", "ncde_stream_step_lowrank",
+    "ncde_stream_hybrid_workspace_bytes", "ncde_stream_hybrid_kernel_name", "ncde_stream_step_hybrid",
+    "ncde_stream_field_hybrid_workspace_bytes", "ncde_stream_field_hybrid_kernel_name", "ncde_stream_step_field_hybrid",
+    "ncde_stream_lowrank_hybrid_workspace_bytes", "ncde_stream_lowrank_hybrid_kernel_name", "ncde_stream_step_lowrank_hybrid",
 )
 
 _LIB = None
@@ -249,6 +252,13 @@ def lib():
         getattr(h, "ncde_stream_%s_kernel_name" % family).argtypes = [P]
         getattr(h, "ncde_stream_%s_kernel_name" % family).restype = ctypes.c_char_p
         getattr(h, "ncde_stream_step_%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream), vp]
+        getattr(h, "ncde_stream_step_%s" % family).restype = ctypes.c_int
+    for family in ("hybrid", "field_hybrid", "lowrank_hybrid"):      # the per-channel mask (a device pointer) before the stream
+        getattr(h, "ncde_stream_%s_workspace_bytes" % family).argtypes = [P]
+        getattr(h, "ncde_stream_%s_workspace_bytes" % family).restype = ctypes.c_int64
+        getattr(h, "ncde_stream_%s_kernel_name" % family).argtypes = [P]
+        getattr(h, "ncde_stream_%s_kernel_name" % family).restype = ctypes.c_char_p
+        getattr(h, "ncde_stream_step_%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream), vp, vp]
         getattr(h, "ncde_stream_step_%s" % family).restype = ctypes.c_int
     PP, SS = ctypes.POINTER(P), ctypes.POINTER(ctypes.POINTER(NcdeStream))      # one pointer per layer of the stack
     h.ncde_stream_stack_workspace_bytes.argtypes = [PP, ctypes.c_int]

@@ -22,6 +22,10 @@
 // layer for a chain of linear CDEs in one launch (see StreamStackArgs), ncde_stream_step_field / ncde_stream_step_field_hermite run
 // them around the stage of the vector-field variants (the minimal-gated field, the evaluate / derivative inputs; see above that
 // kernel), and ncde_stream_step_lowrank around the stage of the low-rank field, on all three paths (see above that kernel).
+//
+// The linear / rectilinear hybrid path (the HYBRID instantiations: ncde_stream_step_hybrid, ncde_stream_step_field_hybrid,
+// ncde_stream_step_lowrank_hybrid; see "The hybrid step" below): a per-channel mask says which channels step rectilinearly, and the
+// second piece of a row is taken per stream, only where one of those channels changed.
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -38,6 +42,7 @@ struct StreamArgs {
     const float* x;
     long long xs_m, xs_b;
     const unsigned char* active;
+    const unsigned char* rmask;      // HYBRID: uint8 [C], 1 = the channel steps rectilinearly; NULL on every other kernel, which never reads it
     float init;
     float* z;
     float* last;
@@ -58,6 +63,7 @@ struct StreamScratch {
     float* DXB;      // second piece (rectilinear); HERMITE: the stage image
     int* STEP;       // steps at this row (0: no; else the step's index + 1)
     int* EVER;       // received a row in this launch
+    int* HASB;       // HYBRID: takes the second piece at this row (a sparse channel changed); NULL otherwise
 };
 struct StreamState {
     float* Y0;
@@ -71,9 +77,9 @@ __device__ __forceinline__ int stream_dp(const KArgs& a) {
     for (int l = 0; l < a.n_layers; ++l) Dp = max(Dp, ru16(a.dout[l]));
     return Dp;
 }
-__device__ __forceinline__ int stream_scratch_floats(int HS, int DS, int CS) { return 4 * HS + 2 * DS + 3 * CS + 32; }
+__device__ __forceinline__ int stream_scratch_floats(int HS, int DS, int CS, bool hybrid = false) { return 4 * HS + 2 * DS + 3 * CS + 32 + (hybrid ? 16 : 0); }
 __device__ __forceinline__ int stream_state_floats(const KArgs& a) { return ru16(a.H) * 16 + 2 * ru4(a.C) * 16 + 16; }
-__device__ __forceinline__ float* stream_carve_scratch(float* p, int HS, int DS, int CS, StreamScratch& w) {
+__device__ __forceinline__ float* stream_carve_scratch(float* p, int HS, int DS, int CS, StreamScratch& w, bool hybrid = false) {
     w.YS = p;
     w.ACT0 = w.YS + HS;
     w.ACT1 = w.ACT0 + DS;
@@ -85,7 +91,8 @@ __device__ __forceinline__ float* stream_carve_scratch(float* p, int HS, int DS,
     w.DXB = w.DXA + CS;
     w.STEP = (int*)(w.DXB + CS);
     w.EVER = w.STEP + 16;
-    return (float*)(w.EVER + 16);
+    w.HASB = hybrid ? w.EVER + 16 : nullptr;
+    return (float*)(w.EVER + (hybrid ? 32 : 16));
 }
 __device__ __forceinline__ StreamState stream_carve_state(float* p, const KArgs& a) {
     StreamState t;
@@ -123,8 +130,11 @@ __device__ __forceinline__ void stream_load_state(const KArgs& a, const StreamAr
 // starts != NULL (the field step's evaluate input): two further [c][s] images, the START ROWS of the two pieces -- starts[..] the
 // stream's last row before this fill, starts[CS + ..] the lagged row -- written in all 16 Cp entries like the dX/dt images (zero
 // for a stream that does not step).
+// HYBRID (see "The hybrid step" below): the lagged row holds the old values of the channels of q.rmask only, and the second piece
+// is per stream.  any_b (uniform, like the return value): whether any stream of the tile takes it at this row.
+template <bool HYBRID = false>
 __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, const float* from,
-                                               int r, int b0, int tid, float* starts = nullptr) {
+                                               int r, int b0, int tid, float* starts = nullptr, int* any_b = nullptr) {
     const int C = a.C, Cp = ru4(C);
     for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
         const int s = e / Cp, c = e - s * Cp, b = b0 + s;
@@ -135,11 +145,14 @@ __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs&
             const float last = t.LAST[c * 16 + s];
             const float fill = xv != xv ? (cnt == 0 ? q.init : last) : xv;
             if (cnt > 0) {
-                const float mid = (q.rect && c != q.ti) ? last : fill;      // rectilinear: the lagged row (new time, old values)
+                float mid;
+                if constexpr (HYBRID) mid = q.rmask[c] ? last : fill;      // hybrid: the lagged row keeps the sparse channels' old values
+                else mid = (q.rect && c != q.ti) ? last : fill;            // rectilinear: the lagged row (new time, old values)
                 da = mid - last;
                 db = fill - mid;
                 dl = cnt == 1 ? da : t.PDX[c * 16 + s];
-                t.PDX[c * 16 + s] = q.rect ? db : da;
+                if constexpr (HYBRID) t.PDX[c * 16 + s] = da;      // (db below, behind the barrier, where the stream takes the second piece)
+                else t.PDX[c * 16 + s] = q.rect ? db : da;
                 xa = last;
                 xb = mid;
             }
@@ -160,19 +173,37 @@ __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs&
         w.STEP[tid] = act ? t.CNT[tid] : 0;       // the first row of a stream (count 0) initialises it: no solver step
         t.CNT[tid] += act;
         w.EVER[tid] |= act;
+        if constexpr (HYBRID) {      // db != 0 somewhere in the stream's column of the image (zero for a stream that does not step)
+            int has = 0;
+            for (int c = 0; c < C; ++c) has |= w.DXB[c * 16 + tid] != 0.0f;
+            w.HASB[tid] = has;       // written every row: the flag of the row before is gone
+        }
     }
     __syncthreads();
     int any_step = 0;
 #pragma unroll
     for (int s = 0; s < 16; ++s) any_step |= w.STEP[s];
+    if constexpr (HYBRID) {
+        int any = 0;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) any |= w.HASB[s];
+        *any_b = any;
+        // prev_dx of a stream that takes the second piece is that piece's.  The same thread owns (c, s) in the loop above at every
+        // row, and the state is stored behind a barrier: no barrier of its own.
+        for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
+            const int s = e / Cp, c = e - s * Cp;
+            if (c < C && w.HASB[s]) t.PDX[c * 16 + s] = w.DXB[c * 16 + s];
+        }
+    }
     return any_step;
 }
 
 // 4. the Butcher stages, one step per piece.  stream_combine: the bookkeeping of stage j for the streams that step (the caller's
-// barrier follows)
-__device__ __forceinline__ void stream_combine(const KArgs& a, const StreamScratch& w, const StreamState& t, int j, int HS, int tid) {
+// barrier follows).  flags: which streams take the piece -- STEP, or on the second piece of a hybrid row HASB; a stream that does
+// not keeps its YS / K1 / K2 / Y0.
+__device__ __forceinline__ void stream_combine(const KArgs& a, const StreamScratch& w, const StreamState& t, const int* flags, int j, int HS, int tid) {
     for (int e = tid; e < HS; e += GEN_THREADS) {
-        if (!w.STEP[e & 15]) continue;
+        if (!flags[e & 15]) continue;
         float y0 = t.Y0[e], k1 = w.K1[e], k2 = w.K2[e];
         bool last;
         const float ys = StageCombine::apply(a.method, j, w.KO[e], 1.0f, y0, k1, k2, last);
@@ -203,16 +234,20 @@ __device__ __forceinline__ void stream_hermite_image(const KArgs& a, const Strea
 }
 // stage(dx): one evaluation of the field at YS with the dX/dt image dx into KO, ending behind a barrier (gen_stage_forward, or
 // the low-rank stage)
-template <bool HERMITE, class Stage>
+// HYBRID: the second piece (n_pieces = 2 only where a stream of the tile takes it: uniform) combines under HASB -- every stream at
+// the start of a piece has YS = Y0 (from the load, or from the last combine it took part in), so one that sits the piece out
+// keeps both, and the KO the stage forms for it is never read.
+template <bool HERMITE, bool HYBRID = false, class Stage>
 __device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid, Stage stage) {
     const int HS = ru16(a.H) * 16, CS = ru4(a.C) * 16;
     const int S = n_stages(a.method);
     for (int pc = 0; pc < n_pieces; ++pc) {
         const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
         const float* dx_left = pc == 0 ? w.DXL : w.DXA;
+        const int* flags = (HYBRID && pc != 0) ? w.HASB : w.STEP;
         for (int j = 0; j < S; ++j) {
             stage(j == 0 ? dx_left : dx_own);
-            stream_combine(a, w, t, j, HS, tid);
+            stream_combine(a, w, t, flags, j, HS, tid);
             if constexpr (HERMITE) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
                 if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid);
             }
@@ -267,21 +302,39 @@ __device__ __forceinline__ void stream_store_state(const KArgs& a, const StreamA
     if (tid < 16 && b0 + tid < a.B && w.EVER[tid]) q.count[b0 + tid] = t.CNT[tid];
 }
 
-template <bool HERMITE>
+// The hybrid step (HYBRID; DESIGN.md 5.14 "Hybrid step"): the online half of linear_rectilinear_hybrid_coeffs.  Time is channel 0;
+// q.rmask [C] marks the sparse channels R, every other channel is linear.  A new row of a stream with count > 0 adds
+//   piece A   time and the linear channels move:  da[c] = fill[c] - last[c] (c not in R), 0 (c in R);  stage 1 reads prev_dx (da itself
+//             at count == 1), the later stages da;
+//   piece B   the sparse channels move:  db[c] = fill[c] - last[c] (c in R), 0 elsewhere;  stage 1 reads da, the later stages db.
+// Piece B is taken by the streams with db != 0 in some channel only (the builder keeps a knot only where a sparse channel
+// changed): the fill phase leaves that per stream in HASB, 16 flags next to STEP and EVER, rewritten at every row between the fill
+// phase's two barriers.  Piece B combines under HASB (a flag implies STEP: db is zero for a stream that does not step), and is
+// skipped altogether -- S stages instead of 2 S -- where no stream of the tile takes it; that branch is uniform, read from the 16
+// flags as any_step is.  prev_dx after the row is db where B was taken and da otherwise.  Precondition: a stream's time strictly
+// increases, so piece A always exists (not checked).
+// LDS: the plan of the non-hybrid body plus the 16 flags; the field body drops XS (no evaluate input on this path).
+template <bool HERMITE, bool HYBRID = false>
 __device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * NCDE_TILE;
     const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
     StreamScratch w;
-    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w), a);
-    const int total = stream_scratch_floats(HS, DS, CS) + stream_state_floats(a);
+    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w, HYBRID), a);
+    const int total = stream_scratch_floats(HS, DS, CS, HYBRID) + stream_state_floats(a);
     for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
     __syncthreads();
     stream_load_state(a, q, t, w.YS, b0, tid);
     __syncthreads();
     for (int r = 0; r < q.m; ++r) {
-        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamGenStage{a, w, tid});
+        if constexpr (HYBRID) {
+            int any_b;
+            if (stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b))
+                stream_stages<false, true>(a, w, t, any_b ? 2 : 1, tid, StreamGenStage{a, w, tid});
+        } else {
+            if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamGenStage{a, w, tid});
+        }
         stream_readout(a, q, t, r, b0, tid);
     }
     __syncthreads();
@@ -290,6 +343,7 @@ __device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArg
 
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) { stream_step_body<false>(a, q); }
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hermite_kernel(KArgs a, StreamArgs q) { stream_step_body<true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hybrid_kernel(KArgs a, StreamArgs q) { stream_step_body<false, true>(a, q); }
 
 // The stacked step (ncde_stream_stack_step): n_stack chained linear layers, layer l + 1 reading layer l's hidden state as its
 // observation.  Everything a layer reads of the one below is per stream, so the tile's workgroup walks the layers of a row with
@@ -398,7 +452,13 @@ __device__ void stream_field_value(const KArgs& a, float* UC, const float* start
 // the value XS + (b + (2c / 2 + 3d s / 3) s) s -- is rebuilt into the DXB slot (free: no rectilinear form; all 16 Cp entries, zeros
 // where the fill left zeros) by the combine phase of the stage before it, under that phase's barrier, as in stream_stages<true>.
 // Same plan, same areas; the second half of XS is written by the fill and not read.
-template <bool HERMITE>
+//
+// HYBRID (ncde_stream_step_field_hybrid; "The hybrid step" above): the matmul and derivative inputs -- the host refuses evaluate,
+// whose stage offset needs the stream's knot index, which the state does not carry.  No XS, 16 flags more:
+//   U, ACT0, ACT1 3 DS | K1, K2, KO 3 HS | DXL, DXA, DXB 3 CS | STEP, EVER, HASB 48 | state HS + 2 CS + 16     = 3 DS + 4 HS + 5 CS + 64
+// The branch around the second piece is the tile-wide any_b; its combine runs under HASB, so a stream that sits the piece out
+// keeps U rows < Hp, K1, K2 and Y0 (its control rows of U are rewritten from the images, whose entries are its own).
+template <bool HERMITE, bool HYBRID = false>
 __device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -416,23 +476,34 @@ __device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamAr
     w.DXL = w.KO + HS;
     w.DXA = w.DXL + CS;
     w.DXB = w.DXA + CS;
-    float* XS = w.DXB + CS;      // the pieces' start rows (evaluate)
-    w.STEP = (int*)(XS + 2 * CS);
+    float* XS = w.DXB + CS;      // the pieces' start rows (evaluate); HYBRID: none
+    w.STEP = (int*)(XS + (HYBRID ? 0 : 2 * CS));
     w.EVER = w.STEP + 16;
-    const StreamState t = stream_carve_state((float*)(w.EVER + 16), a);
+    w.HASB = HYBRID ? w.EVER + 16 : nullptr;
+    const StreamState t = stream_carve_state((float*)(w.EVER + (HYBRID ? 32 : 16)), a);
     float* U = w.YS;
-    const int total = 3 * DS + 4 * HS + 7 * CS + 48;
+    const int total = HYBRID ? 3 * DS + 4 * HS + 5 * CS + 64 : 3 * DS + 4 * HS + 7 * CS + 48;
     for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
     __syncthreads();
     stream_load_state(a, q, t, U, b0, tid);
     __syncthreads();
-    const int S = n_stages(a.method), n_pieces = q.rect ? 2 : 1;
+    const int S = n_stages(a.method);
+    int n_pieces = q.rect ? 2 : 1;
     for (int r = 0; r < q.m; ++r) {
-        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid, evaluate ? XS : nullptr)) {
+        int any_step;
+        if constexpr (HYBRID) {      // (evaluate is refused by the host: XS does not exist)
+            int any_b;
+            any_step = stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b);
+            n_pieces = any_b ? 2 : 1;
+        } else {
+            any_step = stream_fill_row(a, q, w, t, nullptr, r, b0, tid, evaluate ? XS : nullptr);
+        }
+        if (any_step) {
             for (int pc = 0; pc < n_pieces; ++pc) {
                 const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
                 const float* dx_left = pc == 0 ? w.DXL : w.DXA;
                 const float* start = XS + pc * CS;
+                const int* flags = (HYBRID && pc != 0) ? w.HASB : w.STEP;
                 for (int j = 0; j < S; ++j) {
                     const float* img = j == 0 ? dx_left : dx_own;
                     if (!matmul) {
@@ -448,7 +519,7 @@ __device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamAr
                     }
                     // (RU, RG, XB: the gru field's, which the host refuses -- valid addresses all the same, never touched)
                     vr_stage_forward(a, U, w.ACT0, w.ACT0, w.ACT0, w.ACT0, img, w.KO, nullptr, nullptr, nullptr, lds, Hp, Cp, DS, tid);
-                    stream_combine(a, w, t, j, HS, tid);
+                    stream_combine(a, w, t, flags, j, HS, tid);
                     if constexpr (HERMITE) {      // the next stage's image (its reader starts behind the barrier; the last reader of DXB is done)
                         if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid, evaluate ? XS : nullptr);
                     }
@@ -464,6 +535,7 @@ __device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamAr
 
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) { stream_field_body<false>(a, q); }
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hermite_kernel(KArgs a, StreamArgs q) { stream_field_body<true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hybrid_kernel(KArgs a, StreamArgs q) { stream_field_body<false, true>(a, q); }
 
 // The low-rank step (ncde_stream_step_lowrank, ncde_stream_step_lowrank_hermite): the phases and the stage loop of stream_step_body
 // around the stage of ncde_fwd_lowrank (ncde_lowrank_stage.h) -- the inner layers on dense_relu, ping-pong in ACT0 / ACT1, then
@@ -505,7 +577,8 @@ struct StreamLowrankStage {
     }
 };
 
-template <bool HERMITE>
+// HYBRID (ncde_stream_step_lowrank_hybrid; "The hybrid step" above): the same body, 16 flags more (HASB, behind EVER).
+template <bool HERMITE, bool HYBRID = false>
 __device__ __forceinline__ void stream_lowrank_body(const KArgs& a, const StreamArgs& q) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
@@ -513,15 +586,21 @@ __device__ __forceinline__ void stream_lowrank_body(const KArgs& a, const Stream
     const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
     const LrDims d = lr_dims(a, lds);      // (wres_o = -1: d.wl = NULL)
     StreamScratch w;
-    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w), a);
+    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w, HYBRID), a);
     float* PQ = (float*)(t.CNT + 16);      // [NTp][16]
-    const int total = stream_scratch_floats(HS, DS, CS) + stream_state_floats(a) + d.NTp * 16;
+    const int total = stream_scratch_floats(HS, DS, CS, HYBRID) + stream_state_floats(a) + d.NTp * 16;
     for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
     __syncthreads();
     stream_load_state(a, q, t, w.YS, b0, tid);
     __syncthreads();
     for (int r = 0; r < q.m; ++r) {
-        if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
+        if constexpr (HYBRID) {
+            int any_b;
+            if (stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b))
+                stream_stages<false, true>(a, w, t, any_b ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
+        } else {
+            if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
+        }
         stream_readout(a, q, t, r, b0, tid);
     }
     __syncthreads();
@@ -530,6 +609,7 @@ __device__ __forceinline__ void stream_lowrank_body(const KArgs& a, const Stream
 
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<false>(a, q); }
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hermite_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hybrid_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<false, true>(a, q); }
 
 namespace {
 
@@ -570,8 +650,15 @@ int stream_problem_head(const NcdeProblem* in, NcdeProblem* p, bool hermite) {
     return NCDE_OK;
 }
 
-int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
-    const int rc = stream_problem_head(in, p, hermite);
+// hybrid (the *_hybrid entry points): the linear path only -- the Hermite cubic has no hybrid form --, 16 flags more of LDS.
+int stream_hybrid_head(const NcdeProblem* in, NcdeProblem* p) {
+    if (in && in->abi_version >= 1 && in->abi_version <= NCDE_ABI_VERSION && in->interp == NCDE_INTERP_CUBIC)
+        return sfail(NCDE_ERR_UNSUPPORTED, "online hybrid step: the Hermite path has no hybrid form (interp must be NCDE_INTERP_LINEAR)");
+    return stream_problem_head(in, p, false);
+}
+
+int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false, bool hybrid = false) {
+    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, hermite);
     if (rc != NCDE_OK) return rc;
     if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL)
         return sfail(NCDE_ERR_UNSUPPORTED, "online step: the original field with the matmul input only (field_kind %d, field_input %d)", p->field_kind,
@@ -586,7 +673,7 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
     if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
     *y = make_layout(p);
     if (y->lds_fwd > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "generic forward needs %zu B of LDS (> %d)", y->lds_fwd, kLdsLimit);
-    *lds = sizeof(float) * (size_t)(5 * y->HS + 2 * y->DS + 5 * y->Cp * 16 + 48);
+    *lds = sizeof(float) * (size_t)(5 * y->HS + 2 * y->DS + 5 * y->Cp * 16 + 48 + (hybrid ? 16 : 0));
     if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
     return NCDE_OK;
 }
@@ -594,14 +681,18 @@ int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds
 // The problem as the field step reads it: what stream_problem reads, plus the gate head of a gated field, and a layer chain that
 // starts at the width of the field input, d0 = hidden (matmul) or hidden + channels.  hermite: interp = NCDE_INTERP_CUBIC, the same
 // plan (the stage image takes the DXB slot).
-int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false) {
-    const int rc = stream_problem_head(in, p, hermite);
+// hybrid: the matmul and derivative inputs, 3 DS + 4 HS + 5 CS + 64 floats (no start rows, 16 flags more).
+int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false, bool hybrid = false) {
+    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, hermite);
     if (rc != NCDE_OK) return rc;
+    if (hybrid && p->field_input == NCDE_INPUT_EVALUATE)
+        return sfail(NCDE_ERR_UNSUPPORTED, "online hybrid field step: the evaluate input is not covered (its stage offset is the stream's knot index, which the state does not carry)");
     if (p->field_kind == NCDE_FIELD_GRU)
         return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the GRU-gated field is not covered (its stage runs the inner net twice plus a reset gate)");
     if (p->field_kind == NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the low-rank field is not covered");
     if (p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is %s's", hermite ? "ncde_stream_step_hermite" : "ncde_stream_step");
+        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is %s's",
+                     hybrid ? "ncde_stream_step_hybrid" : (hermite ? "ncde_stream_step_hermite" : "ncde_stream_step"));
     if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return sfail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
     int d = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;      // d0
     for (int l = 0; l < p->n_layers; ++l) {
@@ -612,15 +703,16 @@ int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_
     }
     if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
     *y = make_layout(p);
-    *lds = sizeof(float) * (size_t)(3 * y->DS + 4 * y->HS + 7 * y->Cp * 16 + 48);
+    *lds = sizeof(float) * (size_t)(3 * y->DS + 4 * y->HS + (hybrid ? 5 : 7) * y->Cp * 16 + (hybrid ? 64 : 48));
     if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online field step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
     return NCDE_OK;
 }
 
 // The problem as the low-rank step reads it: what stream_problem reads, the rank in the top byte of flags and the second head
 // (Wo / bo = M_h [H R, dlast], Wg / bg = M_o [R C, dlast]).  interp says the path: NCDE_INTERP_LINEAR or NCDE_INTERP_CUBIC (Hermite).
-int stream_lowrank_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
-    const int rc = stream_problem_head(in, p, in && in->interp == NCDE_INTERP_CUBIC);
+// hybrid: 16 flags more.
+int stream_lowrank_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hybrid = false) {
+    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, in && in->interp == NCDE_INTERP_CUBIC);
     if (rc != NCDE_OK) return rc;
     if (p->field_kind != NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field only (field_kind %d)", p->field_kind);
     if (p->field_input != NCDE_INPUT_MATMUL)
@@ -639,12 +731,12 @@ int stream_lowrank_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, siz
     if (!p->Wo || !p->bo || !p->Wg || !p->bg) return sfail(NCDE_ERR_INVALID, "low-rank field: NULL Wo/bo (M_h) or Wg/bg (M_o)");
     *y = make_layout(p);
     const size_t ntp = ((size_t)(p->hidden + p->channels) * (size_t)rank + 15) & ~(size_t)15;
-    *lds = sizeof(float) * ((size_t)5 * y->HS + (size_t)2 * y->DS + (size_t)5 * y->Cp * 16 + 48 + 16 * ntp);
+    *lds = sizeof(float) * ((size_t)5 * y->HS + (size_t)2 * y->DS + (size_t)5 * y->Cp * 16 + 48 + 16 * ntp + (hybrid ? 16 : 0));
     if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
     return NCDE_OK;
 }
 
-enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2, kStepFieldHermite = 3, kStepLowrank = 4 };
+enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2, kStepFieldHermite = 3, kStepLowrank = 4, kStepHybrid = 5, kStepFieldHybrid = 6, kStepLowrankHybrid = 7 };
 
 // every step's problem, by kind
 int stream_problem_of(int kind, const NcdeProblem* p, NcdeProblem* q, Layout* y, size_t* lds) {
@@ -652,6 +744,9 @@ int stream_problem_of(int kind, const NcdeProblem* p, NcdeProblem* q, Layout* y,
         case kStepField: return stream_field_problem(p, q, y, lds);
         case kStepFieldHermite: return stream_field_problem(p, q, y, lds, true);
         case kStepLowrank: return stream_lowrank_problem(p, q, y, lds);
+        case kStepHybrid: return stream_problem(p, q, y, lds, false, true);
+        case kStepFieldHybrid: return stream_field_problem(p, q, y, lds, false, true);
+        case kStepLowrankHybrid: return stream_lowrank_problem(p, q, y, lds, true);
         default: return stream_problem(p, q, y, lds, kind == kStepHermite);
     }
 }
@@ -673,14 +768,19 @@ extern "C" const char* ncde_stream_kernel_name(const NcdeProblem* p) {
     return stream_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step" : nullptr;
 }
 
-static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, int kind) {
+// rect_mask: the hybrid kinds' per-channel mask (a DEVICE pointer, never read here); NULL on every other kind.
+static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, int kind, const unsigned char* rect_mask = nullptr) {
     NcdeProblem q;
     Layout y;
     size_t lds;
     const int rc = stream_problem_of(kind, p, &q, &y, &lds);
     if (rc != NCDE_OK) return rc;
     const bool hermite = q.interp == NCDE_INTERP_CUBIC;
+    const bool hybrid = kind == kStepHybrid || kind == kStepFieldHybrid || kind == kStepLowrankHybrid;
     if (!s) return sfail(NCDE_ERR_INVALID, "stream is NULL");
+    if (hybrid && !rect_mask) return sfail(NCDE_ERR_INVALID, "online hybrid step: rectilinear_mask is NULL (uint8 [channels] on the device)");
+    if (hybrid && s->rectilinear) return sfail(NCDE_ERR_INVALID, "online hybrid step: rectilinear must be 0 (the mask says which channels step)");
+    if (hybrid && s->time_index != 0) return sfail(NCDE_ERR_INVALID, "online hybrid step: time is channel 0 (time_index %d)", s->time_index);
     if (s->n_rows < 1) return sfail(NCDE_ERR_INVALID, "n_rows %d: at least one new row", s->n_rows);
     if (!s->x || !s->z || !s->last_row || !s->prev_dx || !s->count) return sfail(NCDE_ERR_INVALID, "NULL x / z / last_row / prev_dx / count");
     if (s->x_stride_b < q.channels || s->x_stride_m < 0) return sfail(NCDE_ERR_INVALID, "x strides (%lld, %lld): rows of %d channels", (long long)s->x_stride_m, (long long)s->x_stride_b, q.channels);
@@ -694,20 +794,33 @@ static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream
     k.m = s->n_rows; k.rect = s->rectilinear != 0; k.ti = s->time_index; k.n_out = s->Wf ? s->n_out : 0;
     k.x = s->x; k.xs_m = s->x_stride_m; k.xs_b = s->x_stride_b;
     k.active = s->active; k.init = s->initial_value_if_nan;
+    k.rmask = hybrid ? rect_mask : nullptr;
     k.z = s->z; k.last = s->last_row; k.pdx = s->prev_dx; k.count = s->count;
     k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
     void (*kernel)(KArgs, StreamArgs) = hermite ? ncde_stream_step_hermite_kernel : ncde_stream_step_kernel;
     const char* name = hermite ? "ncde_stream_step_hermite" : "ncde_stream_step";
-    if (kind == kStepField || kind == kStepFieldHermite) {      // every weight streamed
+    if (kind == kStepHybrid) {
+        kernel = ncde_stream_step_hybrid_kernel;
+        name = "ncde_stream_step_hybrid";
+    }
+    if (kind == kStepField || kind == kStepFieldHermite || kind == kStepFieldHybrid) {      // every weight streamed
         for (int l = 0; l < NCDE_MAX_LAYERS; ++l) a.wres[l] = -1;
         a.wres_o = a.wres_g = a.wres_r = -1;
         kernel = hermite ? ncde_stream_step_field_hermite_kernel : ncde_stream_step_field_kernel;
         name = hermite ? "ncde_stream_step_field_hermite" : "ncde_stream_step_field";
+        if (hybrid) {
+            kernel = ncde_stream_step_field_hybrid_kernel;
+            name = "ncde_stream_step_field_hybrid";
+        }
     }
-    if (kind == kStepLowrank) {      // the heads streamed
+    if (kind == kStepLowrank || kind == kStepLowrankHybrid) {      // the heads streamed
         a.wres_o = -1;
         kernel = hermite ? ncde_stream_step_lowrank_hermite_kernel : ncde_stream_step_lowrank_kernel;
         name = hermite ? "ncde_stream_step_lowrank_hermite" : "ncde_stream_step_lowrank";
+        if (hybrid) {
+            kernel = ncde_stream_step_lowrank_hybrid_kernel;
+            name = "ncde_stream_step_lowrank_hybrid";
+        }
     }
     if (ncde_lds_optin((const void*)kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
     hipLaunchKernelGGL(kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
@@ -786,6 +899,42 @@ extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) {
 }
 
 extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepHermite); }
+
+// ---- the hybrid steps (the per-channel mask as an extra argument; NcdeProblem and NcdeStream as they are) -------------------------
+namespace {
+
+const char* const kHybridNames[] = {"ncde_stream_step_hybrid", "ncde_stream_step_field_hybrid", "ncde_stream_step_lowrank_hybrid"};
+
+int stream_hybrid_query(int kind, const NcdeProblem* p) {
+    NcdeProblem q;
+    Layout y;
+    size_t lds;
+    return stream_problem_of(kind, p, &q, &y, &lds);
+}
+
+}  // namespace
+
+extern "C" int64_t ncde_stream_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepHybrid, p); }
+extern "C" const char* ncde_stream_hybrid_kernel_name(const NcdeProblem* p) { return stream_hybrid_query(kStepHybrid, p) == NCDE_OK ? kHybridNames[0] : nullptr; }
+extern "C" int ncde_stream_step_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(p, s, stream, kStepHybrid, rectilinear_mask);
+}
+
+extern "C" int64_t ncde_stream_field_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepFieldHybrid, p); }
+extern "C" const char* ncde_stream_field_hybrid_kernel_name(const NcdeProblem* p) {
+    return stream_hybrid_query(kStepFieldHybrid, p) == NCDE_OK ? kHybridNames[1] : nullptr;
+}
+extern "C" int ncde_stream_step_field_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(p, s, stream, kStepFieldHybrid, rectilinear_mask);
+}
+
+extern "C" int64_t ncde_stream_lowrank_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepLowrankHybrid, p); }
+extern "C" const char* ncde_stream_lowrank_hybrid_kernel_name(const NcdeProblem* p) {
+    return stream_hybrid_query(kStepLowrankHybrid, p) == NCDE_OK ? kHybridNames[2] : nullptr;
+}
+extern "C" int ncde_stream_step_lowrank_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(p, s, stream, kStepLowrankHybrid, rectilinear_mask);
+}
 
 // ---- the stacked step ------------------------------------------------------------------------------------------------------------
 namespace {

@@ -105,12 +105,16 @@ class NeuralCDE(nn.Module):
         y = self.final_linear(z)
         return y[:, ::2] if (self.interpolation == "rectilinear" and self.return_filtered_rectilinear) else y
 
-    def online(self, batch_size, *, initial_value_if_nan=0.0, time_index=0):
+    def online(self, batch_size, *, initial_value_if_nan=0.0, time_index=0, rectilinear_indices=None):
         """A handle that carries the state of ``batch_size`` streams from one observation to the next (online.py): ``step(x_new)``
         answers what ``return_sequences=True`` on the whole prefix gives at the newest knot.  Over this module's own parameters
-        (no copies); interpolation 'linear', 'rectilinear' or 'cubic_hermite' (the causal paths) only."""
+        (no copies); interpolation 'linear', 'rectilinear' or 'cubic_hermite' (the causal paths) only.
+        ``rectilinear_indices`` (a list of channels, possibly empty; interpolation 'linear', time in channel 0) selects the linear /
+        rectilinear hybrid path of ``linear_rectilinear_hybrid_coeffs``: the listed channels step, and add a knot only where they
+        change; a stream's time must strictly increase.  None: the model's own path."""
         from .online import OnlineNeuralCDE
-        return OnlineNeuralCDE(self, batch_size, initial_value_if_nan=initial_value_if_nan, time_index=time_index)
+        return OnlineNeuralCDE(self, batch_size, initial_value_if_nan=initial_value_if_nan, time_index=time_index,
+                               rectilinear_indices=rectilinear_indices)
 
     def forward(self, inputs):
         X, z0 = self._control_and_start(inputs)

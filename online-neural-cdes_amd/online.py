@@ -13,6 +13,18 @@ field, a shape whose LDS plan the kernel's query refuses -- takes the torch-op s
 (``hermite_cubic_coefficients_with_backward_differences(x, initial_value_if_nan=v, forward_fill=True)``), whose piece reads the new
 row, the last row and the previous piece's slope -- the state below, unchanged.
 
+``rectilinear_indices=[...]`` on a linear model selects the linear / rectilinear HYBRID path, the online half of
+``linear_rectilinear_hybrid_coeffs(x, rectilinear_indices)`` (DESIGN.md 5.7a, 5.14 "Hybrid step"): time is channel 0, the listed
+(sparse) channels step rectilinearly, every other channel is interpolated linearly.  A new row adds piece A (time and the linear
+channels move) and then, only for a stream whose filled sparse values differ from its last row's, piece B (the sparse channels
+move); a re-observed unchanged value adds nothing.  ``step`` answers ``NeuralCDE(interpolation="linear", return_sequences=True)`` on
+the hybrid coefficients of the stream's causally filled rows so far, read at the stream's last kept knot.  One launch of
+``ncde_stream_step_hybrid`` / ``ncde_stream_step_field_hybrid`` (matmul and derivative inputs) / ``ncde_stream_step_lowrank_hybrid``;
+the evaluate input takes the torch-op step (its stage offset is the stream's knot index, which the state does not carry).
+Precondition, not checked: a stream's time strictly increases from row to row (a repeated time is outside the contract).
+Causality: the batch builder closes interior NaN gaps of the LINEAR channels by interpolation, which looks ahead; this handle
+forward-fills them.  The two agree exactly when the linear channels are forward-filled first or hold no NaN -- the scheme's premise.
+
 State per stream: ``z`` [B, H], ``last_row`` [B, C] (the last filled row), ``prev_dx`` [B, C] (dX/dt of the last piece: stage 1 of
 the next step reads it, the reference's left-piece rule, interpolation_linear.py:212-219) and ``count`` [B] (observations received).
 """
@@ -42,7 +54,20 @@ def _rk_increment(f, method, y):
 
 
 class OnlineNeuralCDE:
-    def __init__(self, model, batch_size, initial_value_if_nan=0.0, time_index=0):
+    def __init__(self, model, batch_size, initial_value_if_nan=0.0, time_index=0, rectilinear_indices=None):
+        if rectilinear_indices is not None:      # the hybrid path: what the batch builder demands of the same arguments
+            if model.interpolation != "linear":
+                raise ValueError("rectilinear_indices selects the linear / rectilinear hybrid path: the model's interpolation must be "
+                                 "'linear' (the hybrid coefficients are linear coefficients), not '%s'" % model.interpolation)
+            if int(time_index) != 0:
+                raise NotImplementedError("the hybrid path takes time in channel 0 only (time_index %d)" % int(time_index))
+            idx = list(rectilinear_indices)
+            if any(isinstance(i, bool) or not isinstance(i, int) for i in idx):
+                raise ValueError("rectilinear_indices must be ints, got %r" % (idx,))
+            if len(set(idx)) != len(idx):
+                raise ValueError("rectilinear_indices must be unique, got %r" % (idx,))
+            if any(not 1 <= i < model.input_dim for i in idx):
+                raise ValueError("rectilinear_indices must lie in [1, %d] (channel 0 is time), got %r" % (model.input_dim - 1, idx))
         if model.interpolation not in ("linear", "rectilinear", "cubic_hermite"):
             raise ValueError("online inference needs a causal control path: interpolation 'linear' or 'rectilinear', not '%s' (a natural "
                              "cubic or smoothed path at knot k depends on later observations)" % model.interpolation)
@@ -66,6 +91,12 @@ class OnlineNeuralCDE:
         self.last_row = torch.zeros(B, C, dtype=ref.dtype, device=ref.device)
         self.prev_dx = torch.zeros(B, C, dtype=ref.dtype, device=ref.device)
         self.count = torch.zeros(B, dtype=torch.int32, device=ref.device)
+        self.hybrid = rectilinear_indices is not None
+        self.rect_mask = None      # hybrid: uint8 [C] on the state's device, 1 = the channel steps rectilinearly
+        if self.hybrid:
+            self.rect_mask = torch.zeros(C, dtype=torch.uint8, device=ref.device)
+            if idx:
+                self.rect_mask[idx] = 1
         self._route = {}
         self._may_init = True      # a stream may still be waiting for its first row (known on the host without a synchronisation)
 
@@ -182,9 +213,12 @@ class OnlineNeuralCDE:
             if self.rectilinear:      # the lagged row: new time, old values
                 mid = self.last_row.clone()
                 mid[:, self.time_index] = fill[:, self.time_index]
+            elif self.hybrid:         # the lagged row: old values in the sparse channels only
+                mid = torch.where(self.rect_mask.bool(), self.last_row, fill)
             else:
                 mid = fill
             da, db = mid - self.last_row, fill - mid
+            has_b = (db != 0).any(dim=1, keepdim=True) if self.hybrid else None      # hybrid: piece B per stream, where a sparse value changed
             dl = torch.where((self.count == 1)[:, None], da, self.prev_dx)
             if self.hermite:      # the piece's b is dl; a stage's offset in the piece as the batch solve forms it, (n + offset) - n
                 two_c = 2 * (3 * (da - dl) - da + dl)
@@ -192,7 +226,7 @@ class OnlineNeuralCDE:
                 n = (self.count - 1).to(xr.dtype)[:, None]
                 frac = [(n + s) - n for s in _STAGE_TIMES[method]]
             z = self.z
-            for start, left, own in [(self.last_row, dl, da)] + ([(mid, da, db)] if self.rectilinear else []):
+            for start, left, own, take in [(self.last_row, dl, da, None)] + ([(mid, da, db, has_b)] if self.rectilinear or self.hybrid else []):
                 def f(j, y, start=start, left=left, own=own):
                     if self.hermite and j > 0:      # stage 1 sits on the knot: the left piece at frac = 1, which is b (and X = the knot)
                         s = frac[j]
@@ -208,9 +242,11 @@ class OnlineNeuralCDE:
                     # evaluate: X at the stage time; at the knot it is the knot's row itself (the batch solve forms it as
                     # prev + 1 * (next - prev) on the left piece: equal up to one rounding)
                     return func(t0, torch.cat([y, start if j == 0 else start + _STAGE_TIMES[method][j] * own], dim=-1))
-                z = z + _rk_increment(f, method, z)
+                z_next = z + _rk_increment(f, method, z)
+                z = z_next if take is None else torch.where(take, z_next, z)
             self.z.copy_(torch.where(steps, z, self.z))
-            self.prev_dx.copy_(torch.where(steps, db if self.rectilinear else da, self.prev_dx))
+            taken = torch.where(has_b, db, da) if self.hybrid else (db if self.rectilinear else da)
+            self.prev_dx.copy_(torch.where(steps, taken, self.prev_dx))
             self.last_row.copy_(torch.where(a[:, None], fill, self.last_row))
             self.count.add_(a.to(torch.int32))
             outs.append(self._readout(self.z).clone())
@@ -244,7 +280,16 @@ class OnlineNeuralCDE:
         """(query, entry) of the step kernel that covers this field on this path, or None (the GRU-gated field): the original field
         with the matmul input has ncde_stream_step / ncde_stream_step_hermite; the minimal-gated field and the evaluate / derivative
         inputs of the two have ncde_stream_step_field / ncde_stream_step_field_hermite; the low-rank field has
-        ncde_stream_step_lowrank on all three paths (the problem's interp says which)."""
+        ncde_stream_step_lowrank on all three paths (the problem's interp says which).  The hybrid path has an entry of its own per
+        family (the query of the field one refuses the evaluate input)."""
+        if self.hybrid:
+            if spec.kind == "original" and spec.mode == "matmul":
+                return "ncde_stream_hybrid_workspace_bytes", "ncde_stream_step_hybrid"
+            if spec.kind in ("original", "minimal"):
+                return "ncde_stream_field_hybrid_workspace_bytes", "ncde_stream_step_field_hybrid"
+            if spec.kind == "lowrank":
+                return "ncde_stream_lowrank_hybrid_workspace_bytes", "ncde_stream_step_lowrank_hybrid"
+            return None
         if spec.kind == "original" and spec.mode == "matmul":
             if self.hermite:
                 return "ncde_stream_hermite_workspace_bytes", "ncde_stream_step_hermite"
@@ -314,7 +359,8 @@ class OnlineNeuralCDE:
         with torch.cuda.device(x.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
             entry = self._kernel_entry(self.model.func.fused_spec())[1]
-            _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(p), ctypes.byref(s), stream), entry)
+            extra = (ctypes.c_void_p(self.rect_mask.data_ptr()),) if self.hybrid else ()
+            _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(p), ctypes.byref(s), *extra, stream), entry)
         return out
 
 

@@ -10,11 +10,18 @@
     python tools/time_stream.py --interpolation cubic_hermite --vector-field minimal --batches 16,4096 --prefixes "" --append --out F
                                                                                # the field step on the Hermite path; --append collects
                                                                                # the runs of several invocations in one file
+    python tools/time_stream.py --interpolation rectilinear,linear --hybrid 0,100 --prefixes ""      # the hybrid step (ncde_stream_step_hybrid,
+                                                                               # DESIGN.md 5.14 "Hybrid step") next to the rectilinear and the
+                                                                               # linear step of the same build, on the same weights
 
 Legs, per batch size B in {1, 16, 256, 4096}:
   online step      handle.step(x_k) of NeuralCDE.online, one new observation per call (one launch of ncde_stream_step)
   prefix k         what a server has without it: one NeuralCDE(return_sequences=False) call on the prefix of k observations
                    (k in {10, 100, 399}; the prefix's coefficients are built BEFORE the clock starts, which flatters this leg)
+  hybrid P%        with --hybrid P[,P..]: a linear handle over the same weights with rectilinear_indices = the upper half of the
+                   channels, on rows whose sparse channels are observed, at a new value, on P % of the (stream, row) pairs and NaN
+                   elsewhere: at 0 % no tile ever takes the second piece (S stages per row), at 100 % every stream takes it at every
+                   row (2 S stages, the rectilinear step's count)
   torch-op step    with --vector-field / --vector-field-type other than original / matmul: a second handle over the same weights held
                    on the torch-op step (online.py::_advance_torch) -- the route such a handle took before its step kernel existed, and
                    the yardstick of that kernel
@@ -48,6 +55,7 @@ def main():
     ap.add_argument("--sparsity", type=float, default=0.5, help="low-rank: rank = ceil(C (1 - sparsity))")
     ap.add_argument("--append", action="store_true", help="--out holds {\"runs\": [...]}: add this run to it instead of overwriting")
     ap.add_argument("--vector-field-type", default="matmul", help="matmul, evaluate or derivative")
+    ap.add_argument("--hybrid", default="", help="comma list of percentages: one hybrid leg each, the sparse channels changing on that share of the rows")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "a timing needs the GPU"
     ROUNDS, STEPS, REPS = (int(os.environ.get(k, d)) for k, d in (("ROUNDS", 5), ("STEPS", 200), ("REPS", 10)))
@@ -61,7 +69,8 @@ def main():
     paths = args.interpolation.split(",")
     assert all(p in ("rectilinear", "linear", "cubic_hermite") for p in paths), paths
     path = paths[0]
-    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "interpolation": paths, "field": field, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
+    shares = [int(v) for v in args.hybrid.split(",") if v]
+    report = {"dims": {k: c[k] for k in ("C", "H", "HH", "nl")}, "interpolation": paths, "hybrid": shares, "field": field, "rounds": ROUNDS, "steps": STEPS, "reps": REPS, "legs": []}
     for B in (int(b) for b in args.batches.split(",")):
         torch.manual_seed(0)
         model = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=path, solver="rk4", **field).cuda()
@@ -72,6 +81,21 @@ def main():
             other = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation=q, solver="rk4", **field).cuda()
             other.load_state_dict(model.state_dict())
             handles[q] = other.online(B)
+        leg_rows = {}      # legs that step rows of their own
+        sparse = list(range(c["C"] - c["C"] // 2, c["C"]))
+        for share in shares:
+            lin = model
+            if path != "linear":
+                lin = ncde_amd.NeuralCDE(c["C"], c["H"], 1, hidden_hidden_dim=c["HH"], num_layers=c["nl"], interpolation="linear", solver="rk4", **field).cuda()
+                lin.load_state_dict(model.state_dict())
+            name = "hybrid %d%%" % share
+            handles[name] = lin.online(B, rectilinear_indices=sparse)
+            g = torch.Generator(device="cpu").manual_seed(4321 + share)
+            seen = (torch.rand(L, B, generator=g) * 100.0 < share).cuda()
+            value = torch.arange(L, dtype=torch.float32, device="cuda")[:, None, None] * 0.01 + torch.rand(L, B, len(sparse), generator=g).cuda()
+            hr = rows.clone()
+            hr[:, :, sparse] = torch.where(seen[:, :, None], value, torch.full_like(value, float("nan")))
+            leg_rows[name] = hr
         if variant:      # the same handle class, held on the torch-op step (its once-only warning is not the subject here)
             handles["torch-op"] = model.online(B)
             handles["torch-op"]._route[("cuda", torch.float32)] = False
@@ -82,13 +106,13 @@ def main():
             coeffs = {k: build(x[:, :k].contiguous(), initial_value_if_nan=0.0, forward_fill=True) for k in prefixes}
 
         def online(n, q=path):
-            handle = handles[q]
+            handle, own = handles[q], leg_rows.get(q, rows)
             handle.reset()
-            handle.step(rows[0])
+            handle.step(own[0])
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for k in range(1, n + 1):
-                handle.step(rows[k])
+                handle.step(own[k])
                 torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
@@ -101,7 +125,7 @@ def main():
                 torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n
 
-        legs = [("online step" if q == path else "online " + q, lambda q=q: online(STEPS, q)) for q in paths] + ([("torch-op step", lambda: online(STEPS, "torch-op"))] if variant else []) + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
+        legs = [("online step" if q == path else "online " + q, lambda q=q: online(STEPS, q)) for q in paths] + [(q, lambda q=q: online(STEPS, q)) for q in leg_rows] + ([("torch-op step", lambda: online(STEPS, "torch-op"))] if variant else []) + [("prefix %d" % k, lambda k=k: prefix(k, REPS)) for k in prefixes]
         for q in handles:
             online(20, q)
         for k in prefixes:
