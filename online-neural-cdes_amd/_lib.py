@@ -228,38 +228,15 @@ def lib():
     h.ncde_control_kernel_name.restype = ctypes.c_char_p
     h.ncde_backward_control.argtypes = [P, vp, vp, G, vp, vp, sz, vp]
     h.ncde_backward_control.restype = ctypes.c_int
-    h.ncde_stream_workspace_bytes.argtypes = [P]
-    h.ncde_stream_workspace_bytes.restype = ctypes.c_int64
-    h.ncde_stream_kernel_name.argtypes = [P]
-    h.ncde_stream_kernel_name.restype = ctypes.c_char_p
-    h.ncde_stream_step.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
-    h.ncde_stream_step.restype = ctypes.c_int
-    h.ncde_stream_hermite_workspace_bytes.argtypes = [P]
-    h.ncde_stream_hermite_workspace_bytes.restype = ctypes.c_int64
-    h.ncde_stream_hermite_kernel_name.argtypes = [P]
-    h.ncde_stream_hermite_kernel_name.restype = ctypes.c_char_p
-    h.ncde_stream_step_hermite.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
-    h.ncde_stream_step_hermite.restype = ctypes.c_int
-    h.ncde_stream_field_workspace_bytes.argtypes = [P]
-    h.ncde_stream_field_workspace_bytes.restype = ctypes.c_int64
-    h.ncde_stream_field_kernel_name.argtypes = [P]
-    h.ncde_stream_field_kernel_name.restype = ctypes.c_char_p
-    h.ncde_stream_step_field.argtypes = [P, ctypes.POINTER(NcdeStream), vp]
-    h.ncde_stream_step_field.restype = ctypes.c_int
-    for family in ("field_hermite", "lowrank"):
-        getattr(h, "ncde_stream_%s_workspace_bytes" % family).argtypes = [P]
-        getattr(h, "ncde_stream_%s_workspace_bytes" % family).restype = ctypes.c_int64
-        getattr(h, "ncde_stream_%s_kernel_name" % family).argtypes = [P]
-        getattr(h, "ncde_stream_%s_kernel_name" % family).restype = ctypes.c_char_p
-        getattr(h, "ncde_stream_step_%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream), vp]
-        getattr(h, "ncde_stream_step_%s" % family).restype = ctypes.c_int
-    for family in ("hybrid", "field_hybrid", "lowrank_hybrid"):      # the per-channel mask (a device pointer) before the stream
-        getattr(h, "ncde_stream_%s_workspace_bytes" % family).argtypes = [P]
-        getattr(h, "ncde_stream_%s_workspace_bytes" % family).restype = ctypes.c_int64
-        getattr(h, "ncde_stream_%s_kernel_name" % family).argtypes = [P]
-        getattr(h, "ncde_stream_%s_kernel_name" % family).restype = ctypes.c_char_p
-        getattr(h, "ncde_stream_step_%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream), vp, vp]
-        getattr(h, "ncde_stream_step_%s" % family).restype = ctypes.c_int
+    # the online steps: (family suffix, takes the per-channel mask -- a device pointer -- before the stream)
+    for family, mask in (("", False), ("_hermite", False), ("_field", False), ("_field_hermite", False), ("_lowrank", False),
+                         ("_hybrid", True), ("_field_hybrid", True), ("_lowrank_hybrid", True)):
+        getattr(h, "ncde_stream%s_workspace_bytes" % family).argtypes = [P]
+        getattr(h, "ncde_stream%s_workspace_bytes" % family).restype = ctypes.c_int64
+        getattr(h, "ncde_stream%s_kernel_name" % family).argtypes = [P]
+        getattr(h, "ncde_stream%s_kernel_name" % family).restype = ctypes.c_char_p
+        getattr(h, "ncde_stream_step%s" % family).argtypes = [P, ctypes.POINTER(NcdeStream)] + [vp] * (2 if mask else 1)
+        getattr(h, "ncde_stream_step%s" % family).restype = ctypes.c_int
     PP, SS = ctypes.POINTER(P), ctypes.POINTER(ctypes.POINTER(NcdeStream))      # one pointer per layer of the stack
     h.ncde_stream_stack_workspace_bytes.argtypes = [PP, ctypes.c_int]
     h.ncde_stream_stack_workspace_bytes.restype = ctypes.c_int64

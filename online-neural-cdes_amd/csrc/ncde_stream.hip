@@ -64,6 +64,7 @@ struct StreamScratch {
     int* STEP;       // steps at this row (0: no; else the step's index + 1)
     int* EVER;       // received a row in this launch
     int* HASB;       // HYBRID: takes the second piece at this row (a sparse channel changed); NULL otherwise
+    float* XS;       // the field step's evaluate input: the start rows of the two pieces, 2 CS; NULL on every other plan
 };
 struct StreamState {
     float* Y0;
@@ -72,34 +73,61 @@ struct StreamState {
     int* CNT;        // observations received
 };
 
-__device__ __forceinline__ int stream_dp(const KArgs& a) {
-    int Dp = ru16(a.H);
-    for (int l = 0; l < a.n_layers; ++l) Dp = max(Dp, ru16(a.dout[l]));
-    return Dp;
+// THE LDS PLAN of a tile, for the host's byte count and the kernels' carve alike (offsets and total in floats; -1: no such area):
+//   YS / U | ACT0 | ACT1 | K1 | K2 | KO | DXL | DXA | DXB | XS | STEP | EVER | HASB | the layers' states | PQ
+// HS, DS, CS: the rounded [Hp][16], [Dp][16], [Cp][16] (a stack: the widest of its layers).  The first area holds the stage input: HS
+// wide, or DS for the field step, whose U carries the control rows.  XS: the field step off the hybrid path; HASB: the hybrid kinds;
+// PQ [NTp][16]: the low-rank step.  state_floats: stream_state_floats of the layer, or their sum over a stack.
+enum StreamFamily { kFamStep = 0, kFamField = 1, kFamLowrank = 2 };
+struct StreamPlan {
+    int act0, act1, k1, k2, ko, dxl, dxa, dxb, xs, step, ever, hasb, states, pq;
+    long long total;
+};
+__host__ __device__ __forceinline__ int stream_state_floats(int HS, int CS) { return HS + 2 * CS + 16; }      // Y0 | LAST | PDX | CNT
+__host__ __device__ __forceinline__ StreamPlan stream_plan(int family, bool hybrid, int HS, int DS, int CS, long long NTp, int state_floats) {
+    StreamPlan n;
+    n.act0 = family == kFamField ? DS : HS;
+    n.act1 = n.act0 + DS;
+    n.k1 = n.act1 + DS;
+    n.k2 = n.k1 + HS;
+    n.ko = n.k2 + HS;
+    n.dxl = n.ko + HS;
+    n.dxa = n.dxl + CS;
+    n.dxb = n.dxa + CS;
+    n.xs = (family == kFamField && !hybrid) ? n.dxb + CS : -1;
+    n.step = n.dxb + CS + (n.xs >= 0 ? 2 * CS : 0);
+    n.ever = n.step + 16;
+    n.hasb = hybrid ? n.ever + 16 : -1;
+    n.states = n.ever + (hybrid ? 32 : 16);
+    n.pq = n.states + state_floats;
+    n.total = n.pq + (family == kFamLowrank ? 16 * NTp : 0);
+    return n;
 }
-__device__ __forceinline__ int stream_scratch_floats(int HS, int DS, int CS, bool hybrid = false) { return 4 * HS + 2 * DS + 3 * CS + 32 + (hybrid ? 16 : 0); }
-__device__ __forceinline__ int stream_state_floats(const KArgs& a) { return ru16(a.H) * 16 + 2 * ru4(a.C) * 16 + 16; }
-__device__ __forceinline__ float* stream_carve_scratch(float* p, int HS, int DS, int CS, StreamScratch& w, bool hybrid = false) {
-    w.YS = p;
-    w.ACT0 = w.YS + HS;
-    w.ACT1 = w.ACT0 + DS;
-    w.K1 = w.ACT1 + DS;
-    w.K2 = w.K1 + HS;
-    w.KO = w.K2 + HS;
-    w.DXL = w.KO + HS;
-    w.DXA = w.DXL + CS;
-    w.DXB = w.DXA + CS;
-    w.STEP = (int*)(w.DXB + CS);
-    w.EVER = w.STEP + 16;
-    w.HASB = hybrid ? w.EVER + 16 : nullptr;
-    return (float*)(w.EVER + (hybrid ? 32 : 16));
+__device__ __forceinline__ StreamScratch stream_carve_scratch(float* lds, const StreamPlan& n) {
+    StreamScratch w;
+    w.YS = lds;
+    w.ACT0 = lds + n.act0;
+    w.ACT1 = lds + n.act1;
+    w.K1 = lds + n.k1;
+    w.K2 = lds + n.k2;
+    w.KO = lds + n.ko;
+    w.DXL = lds + n.dxl;
+    w.DXA = lds + n.dxa;
+    w.DXB = lds + n.dxb;
+    w.XS = n.xs >= 0 ? lds + n.xs : nullptr;
+    w.STEP = (int*)(lds + n.step);
+    w.EVER = (int*)(lds + n.ever);
+    w.HASB = n.hasb >= 0 ? (int*)(lds + n.hasb) : nullptr;
+    return w;
 }
-__device__ __forceinline__ StreamState stream_carve_state(float* p, const KArgs& a) {
+// layer l's state: behind those of the layers below it
+__device__ __forceinline__ StreamState stream_carve_state(float* states, const KArgs* a, int l) {
+    for (int i = 0; i < l; ++i) states += stream_state_floats(ru16(a[i].H) * 16, ru4(a[i].C) * 16);
     StreamState t;
-    t.Y0 = p;
-    t.LAST = t.Y0 + ru16(a.H) * 16;
-    t.PDX = t.LAST + ru4(a.C) * 16;
-    t.CNT = (int*)(t.PDX + ru4(a.C) * 16);
+    t.Y0 = states;
+    t.LAST = t.Y0 + ru16(a[l].H) * 16;
+    t.PDX = t.LAST + ru4(a[l].C) * 16;
+    t.CNT = (int*)(t.PDX + ru4(a[l].C) * 16);
     return t;
 }
 
@@ -132,9 +160,9 @@ __device__ __forceinline__ void stream_load_state(const KArgs& a, const StreamAr
 // for a stream that does not step).
 // HYBRID (see "The hybrid step" below): the lagged row holds the old values of the channels of q.rmask only, and the second piece
 // is per stream.  any_b (uniform, like the return value): whether any stream of the tile takes it at this row.
-template <bool HYBRID = false>
+template <bool HYBRID>
 __device__ __forceinline__ int stream_fill_row(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, const float* from,
-                                               int r, int b0, int tid, float* starts = nullptr, int* any_b = nullptr) {
+                                               int r, int b0, int tid, float* starts, int* any_b) {
     const int C = a.C, Cp = ru4(C);
     for (int e = tid; e < 16 * Cp; e += GEN_THREADS) {
         const int s = e / Cp, c = e - s * Cp, b = b0 + s;
@@ -232,13 +260,17 @@ __device__ __forceinline__ void stream_hermite_image(const KArgs& a, const Strea
         }
     }
 }
-// stage(dx): one evaluation of the field at YS with the dX/dt image dx into KO, ending behind a barrier (gen_stage_forward, or
-// the low-rank stage)
+// A stage object is what a family adds to the body: Stage(a, w, lds, PQ, tid), and
+//   kFamily, tail_rows(a)    the family whose plan its kernels carve (stream_plan), and the rows NTp of its PQ (0: none)
+//   starts()                 the start rows the fill leaves and the Hermite image reads (the field step's evaluate input), or NULL
+//   stage(pc, j, n_pieces, dx)  stage j of piece pc: whatever the field needs before it (the field step rewrites the control rows
+//                            of U, behind a barrier of its own), then one evaluation of the field at YS with the image dx into KO,
+//                            ending behind a barrier (gen_stage_forward, vr_stage_forward, or the low-rank stage)
 // HYBRID: the second piece (n_pieces = 2 only where a stream of the tile takes it: uniform) combines under HASB -- every stream at
 // the start of a piece has YS = Y0 (from the load, or from the last combine it took part in), so one that sits the piece out
 // keeps both, and the KO the stage forms for it is never read.
-template <bool HERMITE, bool HYBRID = false, class Stage>
-__device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid, Stage stage) {
+template <bool HERMITE, bool HYBRID, class Stage>
+__device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratch& w, const StreamState& t, int n_pieces, int tid, const Stage& stage) {
     const int HS = ru16(a.H) * 16, CS = ru4(a.C) * 16;
     const int S = n_stages(a.method);
     for (int pc = 0; pc < n_pieces; ++pc) {
@@ -246,21 +278,25 @@ __device__ __forceinline__ void stream_stages(const KArgs& a, const StreamScratc
         const float* dx_left = pc == 0 ? w.DXL : w.DXA;
         const int* flags = (HYBRID && pc != 0) ? w.HASB : w.STEP;
         for (int j = 0; j < S; ++j) {
-            stage(j == 0 ? dx_left : dx_own);
+            stage.stage(pc, j, n_pieces, j == 0 ? dx_left : dx_own);
             stream_combine(a, w, t, flags, j, HS, tid);
-            if constexpr (HERMITE) {      // the next stage's dX/dt (its reader starts behind the barrier; the last reader of DXB is done)
-                if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid);
+            if constexpr (HERMITE) {      // the next stage's image (its reader starts behind the barrier; the last reader of DXB is done)
+                if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid, stage.starts());
             }
             __syncthreads();
         }
     }
 }
-// the original field's stage for stream_stages
+// the original field's stage
 struct StreamGenStage {
+    static constexpr int kFamily = kFamStep;
     const KArgs& a;
     const StreamScratch& w;
     int tid;
-    __device__ __forceinline__ void operator()(const float* dx) const { gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, dx, w.KO, ru16(a.H), ru4(a.C), tid); }
+    __device__ __forceinline__ StreamGenStage(const KArgs& a_, const StreamScratch& w_, float*, float*, int tid_) : a(a_), w(w_), tid(tid_) {}
+    static __device__ __forceinline__ int tail_rows(const KArgs&) { return 0; }
+    __device__ __forceinline__ float* starts() const { return nullptr; }
+    __device__ __forceinline__ void stage(int, int, int, const float* dx) const { gen_stage_forward(a, w.YS, w.ACT0, w.ACT1, dx, w.KO, ru16(a.H), ru4(a.C), tid); }
 };
 
 // 5. readout of every stream of the tile at row r (a stream without a row: of its unchanged z)
@@ -313,37 +349,65 @@ __device__ __forceinline__ void stream_store_state(const KArgs& a, const StreamA
 // skipped altogether -- S stages instead of 2 S -- where no stream of the tile takes it; that branch is uniform, read from the 16
 // flags as any_step is.  prev_dx after the row is db where B was taken and da otherwise.  Precondition: a stream's time strictly
 // increases, so piece A always exists (not checked).
-// LDS: the plan of the non-hybrid body plus the 16 flags; the field body drops XS (no evaluate input on this path).
-template <bool HERMITE, bool HYBRID = false>
-__device__ __forceinline__ void stream_step_body(const KArgs& a, const StreamArgs& q) {
+// LDS: the plan of the non-hybrid kind plus the 16 flags; the field step drops XS (no evaluate input on this path).
+
+// One layer at one row: fill (from: see stream_fill_row), the pieces' stages where a stream of the tile steps, readout.  The number
+// of pieces is launch-wide (q.rect) or, HYBRID, the tile-wide any_b of this row: uniform either way.
+template <bool HERMITE, bool HYBRID, class Stage>
+__device__ __forceinline__ void stream_row(const KArgs& a, const StreamArgs& q, const StreamScratch& w, const StreamState& t, const float* from, int r,
+                                           int b0, int tid, const Stage& stage) {
+    int any_b = 0;
+    const int any_step = stream_fill_row<HYBRID>(a, q, w, t, from, r, b0, tid, stage.starts(), &any_b);
+    const int n_pieces = (HYBRID ? any_b : q.rect) ? 2 : 1;
+    if (any_step) stream_stages<HERMITE, HYBRID>(a, w, t, n_pieces, tid, stage);
+    stream_readout(a, q, t, r, b0, tid);
+}
+
+// THE BODY of every step kernel: carve and clear the plan, load the state, per row the L layers bottom up, store the state.  L = 1
+// but for the stacked step (STACK, below), whose scratch is sized by its widest layer and whose states lie one behind the other.
+// a, q: the kernel's argument blocks, read only (__restrict__: without it the register allocator leaves an unused 20-byte frame in
+// several of the kernels, DESIGN.md 5.14 "One body").
+template <class Stage, bool HERMITE, bool HYBRID = false, bool STACK = false>
+__device__ __forceinline__ void stream_body(const KArgs* __restrict__ a, const StreamArgs* __restrict__ q, int L) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x;
     const int b0 = blockIdx.x * NCDE_TILE;
-    const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
-    StreamScratch w;
-    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w, HYBRID), a);
-    const int total = stream_scratch_floats(HS, DS, CS, HYBRID) + stream_state_floats(a);
-    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
+    int HS = 0, DS = 0, CS = 0, state_floats = 0;
+    for (int l = 0; l < L; ++l) {
+        const TileDims td = tile_dims(a[l], a[l].d0);
+        HS = max(HS, td.HS);
+        DS = max(DS, td.DS);
+        CS = max(CS, td.Cp * 16);
+        state_floats += stream_state_floats(td.HS, td.Cp * 16);
+    }
+    const StreamPlan n = stream_plan(Stage::kFamily, HYBRID, HS, DS, CS, Stage::tail_rows(a[0]), state_floats);
+    const StreamScratch w = stream_carve_scratch(lds, n);
+    float* states = lds + n.states;
+    for (int e = tid; e < (int)n.total; e += GEN_THREADS) lds[e] = 0.0f;
     __syncthreads();
-    stream_load_state(a, q, t, w.YS, b0, tid);
+    for (int l = 0; l < L; ++l) stream_load_state(a[l], q[l], stream_carve_state(states, a, l), STACK ? nullptr : w.YS, b0, tid);
     __syncthreads();
-    for (int r = 0; r < q.m; ++r) {
-        if constexpr (HYBRID) {
-            int any_b;
-            if (stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b))
-                stream_stages<false, true>(a, w, t, any_b ? 2 : 1, tid, StreamGenStage{a, w, tid});
-        } else {
-            if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamGenStage{a, w, tid});
+    const Stage stage0(a[0], w, lds, lds + n.pq, tid);      // the one layer's stage object: built once per launch (a stack: one per layer and row)
+    for (int r = 0; r < q[0].m; ++r) {
+        const float* below = nullptr;
+        for (int l = 0; l < L; ++l) {
+            const StreamState t = stream_carve_state(states, a, l);
+            if constexpr (STACK) {
+                // the stage input of this layer (the last readers of YS, the layer before, ended behind a barrier; readers start behind fill's)
+                for (int e = tid; e < ru16(a[l].H) * 16; e += GEN_THREADS) w.YS[e] = t.Y0[e];
+            }
+            if constexpr (STACK) stream_row<HERMITE, HYBRID>(a[l], q[l], w, t, below, r, b0, tid, Stage(a[l], w, lds, lds + n.pq, tid));
+            else stream_row<HERMITE, HYBRID>(a[l], q[l], w, t, below, r, b0, tid, stage0);
+            if constexpr (STACK) below = t.Y0;
         }
-        stream_readout(a, q, t, r, b0, tid);
     }
     __syncthreads();
-    stream_store_state(a, q, w, t, b0, tid);
+    for (int l = 0; l < L; ++l) stream_store_state(a[l], q[l], w, stream_carve_state(states, a, l), b0, tid);
 }
 
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) { stream_step_body<false>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hermite_kernel(KArgs a, StreamArgs q) { stream_step_body<true>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hybrid_kernel(KArgs a, StreamArgs q) { stream_step_body<false, true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_kernel(KArgs a, StreamArgs q) { stream_body<StreamGenStage, false>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hermite_kernel(KArgs a, StreamArgs q) { stream_body<StreamGenStage, true>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_hybrid_kernel(KArgs a, StreamArgs q) { stream_body<StreamGenStage, false, true>(&a, &q, 1); }
 
 // The stacked step (ncde_stream_stack_step): n_stack chained linear layers, layer l + 1 reading layer l's hidden state as its
 // observation.  Everything a layer reads of the one below is per stream, so the tile's workgroup walks the layers of a row with
@@ -364,44 +428,8 @@ struct StreamStackArgs {
 };
 static_assert(sizeof(StreamStackArgs) <= 4096, "the stacked step passes every layer's arguments by value: HIP's kernel arguments end at 4 KiB");
 
-__device__ __forceinline__ StreamState stream_stack_state(const StreamStackArgs& k, float* states, int l) {
-    for (int i = 0; i < l; ++i) states += stream_state_floats(k.a[i]);
-    return stream_carve_state(states, k.a[l]);
-}
-
 extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_stack_step_kernel(StreamStackArgs k) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * NCDE_TILE;
-    const int L = k.n_stack;
-    int HS = 0, DS = 0, CS = 0, total = 0;
-    for (int l = 0; l < L; ++l) {
-        HS = max(HS, ru16(k.a[l].H) * 16);
-        DS = max(DS, stream_dp(k.a[l]) * 16);
-        CS = max(CS, ru4(k.a[l].C) * 16);
-        total += stream_state_floats(k.a[l]);
-    }
-    total += stream_scratch_floats(HS, DS, CS);
-    StreamScratch w;
-    float* states = stream_carve_scratch(lds, HS, DS, CS, w);
-    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
-    __syncthreads();
-    for (int l = 0; l < L; ++l) stream_load_state(k.a[l], k.q[l], stream_stack_state(k, states, l), nullptr, b0, tid);
-    __syncthreads();
-    for (int r = 0; r < k.q[0].m; ++r) {
-        const float* below = nullptr;
-        for (int l = 0; l < L; ++l) {
-            const KArgs& a = k.a[l];
-            const StreamState t = stream_stack_state(k, states, l);
-            // the stage input of this layer (the last readers of YS, the layer before, ended behind a barrier; readers start behind fill's)
-            for (int e = tid; e < ru16(a.H) * 16; e += GEN_THREADS) w.YS[e] = t.Y0[e];
-            if (stream_fill_row(a, k.q[l], w, t, below, r, b0, tid)) stream_stages<false>(a, w, t, 1, tid, StreamGenStage{a, w, tid});
-            stream_readout(a, k.q[l], t, r, b0, tid);
-            below = t.Y0;
-        }
-    }
-    __syncthreads();
-    for (int l = 0; l < L; ++l) stream_store_state(k.a[l], k.q[l], w, stream_stack_state(k, states, l), b0, tid);
+    stream_body<StreamGenStage, false, false, true>(k.a, k.q, k.n_stack);
 }
 
 // The field step (ncde_stream_step_field): the same phases around the stage of the vector-field VARIANTS (vr_stage_forward,
@@ -458,86 +486,44 @@ __device__ void stream_field_value(const KArgs& a, float* UC, const float* start
 //   U, ACT0, ACT1 3 DS | K1, K2, KO 3 HS | DXL, DXA, DXB 3 CS | STEP, EVER, HASB 48 | state HS + 2 CS + 16     = 3 DS + 4 HS + 5 CS + 64
 // The branch around the second piece is the tile-wide any_b; its combine runs under HASB, so a stream that sits the piece out
 // keeps U rows < Hp, K1, K2 and Y0 (its control rows of U are rewritten from the images, whose entries are its own).
-template <bool HERMITE, bool HYBRID = false>
-__device__ __forceinline__ void stream_field_body(const KArgs& a, const StreamArgs& q) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * NCDE_TILE;
-    const TileDims td = tile_dims(a, a.d0);
-    const int H = a.H, C = a.C, Hp = td.Hp, Cp = td.Cp, HS = td.HS, DS = td.DS, CS = Cp * 16;
-    const bool matmul = a.field_input == NCDE_INPUT_MATMUL, evaluate = a.field_input == NCDE_INPUT_EVALUATE;
-    StreamScratch w;
-    w.YS = lds;      // U
-    w.ACT0 = w.YS + DS;
-    w.ACT1 = w.ACT0 + DS;
-    w.K1 = w.ACT1 + DS;
-    w.K2 = w.K1 + HS;
-    w.KO = w.K2 + HS;
-    w.DXL = w.KO + HS;
-    w.DXA = w.DXL + CS;
-    w.DXB = w.DXA + CS;
-    float* XS = w.DXB + CS;      // the pieces' start rows (evaluate); HYBRID: none
-    w.STEP = (int*)(XS + (HYBRID ? 0 : 2 * CS));
-    w.EVER = w.STEP + 16;
-    w.HASB = HYBRID ? w.EVER + 16 : nullptr;
-    const StreamState t = stream_carve_state((float*)(w.EVER + (HYBRID ? 32 : 16)), a);
-    float* U = w.YS;
-    const int total = HYBRID ? 3 * DS + 4 * HS + 5 * CS + 64 : 3 * DS + 4 * HS + 7 * CS + 48;
-    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
-    __syncthreads();
-    stream_load_state(a, q, t, U, b0, tid);
-    __syncthreads();
-    const int S = n_stages(a.method);
-    int n_pieces = q.rect ? 2 : 1;
-    for (int r = 0; r < q.m; ++r) {
-        int any_step;
-        if constexpr (HYBRID) {      // (evaluate is refused by the host: XS does not exist)
-            int any_b;
-            any_step = stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b);
-            n_pieces = any_b ? 2 : 1;
-        } else {
-            any_step = stream_fill_row(a, q, w, t, nullptr, r, b0, tid, evaluate ? XS : nullptr);
-        }
-        if (any_step) {
-            for (int pc = 0; pc < n_pieces; ++pc) {
-                const float* dx_own = (HERMITE || pc != 0) ? w.DXB : w.DXA;
-                const float* dx_left = pc == 0 ? w.DXL : w.DXA;
-                const float* start = XS + pc * CS;
-                const int* flags = (HYBRID && pc != 0) ? w.HASB : w.STEP;
-                for (int j = 0; j < S; ++j) {
-                    const float* img = j == 0 ? dx_left : dx_own;
-                    if (!matmul) {
-                        if constexpr (HERMITE) {      // evaluate: the knot's row, then the value image
-                            const float* src = (evaluate && j == 0) ? start : img;
-                            for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = src[e];
-                        } else {
-                            if (evaluate) stream_field_value(a, U + H * 16, start, dx_own, w.STEP, j, n_pieces, pc, tid);
-                            else
-                                for (int e = tid; e < C * 16; e += GEN_THREADS) U[H * 16 + e] = img[e];
-                        }
-                        __syncthreads();
-                    }
-                    // (RU, RG, XB: the gru field's, which the host refuses -- valid addresses all the same, never touched)
-                    vr_stage_forward(a, U, w.ACT0, w.ACT0, w.ACT0, w.ACT0, img, w.KO, nullptr, nullptr, nullptr, lds, Hp, Cp, DS, tid);
-                    stream_combine(a, w, t, flags, j, HS, tid);
-                    if constexpr (HERMITE) {      // the next stage's image (its reader starts behind the barrier; the last reader of DXB is done)
-                        if (j + 1 < S) stream_hermite_image(a, w, j + 1, CS, tid, evaluate ? XS : nullptr);
-                    }
-                    __syncthreads();
-                }
+template <bool HERMITE>
+struct StreamFieldStage {
+    static constexpr int kFamily = kFamField;
+    const KArgs& a;
+    const StreamScratch& w;      // (w.YS: U)
+    float* lds;
+    const TileDims td;
+    int tid;
+    __device__ __forceinline__ StreamFieldStage(const KArgs& a_, const StreamScratch& w_, float* lds_, float*, int tid_)
+        : a(a_), w(w_), lds(lds_), td(tile_dims(a_, a_.d0)), tid(tid_) {}
+    static __device__ __forceinline__ int tail_rows(const KArgs&) { return 0; }
+    // the pieces' start rows (HYBRID: evaluate is refused by the host, XS does not exist)
+    __device__ __forceinline__ float* starts() const { return a.field_input == NCDE_INPUT_EVALUATE ? w.XS : nullptr; }
+    __device__ __forceinline__ void stage(int pc, int j, int n_pieces, const float* img) const {
+        float* UC = w.YS + a.H * 16;      // the control rows of U
+        if (a.field_input != NCDE_INPUT_MATMUL) {
+            const bool evaluate = a.field_input == NCDE_INPUT_EVALUATE;
+            const float* start = evaluate ? w.XS + pc * td.Cp * 16 : nullptr;      // the piece's start row
+            if constexpr (HERMITE) {      // evaluate: the knot's row, then the value image
+                const float* src = (evaluate && j == 0) ? start : img;
+                for (int e = tid; e < a.C * 16; e += GEN_THREADS) UC[e] = src[e];
+            } else {
+                if (evaluate) stream_field_value(a, UC, start, img, w.STEP, j, n_pieces, pc, tid);      // (j > 0: img is the piece's own)
+                else
+                    for (int e = tid; e < a.C * 16; e += GEN_THREADS) UC[e] = img[e];
             }
+            __syncthreads();
         }
-        stream_readout(a, q, t, r, b0, tid);
+        // (RU, RG, XB: the gru field's, which the host refuses -- valid addresses all the same, never touched)
+        vr_stage_forward(a, w.YS, w.ACT0, w.ACT0, w.ACT0, w.ACT0, img, w.KO, nullptr, nullptr, nullptr, lds, td.Hp, td.Cp, td.DS, tid);
     }
-    __syncthreads();
-    stream_store_state(a, q, w, t, b0, tid);
-}
+};
 
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) { stream_field_body<false>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hermite_kernel(KArgs a, StreamArgs q) { stream_field_body<true>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hybrid_kernel(KArgs a, StreamArgs q) { stream_field_body<false, true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_kernel(KArgs a, StreamArgs q) { stream_body<StreamFieldStage<false>, false>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hermite_kernel(KArgs a, StreamArgs q) { stream_body<StreamFieldStage<true>, true>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field_hybrid_kernel(KArgs a, StreamArgs q) { stream_body<StreamFieldStage<false>, false, true>(&a, &q, 1); }
 
-// The low-rank step (ncde_stream_step_lowrank, ncde_stream_step_lowrank_hermite): the phases and the stage loop of stream_step_body
+// The low-rank step (ncde_stream_step_lowrank, ncde_stream_step_lowrank_hermite): the phases and the stage loop of stream_body
 // around the stage of ncde_fwd_lowrank (ncde_lowrank_stage.h) -- the inner layers on dense_relu, ping-pong in ACT0 / ACT1, then
 // lr_heads into PQ, a barrier, and lr_contract of PQ with the stage's dX/dt image into KO.  The image is the one stream_stages hands
 // the original field: the left-piece rule on a linear or rectilinear stream, b and the rebuilt slope image in the DXB slot on the
@@ -556,12 +542,17 @@ extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_field
 //                     lr_contract reads channels < C.  Hermite: DXB all 16 Cp entries again by every rebuild.
 // Every barrier sits in uniform control flow: the only branch around stages is the tile-wide any_step.
 struct StreamLowrankStage {
+    static constexpr int kFamily = kFamLowrank;
     const KArgs& a;
     const StreamScratch& w;
-    const LrDims& d;
-    float* PQ;
+    const LrDims d;      // (wres_o = -1: d.wl = NULL)
+    float* PQ;           // [NTp][16]
     int tid;
-    __device__ __forceinline__ void operator()(const float* dx) const {
+    __device__ __forceinline__ StreamLowrankStage(const KArgs& a_, const StreamScratch& w_, float* lds, float* PQ_, int tid_)
+        : a(a_), w(w_), d(lr_dims(a_, lds)), PQ(PQ_), tid(tid_) {}
+    static __device__ __forceinline__ int tail_rows(const KArgs& a) { return lr_dims(a, nullptr).NTp; }
+    __device__ __forceinline__ float* starts() const { return nullptr; }
+    __device__ __forceinline__ void stage(int, int, int, const float* dx) const {
         const int lane = tid & 63, wave = tid >> 6;
         const float* in = w.YS;
         for (int l = 0; l < a.n_layers; ++l) {
@@ -578,38 +569,9 @@ struct StreamLowrankStage {
 };
 
 // HYBRID (ncde_stream_step_lowrank_hybrid; "The hybrid step" above): the same body, 16 flags more (HASB, behind EVER).
-template <bool HERMITE, bool HYBRID = false>
-__device__ __forceinline__ void stream_lowrank_body(const KArgs& a, const StreamArgs& q) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = threadIdx.x;
-    const int b0 = blockIdx.x * NCDE_TILE;
-    const int HS = ru16(a.H) * 16, DS = stream_dp(a) * 16, CS = ru4(a.C) * 16;
-    const LrDims d = lr_dims(a, lds);      // (wres_o = -1: d.wl = NULL)
-    StreamScratch w;
-    const StreamState t = stream_carve_state(stream_carve_scratch(lds, HS, DS, CS, w, HYBRID), a);
-    float* PQ = (float*)(t.CNT + 16);      // [NTp][16]
-    const int total = stream_scratch_floats(HS, DS, CS, HYBRID) + stream_state_floats(a) + d.NTp * 16;
-    for (int e = tid; e < total; e += GEN_THREADS) lds[e] = 0.0f;
-    __syncthreads();
-    stream_load_state(a, q, t, w.YS, b0, tid);
-    __syncthreads();
-    for (int r = 0; r < q.m; ++r) {
-        if constexpr (HYBRID) {
-            int any_b;
-            if (stream_fill_row<true>(a, q, w, t, nullptr, r, b0, tid, nullptr, &any_b))
-                stream_stages<false, true>(a, w, t, any_b ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
-        } else {
-            if (stream_fill_row(a, q, w, t, nullptr, r, b0, tid)) stream_stages<HERMITE>(a, w, t, q.rect ? 2 : 1, tid, StreamLowrankStage{a, w, d, PQ, tid});
-        }
-        stream_readout(a, q, t, r, b0, tid);
-    }
-    __syncthreads();
-    stream_store_state(a, q, w, t, b0, tid);
-}
-
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<false>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hermite_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<true>(a, q); }
-extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hybrid_kernel(KArgs a, StreamArgs q) { stream_lowrank_body<false, true>(a, q); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_kernel(KArgs a, StreamArgs q) { stream_body<StreamLowrankStage, false>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hermite_kernel(KArgs a, StreamArgs q) { stream_body<StreamLowrankStage, true>(&a, &q, 1); }
+extern "C" __global__ __launch_bounds__(GEN_THREADS) void ncde_stream_step_lowrank_hybrid_kernel(KArgs a, StreamArgs q) { stream_body<StreamLowrankStage, false, true>(&a, &q, 1); }
 
 namespace {
 
@@ -657,126 +619,125 @@ int stream_hybrid_head(const NcdeProblem* in, NcdeProblem* p) {
     return stream_problem_head(in, p, false);
 }
 
-int stream_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false, bool hybrid = false) {
-    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, hermite);
-    if (rc != NCDE_OK) return rc;
-    if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online step: the original field with the matmul input only (field_kind %d, field_input %d)", p->field_kind,
-                     p->field_input);
-    int d = p->hidden;
+// THE STEP KINDS: one row per (family, path) that has an entry point -- which kernel runs it under which name, and which of
+// KArgs' wres* are set to -1 (no resident copy: one step per launch does not repay filling one).
+enum StreamPath { kPathLinear, kPathHermite, kPathInterp, kPathHybrid };      // kPathInterp: linear or Hermite, as the problem's interp says
+enum StreamStreamed { kStreamNone, kStreamHeads, kStreamAll };
+struct StreamKind {
+    int family, path;
+    void (*kernel[2])(KArgs, StreamArgs);      // [1], name[1]: a kPathInterp kind on the Hermite path
+    const char* name[2];
+    int streamed;
+};
+const StreamKind kStep = {kFamStep, kPathLinear, {ncde_stream_step_kernel}, {"ncde_stream_step"}, kStreamNone};
+const StreamKind kStepHermite = {kFamStep, kPathHermite, {ncde_stream_step_hermite_kernel}, {"ncde_stream_step_hermite"}, kStreamNone};
+const StreamKind kStepHybrid = {kFamStep, kPathHybrid, {ncde_stream_step_hybrid_kernel}, {"ncde_stream_step_hybrid"}, kStreamNone};
+const StreamKind kField = {kFamField, kPathLinear, {ncde_stream_step_field_kernel}, {"ncde_stream_step_field"}, kStreamAll};
+const StreamKind kFieldHermite = {kFamField, kPathHermite, {ncde_stream_step_field_hermite_kernel}, {"ncde_stream_step_field_hermite"}, kStreamAll};
+const StreamKind kFieldHybrid = {kFamField, kPathHybrid, {ncde_stream_step_field_hybrid_kernel}, {"ncde_stream_step_field_hybrid"}, kStreamAll};
+const StreamKind kLowrank = {kFamLowrank, kPathInterp, {ncde_stream_step_lowrank_kernel, ncde_stream_step_lowrank_hermite_kernel},
+                             {"ncde_stream_step_lowrank", "ncde_stream_step_lowrank_hermite"}, kStreamHeads};
+const StreamKind kLowrankHybrid = {kFamLowrank, kPathHybrid, {ncde_stream_step_lowrank_hybrid_kernel}, {"ncde_stream_step_lowrank_hybrid"}, kStreamHeads};
+
+// the inner layers chain from d0 and have their weights
+int stream_layer_chain(const NcdeProblem* p, int d) {
     for (int l = 0; l < p->n_layers; ++l) {
         if (p->layer_in[l] != d) return sfail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
         if (p->layer_out[l] < 1) return sfail(NCDE_ERR_INVALID, "layer %d: out=%d", l, p->layer_out[l]);
         if (!p->layer_W[l] || !p->layer_b[l]) return sfail(NCDE_ERR_INVALID, "layer %d: NULL weight/bias", l);
         d = p->layer_out[l];
     }
-    if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
-    *y = make_layout(p);
-    if (y->lds_fwd > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "generic forward needs %zu B of LDS (> %d)", y->lds_fwd, kLdsLimit);
-    *lds = sizeof(float) * (size_t)(5 * y->HS + 2 * y->DS + 5 * y->Cp * 16 + 48 + (hybrid ? 16 : 0));
-    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
     return NCDE_OK;
 }
 
-// The problem as the field step reads it: what stream_problem reads, plus the gate head of a gated field, and a layer chain that
-// starts at the width of the field input, d0 = hidden (matmul) or hidden + channels.  hermite: interp = NCDE_INTERP_CUBIC, the same
-// plan (the stage image takes the DXB slot).
-// hybrid: the matmul and derivative inputs, 3 DS + 4 HS + 5 CS + 64 floats (no start rows, 16 flags more).
-int stream_field_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hermite = false, bool hybrid = false) {
-    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, hermite);
+// The problem as a step of kind k reads it (p), its layout and the bytes of its LDS plan.  By family:
+//   step      the original field with the matmul input.
+//   field     plus the gate head of a gated field, and a layer chain that starts at the width of the field input, d0 = hidden (matmul)
+//             or hidden + channels; the hybrid path takes the matmul and derivative inputs only.
+//   low-rank  the rank in the top byte of flags and the second head (Wo / bo = M_h [H R, dlast], Wg / bg = M_o [R C, dlast]).
+int stream_problem(const StreamKind& k, const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds) {
+    const bool hybrid = k.path == kPathHybrid;
+    const bool hermite = k.path == kPathHermite || (k.path == kPathInterp && in && in->interp == NCDE_INTERP_CUBIC);
+    int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, hermite);
     if (rc != NCDE_OK) return rc;
-    if (hybrid && p->field_input == NCDE_INPUT_EVALUATE)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online hybrid field step: the evaluate input is not covered (its stage offset is the stream's knot index, which the state does not carry)");
-    if (p->field_kind == NCDE_FIELD_GRU)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the GRU-gated field is not covered (its stage runs the inner net twice plus a reset gate)");
-    if (p->field_kind == NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the low-rank field is not covered");
-    if (p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is %s's",
-                     hybrid ? "ncde_stream_step_hybrid" : (hermite ? "ncde_stream_step_hermite" : "ncde_stream_step"));
-    if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return sfail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
-    int d = p->field_input == NCDE_INPUT_MATMUL ? p->hidden : p->hidden + p->channels;      // d0
-    for (int l = 0; l < p->n_layers; ++l) {
-        if (p->layer_in[l] != d) return sfail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
-        if (p->layer_out[l] < 1) return sfail(NCDE_ERR_INVALID, "layer %d: out=%d", l, p->layer_out[l]);
-        if (!p->layer_W[l] || !p->layer_b[l]) return sfail(NCDE_ERR_INVALID, "layer %d: NULL weight/bias", l);
-        d = p->layer_out[l];
+    int d0 = p->hidden;
+    long long ntp = 0;      // rows of PQ (the low-rank step)
+    const char* what = "online step";
+    if (k.family == kFamStep) {
+        if (p->field_kind != NCDE_FIELD_ORIGINAL || p->field_input != NCDE_INPUT_MATMUL)
+            return sfail(NCDE_ERR_UNSUPPORTED, "online step: the original field with the matmul input only (field_kind %d, field_input %d)", p->field_kind,
+                         p->field_input);
+    } else if (k.family == kFamField) {
+        what = "online field step";
+        if (hybrid && p->field_input == NCDE_INPUT_EVALUATE)
+            return sfail(NCDE_ERR_UNSUPPORTED, "online hybrid field step: the evaluate input is not covered (its stage offset is the stream's knot index, which the state does not carry)");
+        if (p->field_kind == NCDE_FIELD_GRU)
+            return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the GRU-gated field is not covered (its stage runs the inner net twice plus a reset gate)");
+        if (p->field_kind == NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the low-rank field is not covered");
+        if (p->field_kind == NCDE_FIELD_ORIGINAL && p->field_input == NCDE_INPUT_MATMUL)
+            return sfail(NCDE_ERR_UNSUPPORTED, "online field step: the original field with the matmul input is %s's",
+                         (hybrid ? kStepHybrid : (hermite ? kStepHermite : kStep)).name[0]);
+        if (p->field_kind != NCDE_FIELD_ORIGINAL && (!p->Wg || !p->bg)) return sfail(NCDE_ERR_INVALID, "gated field: NULL Wg/bg");
+        if (p->field_input != NCDE_INPUT_MATMUL) d0 = p->hidden + p->channels;
+    } else {
+        what = "online low-rank step";
+        if (p->field_kind != NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field only (field_kind %d)", p->field_kind);
+        if (p->field_input != NCDE_INPUT_MATMUL)
+            return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field takes the matmul input only (field_input %d)", p->field_input);
+        const int rank = ncde_field_rank(p);
+        if (rank < 1 || rank > p->channels)
+            return sfail(NCDE_ERR_INVALID, "low-rank field: rank %d (NCDE_FLAG_FIELD_RANK) outside [1, channels = %d]", rank, p->channels);
+        if (p->n_layers < 1) return sfail(NCDE_ERR_INVALID, "online low-rank step: the low-rank kernels need at least one inner layer");
+        ntp = ((long long)(p->hidden + p->channels) * rank + 15) & ~15LL;
     }
-    if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
-    *y = make_layout(p);
-    *lds = sizeof(float) * (size_t)(3 * y->DS + 4 * y->HS + (hybrid ? 5 : 7) * y->Cp * 16 + (hybrid ? 64 : 48));
-    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online field step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
-    return NCDE_OK;
-}
-
-// The problem as the low-rank step reads it: what stream_problem reads, the rank in the top byte of flags and the second head
-// (Wo / bo = M_h [H R, dlast], Wg / bg = M_o [R C, dlast]).  interp says the path: NCDE_INTERP_LINEAR or NCDE_INTERP_CUBIC (Hermite).
-// hybrid: 16 flags more.
-int stream_lowrank_problem(const NcdeProblem* in, NcdeProblem* p, Layout* y, size_t* lds, bool hybrid = false) {
-    const int rc = hybrid ? stream_hybrid_head(in, p) : stream_problem_head(in, p, in && in->interp == NCDE_INTERP_CUBIC);
+    rc = stream_layer_chain(p, d0);
     if (rc != NCDE_OK) return rc;
-    if (p->field_kind != NCDE_FIELD_LOWRANK) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field only (field_kind %d)", p->field_kind);
-    if (p->field_input != NCDE_INPUT_MATMUL)
-        return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step: the low-rank field takes the matmul input only (field_input %d)", p->field_input);
-    const int rank = ncde_field_rank(p);
-    if (rank < 1 || rank > p->channels)
-        return sfail(NCDE_ERR_INVALID, "low-rank field: rank %d (NCDE_FLAG_FIELD_RANK) outside [1, channels = %d]", rank, p->channels);
-    if (p->n_layers < 1) return sfail(NCDE_ERR_INVALID, "online low-rank step: the low-rank kernels need at least one inner layer");
-    int d = p->hidden;
-    for (int l = 0; l < p->n_layers; ++l) {
-        if (p->layer_in[l] != d) return sfail(NCDE_ERR_INVALID, "layer %d: in=%d does not chain from %d", l, p->layer_in[l], d);
-        if (p->layer_out[l] < 1) return sfail(NCDE_ERR_INVALID, "layer %d: out=%d", l, p->layer_out[l]);
-        if (!p->layer_W[l] || !p->layer_b[l]) return sfail(NCDE_ERR_INVALID, "layer %d: NULL weight/bias", l);
-        d = p->layer_out[l];
-    }
-    if (!p->Wo || !p->bo || !p->Wg || !p->bg) return sfail(NCDE_ERR_INVALID, "low-rank field: NULL Wo/bo (M_h) or Wg/bg (M_o)");
+    if (k.family == kFamLowrank) {
+        if (!p->Wo || !p->bo || !p->Wg || !p->bg) return sfail(NCDE_ERR_INVALID, "low-rank field: NULL Wo/bo (M_h) or Wg/bg (M_o)");
+    } else if (!p->Wo || !p->bo) return sfail(NCDE_ERR_INVALID, "NULL Wo/bo");
     *y = make_layout(p);
-    const size_t ntp = ((size_t)(p->hidden + p->channels) * (size_t)rank + 15) & ~(size_t)15;
-    *lds = sizeof(float) * ((size_t)5 * y->HS + (size_t)2 * y->DS + (size_t)5 * y->Cp * 16 + 48 + 16 * ntp + (hybrid ? 16 : 0));
-    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "online low-rank step needs %zu B of LDS (> %d)", *lds, kLdsLimit);
+    if (k.family == kFamStep && y->lds_fwd > (size_t)kLdsLimit)
+        return sfail(NCDE_ERR_UNSUPPORTED, "generic forward needs %zu B of LDS (> %d)", y->lds_fwd, kLdsLimit);
+    *lds = sizeof(float) * (size_t)stream_plan(k.family, hybrid, y->HS, y->DS, y->Cp * 16, ntp, stream_state_floats(y->HS, y->Cp * 16)).total;
+    if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "%s needs %zu B of LDS (> %d)", what, *lds, kLdsLimit);
     return NCDE_OK;
 }
 
-enum { kStepLinear = 0, kStepHermite = 1, kStepField = 2, kStepFieldHermite = 3, kStepLowrank = 4, kStepHybrid = 5, kStepFieldHybrid = 6, kStepLowrankHybrid = 7 };
-
-// every step's problem, by kind
-int stream_problem_of(int kind, const NcdeProblem* p, NcdeProblem* q, Layout* y, size_t* lds) {
-    switch (kind) {
-        case kStepField: return stream_field_problem(p, q, y, lds);
-        case kStepFieldHermite: return stream_field_problem(p, q, y, lds, true);
-        case kStepLowrank: return stream_lowrank_problem(p, q, y, lds);
-        case kStepHybrid: return stream_problem(p, q, y, lds, false, true);
-        case kStepFieldHybrid: return stream_field_problem(p, q, y, lds, false, true);
-        case kStepLowrankHybrid: return stream_lowrank_problem(p, q, y, lds, true);
-        default: return stream_problem(p, q, y, lds, kind == kStepHermite);
-    }
-}
-
-}  // namespace
-
-extern "C" int64_t ncde_stream_workspace_bytes(const NcdeProblem* p) {
+// the two queries of a kind: the status of its problem, and the name of the kernel that would run it
+int stream_query(const StreamKind& k, const NcdeProblem* p, int* interp = nullptr) {
     NcdeProblem q;
     Layout y;
     size_t lds;
-    const int rc = stream_problem(p, &q, &y, &lds);
-    return rc == NCDE_OK ? 0 : rc;
+    const int rc = stream_problem(k, p, &q, &y, &lds);
+    if (rc == NCDE_OK && interp) *interp = q.interp;
+    return rc;
+}
+const char* stream_name(const StreamKind& k, const NcdeProblem* p) {
+    int interp = 0;
+    return stream_query(k, p, &interp) == NCDE_OK ? k.name[k.path == kPathInterp && interp == NCDE_INTERP_CUBIC] : nullptr;
 }
 
-extern "C" const char* ncde_stream_kernel_name(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    return stream_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step" : nullptr;
+// NcdeStream -> StreamArgs.  rows: whose x, mask and fill value (a stack: layer 0's); s: whose state and readout.
+StreamArgs stream_args(const NcdeStream* rows, const NcdeStream* s, int rect, int ti, const unsigned char* rmask) {
+    StreamArgs k{};
+    k.m = rows->n_rows; k.rect = rect; k.ti = ti; k.n_out = s->Wf ? s->n_out : 0;
+    k.x = rows->x; k.xs_m = rows->x_stride_m; k.xs_b = rows->x_stride_b;
+    k.active = rows->active; k.init = rows->initial_value_if_nan;
+    k.rmask = rmask;
+    k.z = s->z; k.last = s->last_row; k.pdx = s->prev_dx; k.count = s->count;
+    k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
+    return k;
 }
 
 // rect_mask: the hybrid kinds' per-channel mask (a DEVICE pointer, never read here); NULL on every other kind.
-static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream, int kind, const unsigned char* rect_mask = nullptr) {
+int stream_launch(const StreamKind& kind, const NcdeProblem* p, const NcdeStream* s, void* stream, const unsigned char* rect_mask = nullptr) {
     NcdeProblem q;
     Layout y;
     size_t lds;
-    const int rc = stream_problem_of(kind, p, &q, &y, &lds);
+    const int rc = stream_problem(kind, p, &q, &y, &lds);
     if (rc != NCDE_OK) return rc;
     const bool hermite = q.interp == NCDE_INTERP_CUBIC;
-    const bool hybrid = kind == kStepHybrid || kind == kStepFieldHybrid || kind == kStepLowrankHybrid;
+    const bool hybrid = kind.path == kPathHybrid;
     if (!s) return sfail(NCDE_ERR_INVALID, "stream is NULL");
     if (hybrid && !rect_mask) return sfail(NCDE_ERR_INVALID, "online hybrid step: rectilinear_mask is NULL (uint8 [channels] on the device)");
     if (hybrid && s->rectilinear) return sfail(NCDE_ERR_INVALID, "online hybrid step: rectilinear must be 0 (the mask says which channels step)");
@@ -790,166 +751,31 @@ static int stream_launch(const NcdeProblem* p, const NcdeStream* s, void* stream
     if (s->Wf ? (s->n_out < 1 || !s->out) : !s->z_out) return sfail(NCDE_ERR_INVALID, "readout: Wf needs n_out >= 1 and out; without Wf pass z_out");
     KArgs a;
     fill_kargs(&q, y, &a);
-    StreamArgs k{};
-    k.m = s->n_rows; k.rect = s->rectilinear != 0; k.ti = s->time_index; k.n_out = s->Wf ? s->n_out : 0;
-    k.x = s->x; k.xs_m = s->x_stride_m; k.xs_b = s->x_stride_b;
-    k.active = s->active; k.init = s->initial_value_if_nan;
-    k.rmask = hybrid ? rect_mask : nullptr;
-    k.z = s->z; k.last = s->last_row; k.pdx = s->prev_dx; k.count = s->count;
-    k.Wf = s->Wf; k.bf = s->bf; k.out = s->out; k.z_out = s->z_out;
-    void (*kernel)(KArgs, StreamArgs) = hermite ? ncde_stream_step_hermite_kernel : ncde_stream_step_kernel;
-    const char* name = hermite ? "ncde_stream_step_hermite" : "ncde_stream_step";
-    if (kind == kStepHybrid) {
-        kernel = ncde_stream_step_hybrid_kernel;
-        name = "ncde_stream_step_hybrid";
-    }
-    if (kind == kStepField || kind == kStepFieldHermite || kind == kStepFieldHybrid) {      // every weight streamed
+    if (kind.streamed == kStreamAll) {
         for (int l = 0; l < NCDE_MAX_LAYERS; ++l) a.wres[l] = -1;
-        a.wres_o = a.wres_g = a.wres_r = -1;
-        kernel = hermite ? ncde_stream_step_field_hermite_kernel : ncde_stream_step_field_kernel;
-        name = hermite ? "ncde_stream_step_field_hermite" : "ncde_stream_step_field";
-        if (hybrid) {
-            kernel = ncde_stream_step_field_hybrid_kernel;
-            name = "ncde_stream_step_field_hybrid";
-        }
+        a.wres_g = a.wres_r = -1;
     }
-    if (kind == kStepLowrank || kind == kStepLowrankHybrid) {      // the heads streamed
-        a.wres_o = -1;
-        kernel = hermite ? ncde_stream_step_lowrank_hermite_kernel : ncde_stream_step_lowrank_kernel;
-        name = hermite ? "ncde_stream_step_lowrank_hermite" : "ncde_stream_step_lowrank";
-        if (hybrid) {
-            kernel = ncde_stream_step_lowrank_hybrid_kernel;
-            name = "ncde_stream_step_lowrank_hybrid";
-        }
-    }
-    if (ncde_lds_optin((const void*)kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
-    hipLaunchKernelGGL(kernel, dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
+    if (kind.streamed != kStreamNone) a.wres_o = -1;
+    const StreamArgs k = stream_args(s, s, s->rectilinear != 0, s->time_index, hybrid ? rect_mask : nullptr);
+    const int which = kind.path == kPathInterp && hermite;
+    if (ncde_lds_optin((const void*)kind.kernel[which], lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
+    hipLaunchKernelGGL(kind.kernel[which], dim3(y.n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, a, k);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "%s launch failed: %s", name, hipGetErrorString(e));
+    if (e != hipSuccess) return sfail(NCDE_ERR_HIP, "%s launch failed: %s", kind.name[which], hipGetErrorString(e));
     return NCDE_OK;
 }
 
-extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepLinear); }
-
-extern "C" int64_t ncde_stream_field_workspace_bytes(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    const int rc = stream_field_problem(p, &q, &y, &lds);
-    return rc == NCDE_OK ? 0 : rc;
-}
-
-extern "C" const char* ncde_stream_field_kernel_name(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    return stream_field_problem(p, &q, &y, &lds) == NCDE_OK ? "ncde_stream_step_field" : nullptr;
-}
-
-extern "C" int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepField); }
-
-extern "C" int64_t ncde_stream_field_hermite_workspace_bytes(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    const int rc = stream_field_problem(p, &q, &y, &lds, true);
-    return rc == NCDE_OK ? 0 : rc;
-}
-
-extern "C" const char* ncde_stream_field_hermite_kernel_name(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    return stream_field_problem(p, &q, &y, &lds, true) == NCDE_OK ? "ncde_stream_step_field_hermite" : nullptr;
-}
-
-extern "C" int ncde_stream_step_field_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepFieldHermite); }
-
-extern "C" int64_t ncde_stream_lowrank_workspace_bytes(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    const int rc = stream_lowrank_problem(p, &q, &y, &lds);
-    return rc == NCDE_OK ? 0 : rc;
-}
-
-extern "C" const char* ncde_stream_lowrank_kernel_name(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    if (stream_lowrank_problem(p, &q, &y, &lds) != NCDE_OK) return nullptr;
-    return q.interp == NCDE_INTERP_CUBIC ? "ncde_stream_step_lowrank_hermite" : "ncde_stream_step_lowrank";
-}
-
-extern "C" int ncde_stream_step_lowrank(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepLowrank); }
-
-extern "C" int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    const int rc = stream_problem(p, &q, &y, &lds, true);
-    return rc == NCDE_OK ? 0 : rc;
-}
-
-extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    return stream_problem(p, &q, &y, &lds, true) == NCDE_OK ? "ncde_stream_step_hermite" : nullptr;
-}
-
-extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(p, s, stream, kStepHermite); }
-
-// ---- the hybrid steps (the per-channel mask as an extra argument; NcdeProblem and NcdeStream as they are) -------------------------
-namespace {
-
-const char* const kHybridNames[] = {"ncde_stream_step_hybrid", "ncde_stream_step_field_hybrid", "ncde_stream_step_lowrank_hybrid"};
-
-int stream_hybrid_query(int kind, const NcdeProblem* p) {
-    NcdeProblem q;
-    Layout y;
-    size_t lds;
-    return stream_problem_of(kind, p, &q, &y, &lds);
-}
-
-}  // namespace
-
-extern "C" int64_t ncde_stream_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepHybrid, p); }
-extern "C" const char* ncde_stream_hybrid_kernel_name(const NcdeProblem* p) { return stream_hybrid_query(kStepHybrid, p) == NCDE_OK ? kHybridNames[0] : nullptr; }
-extern "C" int ncde_stream_step_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
-    return stream_launch(p, s, stream, kStepHybrid, rectilinear_mask);
-}
-
-extern "C" int64_t ncde_stream_field_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepFieldHybrid, p); }
-extern "C" const char* ncde_stream_field_hybrid_kernel_name(const NcdeProblem* p) {
-    return stream_hybrid_query(kStepFieldHybrid, p) == NCDE_OK ? kHybridNames[1] : nullptr;
-}
-extern "C" int ncde_stream_step_field_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
-    return stream_launch(p, s, stream, kStepFieldHybrid, rectilinear_mask);
-}
-
-extern "C" int64_t ncde_stream_lowrank_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_hybrid_query(kStepLowrankHybrid, p); }
-extern "C" const char* ncde_stream_lowrank_hybrid_kernel_name(const NcdeProblem* p) {
-    return stream_hybrid_query(kStepLowrankHybrid, p) == NCDE_OK ? kHybridNames[2] : nullptr;
-}
-extern "C" int ncde_stream_step_lowrank_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
-    return stream_launch(p, s, stream, kStepLowrankHybrid, rectilinear_mask);
-}
-
-// ---- the stacked step ------------------------------------------------------------------------------------------------------------
-namespace {
-
-// Every layer as stream_problem reads it, the chain between the layers and the LDS plan of the whole stack.
+// Every layer of a stack as the plain step reads it, the chain between the layers and the LDS plan of the whole stack: the scratch
+// of the widest layer, every layer's state.
 int stream_stack_problems(const NcdeProblem* const* p, int n_stack, NcdeProblem* q, Layout* y, size_t* lds) {
     if (n_stack < 1 || n_stack > NCDE_STREAM_MAX_STACK) return sfail(NCDE_ERR_INVALID, "n_stack %d outside [1, %d]", n_stack, NCDE_STREAM_MAX_STACK);
     if (!p) return sfail(NCDE_ERR_INVALID, "the list of problems is NULL");
     for (int i = 0; i < n_stack; ++i)
         if (!p[i]) return sfail(NCDE_ERR_INVALID, "stacked online step: problem %d is NULL", i);
-    int HS = 0, DS = 0, CS = 0;
-    size_t states = 0;
+    int HS = 0, DS = 0, CS = 0, states = 0;
     for (int i = 0; i < n_stack; ++i) {
         size_t own;
-        const int rc = stream_problem(p[i], &q[i], &y[i], &own);
+        const int rc = stream_problem(kStep, p[i], &q[i], &y[i], &own);
         if (rc != NCDE_OK) return rc;
         if (i > 0 && q[i].channels != q[i - 1].hidden)
             return sfail(NCDE_ERR_INVALID, "stacked online step: layer %d reads %d channels, layer %d has %d hidden units", i, q[i].channels, i - 1, q[i - 1].hidden);
@@ -957,30 +783,63 @@ int stream_stack_problems(const NcdeProblem* const* p, int n_stack, NcdeProblem*
         HS = std::max(HS, y[i].HS);
         DS = std::max(DS, y[i].DS);
         CS = std::max(CS, y[i].Cp * 16);
-        states += (size_t)(y[i].HS + 2 * y[i].Cp * 16 + 16);
+        states += stream_state_floats(y[i].HS, y[i].Cp * 16);
     }
-    *lds = sizeof(float) * ((size_t)(4 * HS + 2 * DS + 3 * CS + 32) + states);
+    *lds = sizeof(float) * (size_t)stream_plan(kFamStep, false, HS, DS, CS, 0, states).total;
     if (*lds > (size_t)kLdsLimit) return sfail(NCDE_ERR_UNSUPPORTED, "stacked online step of %d layers needs %zu B of LDS (> %d)", n_stack, *lds, kLdsLimit);
     return NCDE_OK;
+}
+int stream_stack_query(const NcdeProblem* const* p, int n_stack) {
+    NcdeProblem q[NCDE_STREAM_MAX_STACK];
+    Layout y[NCDE_STREAM_MAX_STACK];
+    size_t lds;
+    return stream_stack_problems(p, n_stack, q, y, &lds);
 }
 
 }  // namespace
 
-extern "C" int64_t ncde_stream_stack_workspace_bytes(const NcdeProblem* const* p, int n_stack) {
-    NcdeProblem q[NCDE_STREAM_MAX_STACK];
-    Layout y[NCDE_STREAM_MAX_STACK];
-    size_t lds;
-    const int rc = stream_stack_problems(p, n_stack, q, y, &lds);
-    return rc == NCDE_OK ? 0 : rc;
+extern "C" int64_t ncde_stream_workspace_bytes(const NcdeProblem* p) { return stream_query(kStep, p); }
+extern "C" const char* ncde_stream_kernel_name(const NcdeProblem* p) { return stream_name(kStep, p); }
+extern "C" int ncde_stream_step(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(kStep, p, s, stream); }
+
+extern "C" int64_t ncde_stream_hermite_workspace_bytes(const NcdeProblem* p) { return stream_query(kStepHermite, p); }
+extern "C" const char* ncde_stream_hermite_kernel_name(const NcdeProblem* p) { return stream_name(kStepHermite, p); }
+extern "C" int ncde_stream_step_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(kStepHermite, p, s, stream); }
+
+extern "C" int64_t ncde_stream_field_workspace_bytes(const NcdeProblem* p) { return stream_query(kField, p); }
+extern "C" const char* ncde_stream_field_kernel_name(const NcdeProblem* p) { return stream_name(kField, p); }
+extern "C" int ncde_stream_step_field(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(kField, p, s, stream); }
+
+extern "C" int64_t ncde_stream_field_hermite_workspace_bytes(const NcdeProblem* p) { return stream_query(kFieldHermite, p); }
+extern "C" const char* ncde_stream_field_hermite_kernel_name(const NcdeProblem* p) { return stream_name(kFieldHermite, p); }
+extern "C" int ncde_stream_step_field_hermite(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(kFieldHermite, p, s, stream); }
+
+extern "C" int64_t ncde_stream_lowrank_workspace_bytes(const NcdeProblem* p) { return stream_query(kLowrank, p); }
+extern "C" const char* ncde_stream_lowrank_kernel_name(const NcdeProblem* p) { return stream_name(kLowrank, p); }
+extern "C" int ncde_stream_step_lowrank(const NcdeProblem* p, const NcdeStream* s, void* stream) { return stream_launch(kLowrank, p, s, stream); }
+
+// the hybrid steps: the per-channel mask as an extra argument; NcdeProblem and NcdeStream as they are
+extern "C" int64_t ncde_stream_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_query(kStepHybrid, p); }
+extern "C" const char* ncde_stream_hybrid_kernel_name(const NcdeProblem* p) { return stream_name(kStepHybrid, p); }
+extern "C" int ncde_stream_step_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(kStepHybrid, p, s, stream, rectilinear_mask);
+}
+extern "C" int64_t ncde_stream_field_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_query(kFieldHybrid, p); }
+extern "C" const char* ncde_stream_field_hybrid_kernel_name(const NcdeProblem* p) { return stream_name(kFieldHybrid, p); }
+extern "C" int ncde_stream_step_field_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(kFieldHybrid, p, s, stream, rectilinear_mask);
+}
+extern "C" int64_t ncde_stream_lowrank_hybrid_workspace_bytes(const NcdeProblem* p) { return stream_query(kLowrankHybrid, p); }
+extern "C" const char* ncde_stream_lowrank_hybrid_kernel_name(const NcdeProblem* p) { return stream_name(kLowrankHybrid, p); }
+extern "C" int ncde_stream_step_lowrank_hybrid(const NcdeProblem* p, const NcdeStream* s, const unsigned char* rectilinear_mask, void* stream) {
+    return stream_launch(kLowrankHybrid, p, s, stream, rectilinear_mask);
 }
 
+// the stacked step
+extern "C" int64_t ncde_stream_stack_workspace_bytes(const NcdeProblem* const* p, int n_stack) { return stream_stack_query(p, n_stack); }
 extern "C" const char* ncde_stream_stack_kernel_name(const NcdeProblem* const* p, int n_stack) {
-    NcdeProblem q[NCDE_STREAM_MAX_STACK];
-    Layout y[NCDE_STREAM_MAX_STACK];
-    size_t lds;
-    return stream_stack_problems(p, n_stack, q, y, &lds) == NCDE_OK ? "ncde_stream_stack_step" : nullptr;
+    return stream_stack_query(p, n_stack) == NCDE_OK ? "ncde_stream_stack_step" : nullptr;
 }
-
 extern "C" int ncde_stream_stack_step(const NcdeProblem* const* p, const NcdeStream* const* s, int n_stack, void* stream) {
     NcdeProblem q[NCDE_STREAM_MAX_STACK];
     Layout y[NCDE_STREAM_MAX_STACK];
@@ -1006,12 +865,7 @@ extern "C" int ncde_stream_stack_step(const NcdeProblem* const* p, const NcdeStr
         if (si->Wf ? (si->n_out < 1 || !si->out) : (last && !si->z_out))
             return sfail(NCDE_ERR_INVALID, "layer %d readout: Wf needs n_out >= 1 and out; the last layer without Wf needs z_out", i);
         fill_kargs(&q[i], y[i], &k.a[i]);
-        StreamArgs& t = k.q[i];
-        t.m = s0->n_rows; t.rect = 0; t.ti = 0; t.n_out = si->Wf ? si->n_out : 0;
-        t.x = s0->x; t.xs_m = s0->x_stride_m; t.xs_b = s0->x_stride_b;
-        t.active = s0->active; t.init = s0->initial_value_if_nan;
-        t.z = si->z; t.last = si->last_row; t.pdx = si->prev_dx; t.count = si->count;
-        t.Wf = si->Wf; t.bf = si->bf; t.out = si->out; t.z_out = si->z_out;
+        k.q[i] = stream_args(s0, si, 0, 0, nullptr);
     }
     if (ncde_lds_optin((const void*)ncde_stream_stack_step_kernel, lds) != hipSuccess) return sfail(NCDE_ERR_HIP, "LDS opt-in of %zu B failed", lds);
     hipLaunchKernelGGL(ncde_stream_stack_step_kernel, dim3(y[0].n_wg), dim3(GEN_THREADS), lds, (hipStream_t)stream, k);

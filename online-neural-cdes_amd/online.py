@@ -282,25 +282,16 @@ class OnlineNeuralCDE:
         inputs of the two have ncde_stream_step_field / ncde_stream_step_field_hermite; the low-rank field has
         ncde_stream_step_lowrank on all three paths (the problem's interp says which).  The hybrid path has an entry of its own per
         family (the query of the field one refuses the evaluate input)."""
-        if self.hybrid:
-            if spec.kind == "original" and spec.mode == "matmul":
-                return "ncde_stream_hybrid_workspace_bytes", "ncde_stream_step_hybrid"
-            if spec.kind in ("original", "minimal"):
-                return "ncde_stream_field_hybrid_workspace_bytes", "ncde_stream_step_field_hybrid"
-            if spec.kind == "lowrank":
-                return "ncde_stream_lowrank_hybrid_workspace_bytes", "ncde_stream_step_lowrank_hybrid"
-            return None
-        if spec.kind == "original" and spec.mode == "matmul":
-            if self.hermite:
-                return "ncde_stream_hermite_workspace_bytes", "ncde_stream_step_hermite"
-            return "ncde_stream_workspace_bytes", "ncde_stream_step"
-        if spec.kind in ("original", "minimal"):
-            if self.hermite:
-                return "ncde_stream_field_hermite_workspace_bytes", "ncde_stream_step_field_hermite"
-            return "ncde_stream_field_workspace_bytes", "ncde_stream_step_field"
-        if spec.kind == "lowrank":
-            return "ncde_stream_lowrank_workspace_bytes", "ncde_stream_step_lowrank"
-        return None
+        family = "step" if (spec.kind, spec.mode) == ("original", "matmul") else self._FAMILY.get(spec.kind)
+        return self._ENTRY.get((family, "hybrid" if self.hybrid else ("hermite" if self.hermite else "linear")))
+
+    # (family, path) -> (query, entry); a field kind without a family (the GRU-gated field) has none.  Read at every step: the names
+    # are formed here, once.
+    _FAMILY = {"original": "field", "minimal": "field", "lowrank": "lowrank"}
+    _ENTRY = {key: ("ncde_stream%s_workspace_bytes" % suffix, "ncde_stream_step%s" % suffix) for key, suffix in (
+        (("step", "linear"), ""), (("step", "hermite"), "_hermite"), (("step", "hybrid"), "_hybrid"),
+        (("field", "linear"), "_field"), (("field", "hermite"), "_field_hermite"), (("field", "hybrid"), "_field_hybrid"),
+        (("lowrank", "linear"), "_lowrank"), (("lowrank", "hermite"), "_lowrank"), (("lowrank", "hybrid"), "_lowrank_hybrid"))}
 
     def _use_kernel(self, x):
         """The route, in the house style: CUDA fp32, a field one of the step kernels covers (_kernel_entry) and a shape its query
