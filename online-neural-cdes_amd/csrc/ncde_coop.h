@@ -57,6 +57,12 @@ namespace {
 typedef unsigned u32x2c __attribute__((ext_vector_type(2)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 
+// Row of Wo (and element of bo) behind tile row li of the 16-row output tile (state-unit block hb, channel quad cq): a tile is
+// (4 state units) x (4 channels), rows (g, r) <-> (h = 4 hb + g, c = 4 cq + r).  The ONE statement of that order for the pack
+// kernels, the batch-tiled walks, the cooperative images and pass B.  An int, like every index into bo (H * C entries) in these
+// kernels; callers widen to 64 bits before they multiply by the row length.
+__host__ __device__ __forceinline__ int wo_tile_row(int hb, int cq, int li, int C) { return (4 * hb + (li >> 2)) * C + 4 * cq + (li & 3); }
+
 // exchange area of one sample tile (floats): [XL split image | a | dX/dt | scales | f.dX slices | M partials of dL/dx_L]
 struct CoopDims {
     int H, C, dlast, M, G;
@@ -251,10 +257,10 @@ __global__ __launch_bounds__(256) void ncde_coop_absmax(const float* __restrict_
     if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 
-// Row of Wo behind (row tile rt, tile row li): tiles are (4 state units) x (4 channels), rt = hb * (C/4) + cq  (as ncde_pack_panels)
+// Row of Wo behind (row tile rt, tile row li), rt = hb * (C/4) + cq  (as ncde_pack_panels)
 __device__ __forceinline__ long long coop_row(int rt, int li, int C) {
-    const int ncq = C >> 2, hb = rt / ncq, cq = rt - hb * ncq;
-    return (long long)(4 * hb + (li >> 2)) * C + 4 * cq + (li & 3);
+    const int ncq = C >> 2, hb = rt / ncq;
+    return wo_tile_row(hb, rt - hb * ncq, li, C);
 }
 
 // One thread = one (member, wave, fragment, lane): 8 (4) weights, scaled by sw = 2^-e (max |Wo| sw in [1/2, 1)), split into two fp16

@@ -65,7 +65,7 @@ __device__ __forceinline__ void dwo_h2_body(const KArgs& a, int n_sc, int n_st, 
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
             for (int pc = 0; pc < 2; ++pc) W[q][c][pc] = *reinterpret_cast<const u32x4*>(wp + ((((qq * 4 + c) * 2 + pc) * 64) + lane) * 4);
-        bias[q] = a.bo[(4 * hb[q] + (li >> 2)) * C + 4 * cq[q] + (li & 3)];
+        bias[q] = a.bo[wo_tile_row(hb[q], cq[q], li, C)];
 #pragma unroll
         for (int jt = 0; jt < PK; ++jt) gW[q][jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         gb[q] = 0.0f;
@@ -283,7 +283,8 @@ __device__ __forceinline__ void dwo_h2_body(const KArgs& a, int n_sc, int n_st, 
         float v = gb[q];      // this lane: row li of the tile, its samples; the other three k-groups hold the rest
         v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
         if (lk == 0) {
-            float* dst = gp + wo_sz + (4 * hb[q] + (li >> 2)) * C + 4 * cq[q] + (li & 3);
+            float* dst = gp + wo_sz + (4 * hb[q] + (li >> 2)) * C + 4 * cq[q] + (li & 3);      // (element wo_tile_row(hb, cq, li) of dL/dbo,
+            // spelled out to keep this unit's code identical)
             *dst = a.dw2_accum ? *dst + v : v;
         }
     }

@@ -261,7 +261,7 @@ __device__ __forceinline__ void tl_output_pk(const KArgs& a, const float* in, co
     const int per_hb = ncq * npan, nq = nhb_w * per_hb;
     auto wrow_of = [&](int q) {
         const int hb = wave + NWV * (q / per_hb), cq = (q % per_hb) / npan;
-        return a.Wo + (long long)((4 * hb + (li >> 2)) * C + 4 * cq + (li & 3)) * dlast + 4 * lk;
+        return a.Wo + (long long)wo_tile_row(hb, cq, li, C) * dlast + 4 * lk;
     };
     Panel<PK> Pn = tl_load_panel<PK>(wrow_of(0), 0);
     float kacc[NS];
@@ -299,23 +299,25 @@ __device__ __forceinline__ void tl_output_pk(const KArgs& a, const float* in, co
     }
 }
 
-// Same, for the common case K = 16 PK (one panel = the whole tile row block): a straight-line loop body (no branches:
-// the waitcnt pass then keeps the next tile's loads in flight across the MFMAs), two named buffers, unrolled by two.
-// one head tile as fetched: the 16-row weight panel(s) and the bias quad of this lane's D rows
-template <int PK, int GATED>
+// one head tile as fetched: the weights (W: this lane's fragments) and the bias quad of this lane's D rows
+template <class W, int GATED>
 struct TlTile {
-    Panel<PK> P;
+    W w;
     f32x4 bias;
 };
-template <int PK>
-struct TlTile<PK, 1> {
-    Panel<PK> P;
+template <class W>
+struct TlTile<W, 1> {
+    W w;
     f32x4 bias;
-    Panel<PK> G;       // sigmoid head
+    W g;       // sigmoid head
     f32x4 biasg;
 };
 
+// Same, for the common case K = 16 PK (one panel = the whole tile row block): a straight-line loop body (no branches:
+// the waitcnt pass then keeps the next tile's loads in flight across the MFMAs), two named buffers, unrolled by two.
 // GATED: the minimal-gated field (gating.py:7-32) -- a second head Wg, M = sigmoid(Wg x + bg) * tanh(Wo x + bo)
+// (Its own copy of the cursors and the fenced loop of TlWalk / tl_pipeline2 below: on those the one-tile instantiations at 128 wide came
+// out 0.4 - 0.9 % slower at B = 4096.)
 template <int NS, int PK, int NWV, int GATED>
 __device__ __forceinline__ void tl_output_whole(const KArgs& a, const float* in, const float* DX, float* KO, int wave, int lane) {
     constexpr int NSP = NS * 16;
@@ -324,16 +326,16 @@ __device__ __forceinline__ void tl_output_whole(const KArgs& a, const float* in,
     const int nhb_w = (nhb - wave + NWV - 1) / NWV;
     if (nhb_w <= 0) return;
     const int nq = nhb_w * ncq;
-    using TileIn = TlTile<PK, GATED>;
+    using TileIn = TlTile<Panel<PK>, GATED>;
     int fhi = 0, fcq = 0, fq = 0;
     auto fetch = [&]() {
         const int hb = wave + NWV * fhi;
         TileIn t;
         const long long woff = (long long)(hb * ncq + fcq) * (PK * 256);
-        t.P = tl_load_panel_packed<PK>(a.Wo_pk + woff, lane);
+        t.w = tl_load_panel_packed<PK>(a.Wo_pk + woff, lane);
         t.bias = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * C + 4 * fcq);
         if constexpr (GATED != 0) {
-            t.G = tl_load_panel_packed<PK>(a.Wg_pk + woff, lane);
+            t.g = tl_load_panel_packed<PK>(a.Wg_pk + woff, lane);
             t.biasg = *reinterpret_cast<const f32x4*>(a.bg + (4 * hb + lk) * C + 4 * fcq);
         }
         const bool more = fq + 1 < nq, wrap = fcq + 1 == ncq;
@@ -351,11 +353,11 @@ __device__ __forceinline__ void tl_output_whole(const KArgs& a, const float* in,
         f32x4 acc[NS], accg[NS];
 #pragma unroll
         for (int st = 0; st < NS; ++st) acc[st] = t.bias;
-        tl_mma_panel<NS, PK>(t.P, in, 0, li, lk, acc);
+        tl_mma_panel<NS, PK>(t.w, in, 0, li, lk, acc);
         if constexpr (GATED != 0) {
 #pragma unroll
             for (int st = 0; st < NS; ++st) accg[st] = t.biasg;
-            tl_mma_panel<NS, PK>(t.G, in, 0, li, lk, accg);
+            tl_mma_panel<NS, PK>(t.g, in, 0, li, lk, accg);
         }
 #pragma unroll
         for (int st = 0; st < NS; ++st) {
@@ -376,9 +378,7 @@ __device__ __forceinline__ void tl_output_whole(const KArgs& a, const float* in,
     };
     TileIn TA = fetch(), TB;
     for (int i = 0; i < (nq >> 1); ++i) {
-        // the scheduling fences keep each tile's loads a whole tile ahead of their use: left alone, the machine scheduler
-        // sinks them next to the MFMAs that consume them (load, wait, four MFMAs, load, ...), which exposes the L2 latency
-        TB = fetch();
+        TB = fetch();          // fences: see tl_pipeline2
         __builtin_amdgcn_sched_barrier(0);
         step(TA);
         __builtin_amdgcn_sched_barrier(0);
@@ -395,20 +395,6 @@ __device__ __forceinline__ void tl_output_whole(const KArgs& a, const float* in,
 // as three bf16 pieces -- the weights split ONCE per call by ncde_pack_panels_bf (fragment order, 1.5 x the fp32 bytes), the
 // activations split by the layer that produced them (tl_dense_relu_pk, xb) -- and a tile is 6 x (K/32) bf16 MFMAs of 16
 // cycles (ncde_bf3.h: fp32-equivalent, dropped terms <= 3 * 2^-24 relative).
-template <int NCH, int GATED>
-struct BfTile {
-    u32x4 w[NCH][3];
-    f32x4 bias;
-    u32x4 g[GATED ? NCH : 1][3];
-    f32x4 biasg;
-};
-template <int NCH>
-__device__ __forceinline__ void tl_load_bf(const unsigned* tile, int lane, u32x4 (&w)[NCH][3]) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) w[c][p] = *reinterpret_cast<const u32x4*>(tile + ((c * 3 + p) * 64 + lane) * 4);
-}
 // acc += W(tile) x, x read from its split image; two accumulator chains (even / odd chunks)
 template <int NCH>
 __device__ __forceinline__ f32x4 tl_mma_bf(const u32x4 (&w)[NCH][3], const unsigned* xb, int lane, f32x4 acc) {
@@ -435,58 +421,83 @@ __device__ __forceinline__ f32x4 tl_mma_bf(const u32x4 (&w)[NCH][3], const unsig
     return acc;
 }
 
-template <int NCH, int NWV, int GATED>
-__device__ __forceinline__ void tl_output_bf(const KArgs& a, const unsigned* xb, const float* DX, float* KO, int wave, int lane) {
-    constexpr int NSP = 16;
-    const int li = lane & 15, lk = lane >> 4;
-    const int C = a.C, nhb = a.H >> 2, ncq = C >> 2;
-    const int nhb_w = (nhb - wave + NWV - 1) / NWV;
-    if (nhb_w <= 0) return;
-    const int nq = nhb_w * ncq;
-    using TileIn = BfTile<NCH, GATED>;
-    const unsigned* wo = reinterpret_cast<const unsigned*>(a.Wo_pk);
-    const unsigned* wg = reinterpret_cast<const unsigned*>(a.Wg_pk);
-    int fhi = 0, fcq = 0, fq = 0;
-    auto fetch = [&]() {
-        const int hb = wave + NWV * fhi;
-        TileIn t;
-        const long long woff = (long long)(hb * ncq + fcq) * (NCH * 3 * 256);
-        tl_load_bf<NCH>(wo + woff, lane, t.w);
-        t.bias = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * C + 4 * fcq);
-        if constexpr (GATED != 0) {
-            tl_load_bf<NCH>(wg + woff, lane, t.g);
-            t.biasg = *reinterpret_cast<const f32x4*>(a.bg + (4 * hb + lk) * C + 4 * fcq);
-        }
+
+// ---- the streamed walk over the output tiles (K = 16 PK: one panel = the whole tile row block) -----------------------------------
+// A tile FORM says how the weights of one 16-row head tile are kept and multiplied: W (this lane's fragments), Word / kWords (word type
+// and words per tile of the packed image), load, and mma: acc = bias + W(tile) x.  The split-bf16 form is the one on this walk; the
+// fp32 panels (tl_output_whole above) and the split-fp16 tiles (tl_output_h2 below) lose speed on it and keep walks of their own.
+// split-bf16 tiles from ncde_pack_panels_bf: NCH chunks x 3 pieces; x from the split image its layer left (NS = 1)
+template <int NCH>
+struct TlBf3 {
+    struct W {
+        u32x4 p[NCH][3];
+    };
+    using Word = unsigned;
+    static constexpr int kWords = NCH * 3 * 256;
+    static __device__ __forceinline__ W load(const unsigned* tile, int lane) {
+        W w;
+#pragma unroll
+        for (int c = 0; c < NCH; ++c)
+#pragma unroll
+            for (int p = 0; p < 3; ++p) w.p[c][p] = *reinterpret_cast<const u32x4*>(tile + ((c * 3 + p) * 64 + lane) * 4);
+        return w;
+    }
+    static __device__ __forceinline__ void mma(const W& w, const unsigned* xb, int lane, f32x4 bias, f32x4 (&acc)[1]) {
+        acc[0] = tl_mma_bf<NCH>(w.p, xb, lane, bias);
+    }
+};
+
+// The tiles of one wave -- state-unit blocks wave, wave + NWV, ... x every channel quad, nq in all -- and its two positions in them
+template <int NWV>
+struct TlWalk {
+    int wave, ncq, nq;
+    int fhi = 0, fcq = 0, fq = 0;      // the tile to fetch next; stays on the last one (the pipeline fetches one past an even nq)
+    int chi = 0, ccq = 0;              // the tile to compute next
+    __device__ __forceinline__ TlWalk(const KArgs& a, int wave_) : wave(wave_), ncq(a.C >> 2) {
+        const int nhb_w = ((a.H >> 2) - wave + NWV - 1) / NWV;
+        nq = nhb_w > 0 ? nhb_w * ncq : 0;
+    }
+    __device__ __forceinline__ int fetch_hb() const { return wave + NWV * fhi; }
+    __device__ __forceinline__ void fetched() {
         const bool more = fq + 1 < nq, wrap = fcq + 1 == ncq;
         fq += more ? 1 : 0;
         fhi += (more && wrap) ? 1 : 0;
         fcq = more ? (wrap ? 0 : fcq + 1) : fcq;
-        return t;
-    };
-    int chi = 0, ccq = 0;
-    float kacc = 0.0f;
-    auto step = [&](const TileIn& t) {
-        const int hb = wave + NWV * chi;
-        const f32x4 acc = tl_mma_bf<NCH>(t.w, xb, lane, t.bias);
-        f32x4 accg;
-        if constexpr (GATED != 0) accg = tl_mma_bf<NCH>(t.g, xb, lane, t.biasg);
-        const f32x4 dx = *reinterpret_cast<const f32x4*>(DX + (ccq * NSP + li) * 4);
-        float kk = ccq == 0 ? 0.0f : kacc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float m = tanh_dev(acc[r]);
-            if constexpr (GATED != 0) m = tl_sigmoid(accg[r]) * m;
-            kk = fmaf(m, dx[r], kk);
-        }
-        kacc = kk;
-        KO[(hb * NSP + li) * 4 + lk] = kk;     // running sum; the last channel quad leaves the total
+    }
+    __device__ __forceinline__ int hb() const { return wave + NWV * chi; }
+    __device__ __forceinline__ void computed() {
         const bool wrap = ccq + 1 == ncq;
         chi += wrap ? 1 : 0;
         ccq = wrap ? 0 : ccq + 1;
-    };
-    TileIn TA = fetch(), TB;
+    }
+};
+// the next tile of the wave from the packed images wo (and wg: the sigmoid head), with its bias quad(s)
+template <class Form, int GATED, int NWV>
+__device__ __forceinline__ TlTile<typename Form::W, GATED> tl_fetch_tile(const KArgs& a, const typename Form::Word* wo, const typename Form::Word* wg,
+                                                             TlWalk<NWV>& wk, int lane) {
+    const int hb = wk.fetch_hb(), lk = lane >> 4;
+    TlTile<typename Form::W, GATED> t;
+    const long long woff = (long long)(hb * wk.ncq + wk.fcq) * Form::kWords;
+    t.w = Form::load(wo + woff, lane);
+    t.bias = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * a.C + 4 * wk.fcq);
+    if constexpr (GATED != 0) {
+        t.g = Form::load(wg + woff, lane);
+        t.biasg = *reinterpret_cast<const f32x4*>(a.bg + (4 * hb + lk) * a.C + 4 * wk.fcq);
+    }
+    wk.fetched();
+    return t;
+}
+// step(tile) over the nq tiles that fetch() returns in turn: a straight-line loop body (no branches: the waitcnt pass then keeps the
+// next tile's loads in flight across the MFMAs), two named buffers, unrolled by two.
+template <class Fetch, class Step>
+__device__ __forceinline__ void tl_pipeline2(int nq, Fetch fetch, Step step) {
+    if (nq <= 0) return;
+    auto TA = fetch();
+    decltype(TA) TB;
     for (int i = 0; i < (nq >> 1); ++i) {
-        TB = fetch();          // fences: see tl_output_whole
+        // the scheduling fences keep each tile's loads a whole tile ahead of their use: left alone, the machine scheduler
+        // sinks them next to the MFMAs that consume them (load, wait, four MFMAs, load, ...), which exposes the L2 latency
+        TB = fetch();
         __builtin_amdgcn_sched_barrier(0);
         step(TA);
         __builtin_amdgcn_sched_barrier(0);
@@ -498,12 +509,50 @@ __device__ __forceinline__ void tl_output_bf(const KArgs& a, const unsigned* xb,
     if (nq & 1) step(TA);
 }
 
+// output layer + tanh + channel contraction for the h-blocks of this wave -> KO, as tl_output_whole, on the shared cursor and loop
+// (`in`: x_L as the form reads it, NS column tiles)
+template <class Form, int NS, int NWV, int GATED>
+__device__ __forceinline__ void tl_output_tiles(const KArgs& a, const typename Form::Word* in, const float* DX, float* KO, int wave, int lane) {
+    constexpr int NSP = NS * 16;
+    const int li = lane & 15, lk = lane >> 4;
+    using Word = typename Form::Word;
+    const Word* wo = reinterpret_cast<const Word*>(a.Wo_pk);
+    const Word* wg = reinterpret_cast<const Word*>(a.Wg_pk);
+    TlWalk<NWV> wk(a, wave);
+    auto fetch = [&]() { return tl_fetch_tile<Form, GATED>(a, wo, wg, wk, lane); };
+    float kacc[NS];
+#pragma unroll
+    for (int st = 0; st < NS; ++st) kacc[st] = 0.0f;
+    auto step = [&](const TlTile<typename Form::W, GATED>& t) {
+        const int hb = wk.hb();
+        f32x4 acc[NS], accg[NS];
+        Form::mma(t.w, in, lane, t.bias, acc);
+        if constexpr (GATED != 0) Form::mma(t.g, in, lane, t.biasg, accg);
+#pragma unroll
+        for (int st = 0; st < NS; ++st) {
+            const f32x4 dx = *reinterpret_cast<const f32x4*>(DX + (wk.ccq * NSP + st * 16 + li) * 4);
+            float kk = wk.ccq == 0 ? 0.0f : kacc[st];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float m = tanh_dev(acc[st][r]);
+                if constexpr (GATED != 0) m = tl_sigmoid(accg[st][r]) * m;
+                kk = fmaf(m, dx[r], kk);
+            }
+            kacc[st] = kk;
+            KO[(hb * NSP + st * 16 + li) * 4 + lk] = kk;     // running sum; the last channel quad leaves the total
+        }
+        wk.computed();
+    };
+    tl_pipeline2(wk.nq, fetch, step);
+}
 
 // ---- split-fp16 output tiles (round 4; NS = 1, last hidden width a multiple of 32) ------------------------------------------------
 // The forward-side operands -- weights and x_L, O(1) magnitudes -- as TWO fp16 pieces (ncde_bf3.h): 3 f16 MFMAs per K-chunk of 32
 // instead of 6 bf16 ones, and a weight stream of 1.0 x the fp32 bytes instead of 1.5 x -- the stream is what bounds the output
 // phase at cfg5.  The fp16 range is speculated on exactly as in the register-resident family: the
 // workgroup reports a range fault for its sample tile and the split-bf16 instantiation, launched behind it, re-executes that tile.
+// This walk keeps its own copy of the cursors and of the fenced loop of tl_output_tiles: moved onto them, its gated instantiation for a
+// 128-wide last layer (already spilling at 256 registers) came out 3.9 % slower at B = 4096.
 template <int NCH, int GATED>
 struct H2Tile {
     u32x4 w[NCH][2];
@@ -596,7 +645,7 @@ __device__ __forceinline__ void tl_output_h2(const KArgs& a, const unsigned* xb,
     };
     TileIn TA = fetch(), TB;
     for (int i = 0; i < (nq >> 1); ++i) {
-        TB = fetch();          // fences: see tl_output_whole
+        TB = fetch();          // fences: see tl_pipeline2
         __builtin_amdgcn_sched_barrier(0);
         step(TA);
         __builtin_amdgcn_sched_barrier(0);
@@ -614,7 +663,7 @@ __device__ __forceinline__ void tl_output_h2(const KArgs& a, const unsigned* xb,
 // output-layer weights in fragment order (once per call: the parameters change every training step)
 // ------------------------------------------------------------------------------------------------
 // dst[((tile * PK + i) * 64 + lane) * 4 + e] = W[row(tile, lane & 15)][16 i + 4 (lane >> 4) + e], tile = hb * (C/4) + cq,
-// row(tile, li) = (4 hb + (li >> 2)) * C + 4 cq + (li & 3): exactly what lane `lane` feeds the i-th MFMA group of the tile.
+// row(tile, li) = wo_tile_row(hb, cq, li): exactly what lane `lane` feeds the i-th MFMA group of the tile.
 __global__ __launch_bounds__(256) void ncde_pack_panels(const float* __restrict__ W, float* __restrict__ dst, int H, int C, int pk) {
     const long long n = (long long)H * C * pk * 4;          // float4 pieces
     const int ncq = C >> 2;
@@ -623,8 +672,8 @@ __global__ __launch_bounds__(256) void ncde_pack_panels(const float* __restrict_
         const long long ti = v >> 6;
         const int i = (int)(ti % pk);
         const int tile = (int)(ti / pk);
-        const int hb = tile / ncq, cq = tile - hb * ncq, li = lane & 15, lk = lane >> 4;
-        const long long row = (long long)(4 * hb + (li >> 2)) * C + 4 * cq + (li & 3);
+        const int hb = tile / ncq, cq = tile - hb * ncq, lk = lane >> 4;
+        const long long row = wo_tile_row(hb, cq, lane & 15, C);
         reinterpret_cast<f32x4*>(dst)[v] = *reinterpret_cast<const f32x4*>(W + row * (16 * pk) + 16 * i + 4 * lk);
     }
 }
@@ -637,31 +686,24 @@ __global__ __launch_bounds__(256) void ncde_pad_columns(const float* __restrict_
     }
 }
 
-// The split-bf16 copy: word (((tile * NCH + c) * 3 + piece) * 64 + lane) * 4 + dw = bf16 pieces of
-// W[row(tile, lane & 15)][32 c + 8 (lane >> 4) + 2 dw, + 1] -- the A operand of v_mfma_f32_16x16x32_bf16.
-__global__ __launch_bounds__(256) void ncde_pack_panels_bf(const float* __restrict__ W, unsigned* __restrict__ dst, int H, int C, int nch) {
-    const long long n = (long long)H * C / 16 * nch * 64;          // (tile, chunk, lane) triples
-    const int ncq = C >> 2;
-    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < n; v += (long long)gridDim.x * 256) {
-        const int lane = (int)(v & 63);
-        const long long tc = v >> 6;
-        const int c = (int)(tc % nch);
-        const int tile = (int)(tc / nch);
-        const int hb = tile / ncq, cq = tile - hb * ncq, li = lane & 15, kg = lane >> 4;
-        const long long row = (long long)(4 * hb + (li >> 2)) * C + 4 * cq + (li & 3);
-        const float* src = W + row * (32 * nch) + 32 * c + 8 * kg;
-        float vals[8];
-        *reinterpret_cast<f32x4*>(vals) = *reinterpret_cast<const f32x4*>(src);
-        *reinterpret_cast<f32x4*>(vals + 4) = *reinterpret_cast<const f32x4*>(src + 4);
-        const Split3 sp = split8(vals);
-        u32x4* o = reinterpret_cast<u32x4*>(dst) + (tc * 3) * 64 + lane;
-        o[0] = sp.hi; o[64] = sp.mid; o[128] = sp.lo;
-    }
-}
-
-// The split-fp16 copy: word (((tile * NCH + c) * 2 + piece) * 64 + lane) * 4 + dw -- the A operand of v_mfma_f32_16x16x32_f16.
-// A weight outside the fp16 range faults EVERY sample tile: *wfault is set and the forward kernel ORs it into its tile's word.
-__global__ __launch_bounds__(256) void ncde_pack_panels_h2(const float* __restrict__ W, unsigned* __restrict__ dst, int H, int C, int nch, int* wfault) {
+// The split copies: word (((tile * NCH + c) * S::NP + piece) * 64 + lane) * 4 + dw = the pieces of
+// W[row(tile, lane & 15)][32 c + 8 (lane >> 4) + 2 dw, + 1] -- the A operand of v_mfma_f32_16x16x32_bf16 / _f16.
+// S, the split form: pieces per K-chunk of 32, the split of eight weights into this lane's slots (o: the first piece's; mx tracks the
+// largest magnitude split) and the form's range check.  A weight outside the fp16 range faults EVERY sample tile: *wfault is set and the
+// forward kernel ORs it into its tile's word.
+namespace {
+struct TlPackBf3 {
+    static constexpr int NP = 3;
+    static __device__ __forceinline__ void split(const float* v, float&, u32x4* o) { const Split3 sp = split8(v); o[0] = sp.hi; o[64] = sp.mid; o[128] = sp.lo; }
+    static __device__ __forceinline__ bool range_fault(float) { return false; }
+};
+struct TlPackH2 {
+    static constexpr int NP = 2;
+    static __device__ __forceinline__ void split(const float* v, float& mx, u32x4* o) { const Split2h sp = split8h(v, mx); o[0] = sp.hi; o[64] = sp.lo; }
+    static __device__ __forceinline__ bool range_fault(float mx) { return h2_range_fault(mx); }
+};
+template <class S>
+__device__ __forceinline__ void tl_pack_split(const float* __restrict__ W, unsigned* __restrict__ dst, int H, int C, int nch, int* wfault) {
     const long long n = (long long)H * C / 16 * nch * 64;          // (tile, chunk, lane) triples
     const int ncq = C >> 2;
     float mx = 0.0f;
@@ -670,17 +712,21 @@ __global__ __launch_bounds__(256) void ncde_pack_panels_h2(const float* __restri
         const long long tc = v >> 6;
         const int c = (int)(tc % nch);
         const int tile = (int)(tc / nch);
-        const int hb = tile / ncq, cq = tile - hb * ncq, li = lane & 15, kg = lane >> 4;
-        const long long row = (long long)(4 * hb + (li >> 2)) * C + 4 * cq + (li & 3);
-        const float* src = W + row * (32 * nch) + 32 * c + 8 * kg;
+        const int hb = tile / ncq, cq = tile - hb * ncq, kg = lane >> 4;
+        const float* src = W + (long long)wo_tile_row(hb, cq, lane & 15, C) * (32 * nch) + 32 * c + 8 * kg;
         float vals[8];
         *reinterpret_cast<f32x4*>(vals) = *reinterpret_cast<const f32x4*>(src);
         *reinterpret_cast<f32x4*>(vals + 4) = *reinterpret_cast<const f32x4*>(src + 4);
-        const Split2h sp = split8h(vals, mx);
-        u32x4* o = reinterpret_cast<u32x4*>(dst) + (tc * 2) * 64 + lane;
-        o[0] = sp.hi; o[64] = sp.lo;
+        S::split(vals, mx, reinterpret_cast<u32x4*>(dst) + (tc * S::NP) * 64 + lane);
     }
-    if (h2_range_fault(mx)) *wfault = 1;
+    if (S::range_fault(mx)) *wfault = 1;
+}
+}  // namespace
+__global__ __launch_bounds__(256) void ncde_pack_panels_bf(const float* __restrict__ W, unsigned* __restrict__ dst, int H, int C, int nch) {
+    tl_pack_split<TlPackBf3>(W, dst, H, C, nch, nullptr);
+}
+__global__ __launch_bounds__(256) void ncde_pack_panels_h2(const float* __restrict__ W, unsigned* __restrict__ dst, int H, int C, int nch, int* wfault) {
+    tl_pack_split<TlPackH2>(W, dst, H, C, nch, wfault);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1092,9 +1138,9 @@ __global__ __launch_bounds__(64 * NWV) void ncde_fwd_tiled(KArgs a) {
                 }
             } else if constexpr (BF != 0) {
                 switch (nkb_o) {
-                    case 8: tl_output_bf<4, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
-                    case 4: tl_output_bf<2, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
-                    default: tl_output_bf<1, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
+                    case 8: tl_output_tiles<TlBf3<4>, 1, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
+                    case 4: tl_output_tiles<TlBf3<2>, 1, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
+                    default: tl_output_tiles<TlBf3<1>, 1, NWV, GATED>(a, XB, DX, KO, wave, lane); break;
                 }
             } else
             switch (nkb_o) {
@@ -1187,8 +1233,11 @@ __global__ __launch_bounds__(64 * NWV) void ncde_fwd_tiled(KArgs a) {
 namespace {
 
 template <int PK>
-using WoTile = TlTile<PK, 0>;
+using WoTile = TlTile<Panel<PK>, 0>;
 
+// The sweep's walk over the output tiles: the tile types of tl_output_tiles, but its own copy of the cursors and of the fenced loop --
+// moved onto TlWalk / tl_pipeline2, its split-bf16 instantiation with resident hidden matrices spilled more (scratch 360 -> 388 bytes)
+// and the sweep at (C, H, HH) = (16, 64, 64), B = 4096 came out 4.7 % slower.
 // RES = 1: the (at most two) output tiles of this wave are resident in registers (`res`), nothing is fetched.
 // BFP = 1 (original field, streamed weights): P from the split-bf16 copy of the tile (prefetched a tile ahead) and the split
 // image xb of x_L; the fp32 copy of the SAME tile, needed only for the transposed products, is requested at the top of the
@@ -1213,21 +1262,17 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
     for (int jt = 0; jt < PK; ++jt) accJ[jt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     const int nhb_w = (nhb - wave + NWV - 1) / NWV;
     const int nq = nhb_w > 0 ? nhb_w * ncq : 0;
-    struct BfIn {
-        u32x4 w[NCH][3];
-        f32x4 bias;
-    };
-    using TileIn = std::conditional_t<BFP != 0, BfIn, TlTile<PK, GATED>>;
+    using TileIn = std::conditional_t<BFP != 0, TlTile<typename TlBf3<NCH>::W, 0>, TlTile<Panel<PK>, GATED>>;
     int fhi = 0, fcq = 0, fq = 0;
     auto fetch = [&]() {
         const int hb = wave + NWV * fhi;
         TileIn t;
         const long long woff = (long long)(hb * ncq + fcq) * (PK * 256);
-        if constexpr (BFP != 0) tl_load_bf<NCH>(a.Wo_bf + (long long)(hb * ncq + fcq) * (NCH * 3 * 256), lane, t.w);
-        else t.P = tl_load_panel_packed<PK>(a.Wo_pk + woff, lane);
+        if constexpr (BFP != 0) t.w = TlBf3<NCH>::load(a.Wo_bf + (long long)(hb * ncq + fcq) * TlBf3<NCH>::kWords, lane);
+        else t.w = tl_load_panel_packed<PK>(a.Wo_pk + woff, lane);
         t.bias = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * C + 4 * fcq);
         if constexpr (GATED != 0) {
-            t.G = tl_load_panel_packed<PK>(a.Wg_pk + woff, lane);
+            t.g = tl_load_panel_packed<PK>(a.Wg_pk + woff, lane);
             t.biasg = *reinterpret_cast<const f32x4*>(a.bg + (4 * hb + lk) * C + 4 * fcq);
         }
         const bool more = fq + 1 < nq, wrap = fcq + 1 == ncq;
@@ -1244,14 +1289,14 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
         f32x4 acc[1];
         if constexpr (BFP != 0) {
             const Panel<PK> Pf = tl_load_panel_packed<PK>(a.Wo_pk + (long long)(hb * ncq + cq) * (PK * 256), lane);
-            acc[0] = tl_mma_bf<NCH>(t.w, xb, lane, t.bias);
+            acc[0] = tl_mma_bf<NCH>(t.w.p, xb, lane, t.bias);
 #pragma unroll
             for (int i = 0; i < PK; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = Pf.v[i];
         } else {
 #pragma unroll
-            for (int i = 0; i < PKH; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.P.v[i];
+            for (int i = 0; i < PKH; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.w.v[i];
             acc[0] = t.bias;
-            tl_mma_panel<1, PK>(t.P, xL, 0, li, lk, acc);
+            tl_mma_panel<1, PK>(t.w, xL, 0, li, lk, acc);
         }
         const float aval = AS[(hb * NSP + li) * 4 + lk];
         const f32x4 dx = *reinterpret_cast<const f32x4*>(DX + (cq * NSP + li) * 4);
@@ -1260,7 +1305,7 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
         f32x4 accg[1];
         if constexpr (GATED != 0) {
             accg[0] = t.biasg;
-            tl_mma_panel<1, PK>(t.G, xL, 0, li, lk, accg);
+            tl_mma_panel<1, PK>(t.g, xL, 0, li, lk, accg);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1283,10 +1328,10 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
         for (int jt = 0; jt < PKH; ++jt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) accJ[jt] = mfma16(scr[(4 * lk + r) * SCS + 16 * jt + li], dP[r], accJ[jt]);
-        if constexpr (PK > 8) {         // k-blocks 8 .. 15 through the same scratch (fp32 tiles only: t.P is the tile)
+        if constexpr (PK > 8) {         // k-blocks 8 .. 15 through the same scratch (fp32 tiles only: t.w is the tile)
             if constexpr (BFP == 0) {
 #pragma unroll
-                for (int i = 0; i < PKH; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.P.v[PKH + i];
+                for (int i = 0; i < PKH; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.w.v[PKH + i];
             }
 #pragma unroll
             for (int jt = 0; jt < PKH; ++jt)
@@ -1295,7 +1340,7 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
         }
         if constexpr (GATED != 0) {     // ... + sum_u Wg[u][j] dPg[u][s], through the same scratch
 #pragma unroll
-            for (int i = 0; i < PK; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.G.v[i];
+            for (int i = 0; i < PK; ++i) *reinterpret_cast<f32x4*>(scr + li * SCS + 16 * i + 4 * lk) = t.g.v[i];
 #pragma unroll
             for (int jt = 0; jt < PK; ++jt)
 #pragma unroll
@@ -1312,7 +1357,7 @@ __device__ __forceinline__ void tl_output_vjp(const KArgs& a, const float* xL, c
         if (nq > 0) {
             TileIn TA = fetch(), TB;
             for (int i = 0; i < (nq >> 1); ++i) {
-                TB = fetch();          // fences: see tl_output_whole
+                TB = fetch();          // fences: see tl_pipeline2
                 __builtin_amdgcn_sched_barrier(0);
                 step(TA);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1643,7 +1688,7 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
             for (int q = 0; q < 2; ++q) {
                 int hb = wave + NWV * (q / ncq), cq = q % ncq;
                 if (hb >= nhb) { hb = 0; cq = 0; }
-                wo[q].P = tl_load_panel<PK>(a.Wo + (long long)((4 * hb + (li >> 2)) * C + 4 * cq + (li & 3)) * dlast + 4 * lk, 0);
+                wo[q].w = tl_load_panel<PK>(a.Wo + (long long)wo_tile_row(hb, cq, li, C) * dlast + 4 * lk, 0);
                 wo[q].bias = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb + lk) * C + 4 * cq);
             }
         }
@@ -2501,6 +2546,44 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
 // measured at cfg5 with one tile per wave the pass moved 13.7 TB/s through the L2 (3.9 M fragments x 16 KB per 4.7 ms
 // window) and sat at that, not at the MFMA rate.  One wave per SIMD, so the 512-register file holds NRT = 4 tiles.
 // (fp32 records; the sweep's split-record mode is consumed by ncde_dwo_pair below)
+
+// The end of pass B for one row tile (hb, cq): the four waves' accumulators gW / gb are summed through `red`, PKR column tiles at a
+// time (16 x 256 floats x 4 waves would not fit the 64 KB of static LDS), and written to the partial gp -- added to what the earlier
+// time windows left there when a.resume.  first: nothing of the workgroup is in `red` yet (no barrier needed in front).
+template <int PK, int PKR>
+__device__ __forceinline__ void tl_dwo_reduce(const KArgs& a, const f32x4 (&gW)[PK], const float (&gb)[4], float (&red)[4][PKR * 256 + 64],
+                                              float* gp, int hb, int cq, bool first, int tid) {
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lk = lane >> 4;
+    const int C = a.C, dlast = 16 * PK;
+#pragma unroll
+    for (int j0 = 0; j0 < PK; j0 += PKR) {
+        if (!first || j0 > 0) __syncthreads();
+#pragma unroll
+        for (int jt = 0; jt < PKR; ++jt) *reinterpret_cast<f32x4*>(&red[wave][(jt * 64 + lane) * 4]) = gW[j0 + jt];
+        if (j0 == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = gb[r];
+                v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
+                if (li == 0) red[wave][PKR * 256 + 4 * lk + r] = v;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < PKR * 256; e += 256) {
+            const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
+            const int r = e & 3, ln = (e >> 2) & 63, jt = j0 + (e >> 8);
+            const int row = wo_tile_row(hb, cq, 4 * (ln >> 4) + r, C);      // (D row 4 lk + r of lane ln)
+            float* dst = gp + (long long)row * dlast + 16 * jt + (ln & 15);
+            *dst = a.resume ? *dst + v : v;
+        }
+        if (j0 == 0 && tid < 16) {
+            const float v = (red[0][PKR * 256 + tid] + red[1][PKR * 256 + tid]) + (red[2][PKR * 256 + tid] + red[3][PKR * 256 + tid]);
+            float* dst = gp + (long long)a.H * C * dlast + wo_tile_row(hb, cq, tid, C);      // (dL/dbo follows dL/dWo)
+            *dst = a.resume ? *dst + v : v;
+        }
+    }
+}
+
 template <int PK, int HEAD = 0, int NRT = 1>
 __global__ __launch_bounds__(256) void ncde_dwo_tiled(KArgs a, int n_sc, int n_st, float* gpartB) {
     // n_sc = stages recorded in this time window; a.resume != 0: add to the partial the earlier windows left in gpartB
@@ -2526,7 +2609,7 @@ __global__ __launch_bounds__(256) void ncde_dwo_tiled(KArgs a, int n_sc, int n_s
         const int tile = blockIdx.x * NRT + rt;
         hb[rt] = tile / ncq;
         cq[rt] = tile - hb[rt] * ncq;
-        const long long woff = (long long)((4 * hb[rt] + (li >> 2)) * C + 4 * cq[rt] + (li & 3)) * dlast + 4 * lk;
+        const long long woff = (long long)wo_tile_row(hb[rt], cq[rt], li, C) * dlast + 4 * lk;
         bv[rt] = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb[rt] + lk) * C + 4 * cq[rt]);
         Wp[rt] = tl_load_panel<PK>(a.Wo + woff, 0);
         if constexpr (HEAD != 0) {
@@ -2627,35 +2710,7 @@ __global__ __launch_bounds__(256) void ncde_dwo_tiled(KArgs a, int n_sc, int n_s
     const long long wo_sz = (long long)H * C * dlast, theta_o = wo_sz + (long long)H * C;
     float* gp = gpartB + (long long)blockIdx.y * theta_o;
 #pragma unroll
-    for (int rt = 0; rt < NRT; ++rt) {
-#pragma unroll
-        for (int j0 = 0; j0 < PK; j0 += PKR) {
-            if (rt > 0 || j0 > 0) __syncthreads();
-#pragma unroll
-            for (int jt = 0; jt < PKR; ++jt) *reinterpret_cast<f32x4*>(&red[wave][(jt * 64 + lane) * 4]) = gW[rt][j0 + jt];
-            if (j0 == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = gb[rt][r];
-                    v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
-                    if (li == 0) red[wave][PKR * 256 + 4 * lk + r] = v;
-                }
-            }
-            __syncthreads();
-            for (int e = tid; e < PKR * 256; e += 256) {
-                const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-                const int r = e & 3, ln = (e >> 2) & 63, jt = j0 + (e >> 8);
-                const int row = (4 * hb[rt] + (ln >> 4)) * C + 4 * cq[rt] + r;
-                float* dst = gp + (long long)row * dlast + 16 * jt + (ln & 15);
-                *dst = a.resume ? *dst + v : v;
-            }
-            if (j0 == 0 && tid < 16) {
-                const float v = (red[0][PKR * 256 + tid] + red[1][PKR * 256 + tid]) + (red[2][PKR * 256 + tid] + red[3][PKR * 256 + tid]);
-                float* dst = gp + wo_sz + (4 * hb[rt] + (tid >> 2)) * C + 4 * cq[rt] + (tid & 3);
-                *dst = a.resume ? *dst + v : v;
-            }
-        }
-    }
+    for (int rt = 0; rt < NRT; ++rt) tl_dwo_reduce<PK, PKR>(a, gW[rt], gb[rt], red, gp, hb[rt], cq[rt], rt == 0, tid);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2692,7 +2747,7 @@ __global__ __launch_bounds__(256) void ncde_dwo_pair(KArgs a, int n_sc, int n_st
         const int tile = blockIdx.x * NRT + rt;
         hb[rt] = tile / ncq;
         cq[rt] = tile - hb[rt] * ncq;
-        const long long wrow = (long long)((4 * hb[rt] + (li >> 2)) * C + 4 * cq[rt] + (li & 3)) * dlast;
+        const long long wrow = (long long)wo_tile_row(hb[rt], cq[rt], li, C) * dlast;
         bv[rt] = *reinterpret_cast<const f32x4*>(a.bo + (4 * hb[rt] + lk) * C + 4 * cq[rt]);
         if constexpr (HEAD != 0) bq[rt] = *reinterpret_cast<const f32x4*>(a.bg + (4 * hb[rt] + lk) * C + 4 * cq[rt]);
 #pragma unroll
@@ -2876,28 +2931,7 @@ __global__ __launch_bounds__(256) void ncde_dwo_pair(KArgs a, int n_sc, int n_st
         const int hh = hr / NRT, rt = hr - hh * NRT;
         // HEAD 3: the gate head's partials follow the tanh head's gridDim.y partials (the host's gB2 = gB + parts * theta_o)
         float* gp = gpartB + ((long long)hh * gridDim.y + blockIdx.y) * theta_o;
-        if (hr > 0) __syncthreads();
-#pragma unroll
-        for (int jt = 0; jt < PK; ++jt) *reinterpret_cast<f32x4*>(&red[wave][(jt * 64 + lane) * 4]) = gW[hh][rt][jt];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = gb[hh][rt][r];
-            v += __shfl_xor(v, 8, 64); v += __shfl_xor(v, 4, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 1, 64);
-            if (li == 0) red[wave][PK * 256 + 4 * lk + r] = v;
-        }
-        __syncthreads();
-        for (int e = tid; e < PK * 256; e += 256) {
-            const float v = (red[0][e] + red[1][e]) + (red[2][e] + red[3][e]);
-            const int r = e & 3, ln = (e >> 2) & 63, jt = e >> 8;
-            const int row = (4 * hb[rt] + (ln >> 4)) * C + 4 * cq[rt] + r;
-            float* dst = gp + (long long)row * dlast + 16 * jt + (ln & 15);
-            *dst = a.resume ? *dst + v : v;
-        }
-        if (tid < 16) {
-            const float v = (red[0][PK * 256 + tid] + red[1][PK * 256 + tid]) + (red[2][PK * 256 + tid] + red[3][PK * 256 + tid]);
-            float* dst = gp + wo_sz + (4 * hb[rt] + (tid >> 2)) * C + 4 * cq[rt] + (tid & 3);
-            *dst = a.resume ? *dst + v : v;
-        }
+        tl_dwo_reduce<PK, PK>(a, gW[hh][rt], gb[hh][rt], red, gp, hb[rt], cq[rt], hr == 0, tid);
     }
 }
 

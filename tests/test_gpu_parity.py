@@ -1086,6 +1086,7 @@ def test_tiled_minimal_gated_vs_oracle(shape, interp, method, seq, gpu_lib):
     gradient pass per head): forward, continuous adjoint and exact discrete backward against the oracle, and against the
     variant kernels on the generic structure."""
     import gpu_util
+    from ncde_amd import _lib
     C, H, HH, nl = shape
     case = _seeded_case(interp, method, seq, B=37, L=6, C=C, H=H, HH=HH, nl=nl, seed=700 + C, kind="minimal")
     ex = case["expect"]
@@ -1098,6 +1099,9 @@ def test_tiled_minimal_gated_vs_oracle(shape, interp, method, seq, gpu_lib):
     for flag in (0x1000, 0x2000, 0x4000):
         rn = gpu_util.run_case(case, flags=flag, need_grads=False)
         assert gu.relerr(rn["z_out"], ex["z_out"]) <= TIGHT_Z, (flag, rn["kernels"])
+    # one sample tile: both heads on the split-bf16 output tiles (1, 1, 2, 4 chunks of 32 at these widths)
+    rn = gpu_util.run_case(case, flags=0x1000 | _lib.FLAG_SPLIT_BF16, need_grads=False)
+    assert rn["kernels"][0] == "ncde_fwd_tiled<NS1,gated,bf16>" and gu.relerr(rn["z_out"], ex["z_out"]) <= TIGHT_Z, rn["kernels"]
     iso = gpu_util.run_adjoint_direct(case, ex["z_out"])
     for k, e in _grad_errors(case, iso).items():
         assert e <= TIGHT_G, ("gated tiled adjoint", k, e)
