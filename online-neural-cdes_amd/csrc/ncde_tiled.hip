@@ -2081,7 +2081,9 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
                     // the Butcher k-registers wait in LDS arrays that are dead until the reduction (KOY, KOA, G0, G1: 2048 floats each)
 #pragma unroll
                     for (int q = 0; q < TL_EADJ; ++q) {
-                        if (q * NT < HS) {      // (H < 128: the upper slots of the state slice are unused, the LDS arrays hold HS floats)
+                        if (q * NT + tid < HS) {      // (H < 128: the upper slots of the state slice are unused, the LDS arrays hold HS floats --
+                            // per THREAD where H is no multiple of 32: HS = 16 H ends inside a round of NT = 512, and the threads past it would
+                            // write their unused slots over the head of the next array, AS's over the ky1 just parked in KOY)
                             KOY[q * NT + tid] = ky1[q]; KOA[q * NT + tid] = ky2[q];
                             G0[q * NT + tid] = ka1[q]; G1[q * NT + tid] = ka2[q];
                             AS[q * NT + tid] = y0[q]; reinterpret_cast<float*>(XBA)[q * NT + tid] = a0[q];      // (a and the split image: recorded above)
@@ -2294,7 +2296,7 @@ __global__ __launch_bounds__(64 * NWV) void ncde_adj_tiled(KArgs a) {
                     TL_TICK(10)
 #pragma unroll
                     for (int q = 0; q < TL_EADJ; ++q) {
-                        if (q * NT < HS) {
+                        if (q * NT + tid < HS) {
                             ky1[q] = KOY[q * NT + tid]; ky2[q] = KOA[q * NT + tid];
                             ka1[q] = G0[q * NT + tid]; ka2[q] = G1[q * NT + tid];
                             y0[q] = AS[q * NT + tid]; a0[q] = reinterpret_cast<const float*>(XBA)[q * NT + tid];
